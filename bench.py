@@ -10,6 +10,11 @@ One step = one pass of the hot path over one batch of synthetic images already r
   per-class NMS 0.6) -> ClipBoxes, plus (N > 1) one RCCL all-gather of the padded detections.
 Per GPU: 16 images of 3x640x640 fp32 (weak scaling: the global batch is 16*N), 80 classes, random-init weights
 with randomised BN statistics, seeded.  Rank 0 prints ONE JSON line (see DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds every other measurement after the
+timed region (per-kernel-family rooflines, parity against the CPU oracle, the f16x3 / mixed modes, the NMS and
+post-process micro-benchmarks, the training-step diagnostic, the CPU baseline).  --dump-outputs DIR writes what the
+last timed step returned as DIR/<name>.npy (float32 / float64), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -589,8 +594,6 @@ def train_mode(args, rank, world, dev, use_dist, out=sys.stdout):
     """`--mode train` (SURVEY Cfg4): the reference's train.py step on N GPUs -- DistributedDataParallel around the model
     (gradient all-reduce over RCCL, bucketed and overlapped with backward by DDP), HIP forward / backward / target /
     loss kernels, SGD.  Weak scaling: --batch images of --size per GPU (defaults 16 x 512 x 512, 20 classes: voc.yaml)."""
-    from pytorch_object_detection_amd import ops
-    from pytorch_object_detection_amd._lib import Segs
     from pytorch_object_detection_amd.model.loss import FCOSLoss
     from pytorch_object_detection_amd.model.modules.head import FCOSGenTargets
     from pytorch_object_detection_amd.model.od import HalfInvertedStageFCOS
@@ -673,6 +676,35 @@ def train_mode(args, rank, world, dev, use_dist, out=sys.stdout):
         el = float(t.item())
     if rank != 0:
         return
+    if args.dump_outputs:       # the last step's loss and the weights it updated (a fixed, seeded sample of 4 Mi of them)
+        import numpy as np
+        flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters() if p.requires_grad])
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), min(flat.numel(), 1 << 22), replace=False))
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().double().reshape(1), "params": flat[torch.from_numpy(idx).to(dev)]})
+    line = {
+        "metric": f"images/sec HISFCOS-R50 {size}x{size} train step (GIoU loss, SGD)", "value": round(batch * world * args.steps / el, 2),
+        "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(el / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f16 operands / f32 accumulate in every dense conv: forward, data gradient, weight gradient (torch.autocast + GradScaler, the reference's AMP arithmetic); norms, depthwise, losses f32" if amp else "f32",
+        "data": "synthetic", "amp": amp,
+        "config": {"workload": f"HISFCOS-R50 train.py step, {batch} x {size}x{size} images/GPU, {ncls} classes, 8 GT boxes/image, "
+                               "HIP forward/backward/target/loss kernels" + (", DDP gradient all-reduce + SyncBatchNorm statistics all-reduces over RCCL" if use_dist else ""),
+                   "batchnorm": "backbone frozen (eval); FPN BatchNorms on batch statistics" + (" over all ranks (SyncBatchNorm on the HIP statistics kernels)" if use_dist else ""),
+                   "step_enqueue": step_mode,
+                   "optimizer": "SGD momentum 0.9" + (", fused=True (GradScaler's found_inf handled on the device: no host synchronisation per step)" if fused_opt else ""),
+                   "amp_activation_maps": ("f16 in HBM inside the ResNet bottlenecks (train_ops.AMP_F16_STORE), fp32 elsewhere" if amp else None),
+                   "global_batch": batch * world, "parallelism": f"dp{world} (DistributedDataParallel)"},
+        "final_loss": round(float(loss.detach()), 5)}
+    if args.full:
+        line.update(train_rooflines(args, dev, size, batch, amp))
+    print(json.dumps(line), file=out, flush=True)
+
+
+def train_rooflines(args, dev, size: int, batch: int, amp: bool) -> dict:
+    """--full, `--mode train`: kernel rooflines timed on their own after the timed steps -- the head tower's weight gradient (`roofline`)
+    and, under --amp, its f16 forward (`roofline_amp_f16`)."""
+    from pytorch_object_detection_amd import ops
+    from pytorch_object_detection_amd._lib import Segs
     # roofline of the dominant backward kernel: the weight gradient of the head tower 3x3 (256 -> 256, all five levels)
     lv = [(size // st, size // st) for st in (8, 16, 32, 64, 128)]
     segs = Segs.make(batch, lv)
@@ -715,25 +747,12 @@ def train_mode(args, rank, world, dev, use_dist, out=sys.stdout):
                               ("f16 activation map in (the step stores the towers' input as f16), fp32 out" if z16 else "fp32 activation map in"),
                     "instruction": "v_mfma_f32_32x32x16_f16", "achieved": round(tfl / (tms * 1e-3) / 1e12, 1), "peak": 2500.0, "unit": "TFLOP/s",
                     "frac": round(tfl / (tms * 1e-3) / 1e12 / 2500.0, 4), "traffic": None, "flops_per_launch": tfl, "avg_launch_ms": round(tms, 4)}
-    print(json.dumps({
-        "metric": f"images/sec HISFCOS-R50 {size}x{size} train step (GIoU loss, SGD)", "value": round(batch * world * args.steps / el, 2),
-        "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(el / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f16 operands / f32 accumulate in every dense conv: forward, data gradient, weight gradient (torch.autocast + GradScaler, the reference's AMP arithmetic); norms, depthwise, losses f32" if amp else "f32",
-        "data": "synthetic", "amp": amp, "roofline_amp_f16": amp_roof,
-        "config": {"workload": f"HISFCOS-R50 train.py step, {batch} x {size}x{size} images/GPU, {ncls} classes, 8 GT boxes/image, "
-                               "HIP forward/backward/target/loss kernels" + (", DDP gradient all-reduce + SyncBatchNorm statistics all-reduces over RCCL" if use_dist else ""),
-                   "batchnorm": "backbone frozen (eval); FPN BatchNorms on batch statistics" + (" over all ranks (SyncBatchNorm on the HIP statistics kernels)" if use_dist else ""),
-                   "step_enqueue": step_mode,
-                   "optimizer": "SGD momentum 0.9" + (", fused=True (GradScaler's found_inf handled on the device: no host synchronisation per step)" if fused_opt else ""),
-                   "amp_activation_maps": ("f16 in HBM inside the ResNet bottlenecks (train_ops.AMP_F16_STORE), fp32 elsewhere" if amp else None),
-                   "global_batch": batch * world, "parallelism": f"dp{world} (DistributedDataParallel)"},
-        "roofline": {"bound": "mfma", "kernel": ("conv_wgrad_f16_kernel" if wprec else "conv_wgrad_kernel") + " (head tower 3x3 weight gradient, 5 levels) + ordered slab reduce",
-                     "instruction": "v_mfma_f32_32x32x16_f16" if wprec else "v_mfma_f32_32x32x2_f32", "achieved": round(ach, 2),
-                     "peak": 2500.0 if wprec else PEAK_F32_MFMA_TFLOPS,
-                     "unit": "TFLOP/s", "frac": round(ach / (2500.0 if wprec else PEAK_F32_MFMA_TFLOPS), 4), "traffic": None,
-                     "flops_per_launch": wflops, "avg_launch_ms": round(wms, 4)},
-        "final_loss": round(float(loss.detach()), 5)}), file=out, flush=True)
+    return {"roofline_amp_f16": amp_roof,
+            "roofline": {"bound": "mfma", "kernel": ("conv_wgrad_f16_kernel" if wprec else "conv_wgrad_kernel") + " (head tower 3x3 weight gradient, 5 levels) + ordered slab reduce",
+                         "instruction": "v_mfma_f32_32x32x16_f16" if wprec else "v_mfma_f32_32x32x2_f32", "achieved": round(ach, 2),
+                         "peak": 2500.0 if wprec else PEAK_F32_MFMA_TFLOPS,
+                         "unit": "TFLOP/s", "frac": round(ach / (2500.0 if wprec else PEAK_F32_MFMA_TFLOPS), 4), "traffic": None,
+                         "flops_per_launch": wflops, "avg_launch_ms": round(wms, 4)}}
 
 
 def layer_times(plan, x, path, reps=5):
@@ -761,6 +780,32 @@ def layer_times(plan, x, path, reps=5):
             fl = plan.step_flops.get(i, 0)
             f.write(f"{i}\t{name}\t{ms:.4f}\t{fl / 1e9:.2f}\t{(fl / (ms * 1e-3) / 1e12) if fl else 0:.1f}\t{plan.tiles.get(name, '')}\n")
         f.write(f"#total_ms\t{tot:.3f}\n")
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """--dump-outputs: write every array as <path>/<name>.npy, float64 where it is float64 and float32 otherwise (class ids and
+    counts are small integers, exact in float32).  The arrays together stay within `budget` bytes: smallest first, an array larger
+    than an equal share of what is left of the budget is replaced by its elements at a fixed, seeded set of flat indices (the same
+    set in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        out[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    left = budget
+    order = sorted(out, key=lambda n: out[n].nbytes)
+    for k, name in enumerate(order):
+        a = out[name]
+        share = left // (len(order) - k)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _claim_stdout():
@@ -847,6 +892,11 @@ def main():
     ap.add_argument("--save-tuning", action="store_true", help="write the conv tile table measured in this run back to tuned/gfx950_tiles.json")
     ap.add_argument("--no-train-step", action="store_true", help="skip the Cfg4 training-step diagnostic")
     ap.add_argument("--layer-times", default="", help="diagnostic: write per-plan-step timings (TSV) to this file and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement of the line (kernel-family rooflines, parity vs the CPU oracle, "
+                         "f16x3 / mixed modes, NMS / post-process micro-benchmarks, training-step diagnostic, CPU baseline; --mode train: its rooflines)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
     hw = [int(v) for v in str(args.size).lower().split("x")]
     args.height, args.width = (hw[0], hw[0]) if len(hw) == 1 else (hw[0], hw[1])
@@ -911,7 +961,7 @@ def main():
     model = build_model(args.classes, seed=0, name=args.model)
     if args.model != "HISFCOS":
         args.no_cpu_baseline = True   # the CPU-baseline leg restates HISFCOS only
-    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if (rank == 0 and world == 1 and args.full and not args.no_cpu_baseline) else None
     model.to(dev)
     if args.graph:
         model.use_graph, args.inflight = True, 1
@@ -983,16 +1033,22 @@ def main():
         el = float(t.item())
 
     if rank == 0:
-        if args.graph:      # (a replayed graph has no per-launch events: tower / NMS times come from the same plans launched eagerly afterwards)
+        if args.dump_outputs:   # (before anything else runs on the device: what the last timed step returned)
+            dump_outputs(args.dump_outputs, dict(zip(("scores", "classes", "boxes", "counts"), res)))
+        # the head-tower and NMS events were recorded inside the timed steps; a replayed graph has none: with --full its tower / NMS
+        # times come from the same plans launched eagerly afterwards, a plain --graph run reports neither
+        step_events = not args.graph
+        if args.graph and args.full:
             for i in range(args.steps):
                 post(model(x, events={"head.tower3x3": ev_pairs[i]}), x, i)
             torch.cuda.synchronize()
+            step_events = True
         images = args.batch * world * args.steps
-        tower_ms = sum(a.elapsed_time(b) for a, b in ev_pairs) / args.steps
-        nms_ms = sum(a.elapsed_time(b) for a, b in nms_pairs) / args.steps
         ms_step = el / args.steps * 1e3
-        fams = family_rooflines(plan, x)
-        step_ms = fams.pop("_step_ms")
+        fams = step_ms = None
+        if args.full:
+            fams = family_rooflines(plan, x)
+            step_ms = fams.pop("_step_ms")
         workload = {"model": args.model, "batch": args.batch, "height": args.height, "width": args.width}
         line = {
             "metric": f"images/sec {args.model if '-' in args.model else args.model + '-R50'} {args.height}x{args.width} inference",
@@ -1004,9 +1060,7 @@ def main():
                                    + (", RCCL detection all-gather" if world > 1 else ""),
                        "global_batch": args.batch * world, "parallelism": f"dp{world} (image-sharded)",
                        "batches_in_flight": args.inflight, "hip_graph": bool(args.graph)},
-            "roofline": tower_roofline(plan, tower_ms, workload, layer_ms=tower_layer_ms(plan, step_ms)),
             "model_conv_tflops": round(plan.flops / (ms_step * 1e-3) / 1e12, 2),
-            "nms_boxes_per_ms": round(args.batch * 1000 / nms_ms, 1), "nms_ms": round(nms_ms, 4),
             "detections_kept_rank0": [int(v) for v in res[3][:args.batch].tolist()][:4],
             "kept_mean": round(float(res[3][:args.batch].float().mean()), 1),
             "parity_note": ("per-stage results on identical inputs are bit-exact vs the oracle (decode boxes, top-k order, NMS kept indices, "
@@ -1017,29 +1071,35 @@ def main():
                             "runs differ by 4e-6 relative between thread counts (SURVEY section 7); `max_abs` is reported beside it, not asserted"),
         }
         line["head_calibrated"] = True      # bench.calibrate_head rescales the prediction layers (since round 3): lines of rounds 1-2 ran an NMS that kept all 1000 candidates
-        if sd_cpu is not None:
-            line["max_err_over_1_plus_abs_vs_oracle"] = parity_vs_oracle(model, x, sd_cpu)
-        f1 = fams.get("1x1")
-        if f1:
-            line["roofline_1x1"] = {"bound": "mfma", "kernel": "conv_igemm_kernel / conv1x1 family: every GEMM-addressed 1x1 conv of the plan "
-                                    f"({f1['launches']} launches)", "instruction": "v_mfma_f32_32x32x2_f32",
-                                    "achieved": f1["executed_tflops"], "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                                    "frac": f1["frac_of_f32_mfma_peak"], "family_ms": f1["ms"], "family_gflop": f1["algorithmic_gflop"],
-                                    "timing": "sum of per-launch HIP-event times, one batch in flight, median of 5 passes after the timed region"}
-        line["kernel_families"] = fams
-        if world == 1 and not args.no_fast_mode:
-            line["fast_mode"] = fast_mode(model, head, clip, x, args, res)
-            line["fast_mode_mixed"] = fast_mode(model, head, clip, x, args, res, "mixed")
-        if world == 1:
-            line["nms_micro"] = nms_micro(dev, args.batch, with_cpu=sd_cpu is not None)
-            line["postproc"] = postproc_bench(dev, args.classes)
-            line["note_end_to_end_nms"] = ("the bench head is calibrated (bench.calibrate_head, seeded): the timed end-to-end step's NMS suppresses "
-                                           "most of its 1000 candidates per image (kept_mean); nms_micro / postproc are SURVEY 8d's synthetic workloads")
-        if world == 1 and not args.no_train_step:
-            line["train_step"] = train_step(dev)
-        if sd_cpu is not None:
-            line["cpu_baseline"] = cpu_baseline(sd_cpu, args.classes, args.height)
-            line["cpu_baseline"]["hip_beside_legs"] = gpu_legs_beside_cpu(dev, args.height)
+        if step_events:
+            tower_ms = sum(a.elapsed_time(b) for a, b in ev_pairs) / args.steps
+            nms_ms = sum(a.elapsed_time(b) for a, b in nms_pairs) / args.steps
+            line["roofline"] = tower_roofline(plan, tower_ms, workload, layer_ms=tower_layer_ms(plan, step_ms) if step_ms is not None else None)
+            line["nms_boxes_per_ms"], line["nms_ms"] = round(args.batch * 1000 / nms_ms, 1), round(nms_ms, 4)
+        if args.full:
+            if sd_cpu is not None:
+                line["max_err_over_1_plus_abs_vs_oracle"] = parity_vs_oracle(model, x, sd_cpu)
+            f1 = fams.get("1x1")
+            if f1:
+                line["roofline_1x1"] = {"bound": "mfma", "kernel": "conv_igemm_kernel / conv1x1 family: every GEMM-addressed 1x1 conv of the plan "
+                                        f"({f1['launches']} launches)", "instruction": "v_mfma_f32_32x32x2_f32",
+                                        "achieved": f1["executed_tflops"], "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                                        "frac": f1["frac_of_f32_mfma_peak"], "family_ms": f1["ms"], "family_gflop": f1["algorithmic_gflop"],
+                                        "timing": "sum of per-launch HIP-event times, one batch in flight, median of 5 passes after the timed region"}
+            line["kernel_families"] = fams
+            if world == 1 and not args.no_fast_mode:
+                line["fast_mode"] = fast_mode(model, head, clip, x, args, res)
+                line["fast_mode_mixed"] = fast_mode(model, head, clip, x, args, res, "mixed")
+            if world == 1:
+                line["nms_micro"] = nms_micro(dev, args.batch, with_cpu=sd_cpu is not None)
+                line["postproc"] = postproc_bench(dev, args.classes)
+                line["note_end_to_end_nms"] = ("the bench head is calibrated (bench.calibrate_head, seeded): the timed end-to-end step's NMS suppresses "
+                                               "most of its 1000 candidates per image (kept_mean); nms_micro / postproc are SURVEY 8d's synthetic workloads")
+            if world == 1 and not args.no_train_step:
+                line["train_step"] = train_step(dev)
+            if sd_cpu is not None:
+                line["cpu_baseline"] = cpu_baseline(sd_cpu, args.classes, args.height)
+                line["cpu_baseline"]["hip_beside_legs"] = gpu_legs_beside_cpu(dev, args.height)
         out.write(json.dumps(line) + "\n")
         out.flush()
     if use_dist:

@@ -379,6 +379,30 @@ def test_bench_roofline_object_describes_the_marked_launch():
     assert bench.pmc_traffic(dict(bench.PMC_WORKLOAD), "igemm") == (None, None)
 
 
+def test_bench_dump_outputs_types_and_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs): one <name>.npy per array, float64 kept, everything else float32; over the byte budget an
+    array is cut to the same seeded sample of its elements in every run, and the files together stay within the budget."""
+    import numpy as np
+    import bench
+    scores = torch.rand(4, 1000)
+    classes = torch.randint(1, 81, (4, 1000))
+    loss = torch.tensor([0.25], dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"scores": scores, "classes": classes, "loss": loss})
+    s, c, l = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("scores", "classes", "loss"))
+    assert s.dtype == np.float32 and c.dtype == np.float32 and l.dtype == np.float64
+    np.testing.assert_array_equal(s, scores.numpy())
+    np.testing.assert_array_equal(c, classes.numpy().astype(np.float32))
+    assert l.tolist() == [0.25]
+    big = {"w": torch.arange(100_000, dtype=torch.float32), "b": torch.arange(10, dtype=torch.float32)}
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), big, budget=40_000)
+    w1, w2 = np.load(tmp_path / "b1" / "w.npy"), np.load(tmp_path / "b2" / "w.npy")
+    np.testing.assert_array_equal(w1, w2)
+    assert np.all(np.diff(w1) > 0) and 9_000 < w1.size < 10_000
+    np.testing.assert_array_equal(np.load(tmp_path / "b1" / "b.npy"), np.arange(10, dtype=np.float32))
+    assert sum(os.path.getsize(p) - 128 for p in (tmp_path / "b1").iterdir()) <= 40_000
+
+
 def test_round5_entry_points_validate_on_the_host():
     """The round-5 additions are host arithmetic / host checks until a launch: workspace and pool sizes, weight packings, rejected argument combinations (no GPU needed)."""
     lib = _lib.lib()

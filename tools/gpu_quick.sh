@@ -9,4 +9,4 @@ if [ "$kexpr" != "none" ]; then
   echo "pytest rc=$?"; grep -E "max \|err\||passed|failed|error" $O/pytest.log | tail -25
 fi
 timeout -k 10 300 python bench.py --inflight 1 --layer-times $O/layer_times.tsv > /dev/null 2> $O/layer_times.err; tail -1 $O/layer_times.tsv
-timeout -k 10 600 python bench.py --no-train-step --no-fast-mode > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-300 $O/bench.json
+timeout -k 10 600 python bench.py --full --no-train-step --no-fast-mode > $O/bench.json 2> $O/bench.err; tail -2 $O/bench.err; cut -c1-300 $O/bench.json

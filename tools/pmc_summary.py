@@ -67,7 +67,7 @@ out = {"tag": tag, "commit_of_the_working_tree_summarised": commit, "decode_kern
                            "mfma_busy_frac": sum(util) / len(util), "clock_ghz": sum(clk) / len(clk),
                            "avg_dur_ms_under_pmc": sum(v["dur_ns"] for v in q) / len(q) / 1e6},
        "fetch_size_calibration_normalise_pass(read/written)": cal,
-       "source": f"rocprofv3 --kernel-trace --pmc <one counter set per pass> -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline ({tag})"}
+       "source": f"rocprofv3 --kernel-trace --pmc <one counter set per pass> -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline ({tag})"}
 json.dump(out, open(f"profiles/{tag}_pmc_summary.json", "w"), indent=1)
 json.dump(out, open("profiles/pmc_traffic.json", "w"), indent=1)
 print(json.dumps(out, indent=1))
