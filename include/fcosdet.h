@@ -610,6 +610,38 @@ int32_t fd_unpack_detections(const float* records, int32_t B, int32_t K, float* 
                              int32_t* counts, fd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
+/* VOC average precision (reference test.py:15-20 sort_by_score + 23-162 iou_2d / _compute_ap / eval_ap_2d, the mAP of
+ * evaluate 225-238), whole computation on the device.  Inputs (device memory): detections scores [N][K] fp32, classes [N][K]
+ * int64 (1-based, as FCOSHead emits), boxes [N][K][4] fp32 xyxy, det_counts [N] int32 or NULL (= K: rows >= count are ignored);
+ * GT boxes [N][G][4] fp32, classes [N][G] int64, gt_counts [N] or NULL (= G).  Rows whose label is outside 1 .. num_cls-1 never
+ * take part (class 0, the collate's -1 padding, labels >= num_cls).  thresholds: HOST array of n_thr fp32 IoU thresholds.
+ * Semantics, per label 1 .. num_cls-1 and threshold:
+ *   - each image's detections in descending score order (ties: lower row first); flags & FD_EVAL_INPUT_ORDER: in row order
+ *     instead (eval_ap_2d takes its lists as given, sort_by_score is a separate step);
+ *   - no GT box of the label in the image: false positive.  Else IoU against each GT box of the label in row order, fp32 without
+ *     the "+1" convention: w = max(0, min(x2) - max(x1)), h alike, overlap = w * h, iou = overlap / ((area_gt + area_det) - overlap);
+ *     min / max propagate NaN as np.minimum / np.maximum do (a NaN coordinate gives a NaN IoU);
+ *     j = argmax, first maximum, a NaN wins (first NaN; zero-area GT against a zero-area detection);
+ *   - TP iff iou[j] >= thr (fp32 compare; NaN never) and GT box j of the image is not yet assigned; a TP assigns j.  An assigned
+ *     j makes the detection a false positive: there is no fall-back to the next-best box;
+ *   - the label's detections of all images in (image, rank) order, sorted by descending score, STABLE (the reference's
+ *     np.argsort is an unstable quicksort: the only intended difference, visible only on exactly equal scores);
+ *   - fp64 running tp / fp, recall = tp / n_gt, precision = tp / max(tp + fp, eps); AP = sum over the recall change points of
+ *     (mrec[i+1] - mrec[i]) * envelope(mpre)[i+1] with sentinels mrec = [0, r.., 1], mpre = [0, p.., 0], summed in numpy's
+ *     pairwise order (8 accumulators, blocks of 128, halves rounded to multiples of 8): bit-identical to numpy;
+ *   - n_gt > 0 and no detection: 0.0; detections but n_gt == 0: NaN (recall 0 / 0); neither: 0.0.
+ * Outputs (device): ap [n_thr][num_cls] fp64, n_gt [num_cls], n_pred [num_cls], n_tp [n_thr][num_cls] int32; column 0 (background)
+ * is 0.  Limits: K <= 1024, G <= 512, 2 <= num_cls <= 128, n_thr <= 16, N * K < 2^31 (FD_E_UNSUPPORTED names the limit).
+ * Deterministic: no output depends on the order of atomics.  Boxes 16-byte aligned; workspace (fd_eval_ap_workspace_bytes:
+ * about 25 bytes per detection row, linear in N * K) 256-byte aligned.  21 launches on `stream`, no host synchronisation. */
+#define FD_EVAL_INPUT_ORDER 1
+int64_t fd_eval_ap_workspace_bytes(int32_t N, int32_t K, int32_t G, int32_t num_cls, int32_t n_thr);
+int32_t fd_eval_ap(const float* det_scores, const int64_t* det_classes, const float* det_boxes, const int32_t* det_counts, int32_t N,
+                   int32_t K, const float* gt_boxes, const int64_t* gt_classes, const int32_t* gt_counts, int32_t G, int32_t num_cls,
+                   const float* thresholds, int32_t n_thr, int32_t flags, double* ap, int32_t* n_gt, int32_t* n_pred, int32_t* n_tp,
+                   void* workspace, fd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- */
 /* LTRB IoU / GIoU regression loss (reference model/loss.py:116-177), fused masked forward + backward.
  * pred/target [B][L][4], mask [B][L] (uint8, positives).  mode 0 = 'iou', 1 = 'giou'.
  * loss_per_image [B] = sum over positives (NOT yet divided by num_pos), num_pos [B] int32.

@@ -1350,3 +1350,64 @@ def fcos_gen_targets(gt_boxes: torch.Tensor, labels: torch.Tensor, level_hw, str
     check(_lib.lib().fd_fcos_gen_targets(gb.data_ptr(), lb.data_ptr(), M, C.byref(segs), st, lo, hi, radius, cls.data_ptr(),
                                          cnt.data_ptr(), reg.data_ptr(), _stream()), "fd_fcos_gen_targets")
     return cls, cnt, reg
+
+
+EVAL_INPUT_ORDER = 1    # include/fcosdet.h FD_EVAL_INPUT_ORDER: match each image's detections in row order (eval_ap_2d) instead of score order
+
+
+def eval_ap_bytes(n_thr: int, num_cls: int) -> int:
+    """Size of the packed result buffer of eval_ap: ap [T, C] f64, n_gt [C], n_pred [C], n_tp [T, C] int32."""
+    return n_thr * num_cls * 8 + 2 * num_cls * 4 + n_thr * num_cls * 4
+
+
+def eval_ap_views(buf: torch.Tensor, n_thr: int, num_cls: int):
+    """(ap, n_gt, n_pred, n_tp) views of a packed uint8 result buffer (device or host copy alike)."""
+    T, Cn = n_thr, num_cls
+    a = T * Cn * 8
+    ap = buf[:a].view(torch.float64).view(T, Cn)
+    n_gt = buf[a:a + 4 * Cn].view(torch.int32)
+    n_pred = buf[a + 4 * Cn:a + 8 * Cn].view(torch.int32)
+    n_tp = buf[a + 8 * Cn:a + 8 * Cn + 4 * T * Cn].view(torch.int32).view(T, Cn)
+    return ap, n_gt, n_pred, n_tp
+
+
+def eval_ap(scores: torch.Tensor, classes: torch.Tensor, boxes: torch.Tensor, det_counts: Optional[torch.Tensor],
+            gt_boxes: torch.Tensor, gt_classes: torch.Tensor, gt_counts: Optional[torch.Tensor], num_cls: int,
+            thresholds: Sequence[float], flags: int = 0, out: Optional[torch.Tensor] = None):
+    """VOC AP of the reference's eval_ap_2d (fd_eval_ap, include/fcosdet.h) on the current stream.
+    scores [N,K] f32, classes [N,K] int64, boxes [N,K,4] f32, det_counts [N] int32 or None; gt_boxes [N,G,4] f32, gt_classes [N,G]
+    int64, gt_counts [N] int32 or None.  -> (ap [T, num_cls] f64, n_gt [num_cls], n_pred [num_cls], n_tp [T, num_cls] int32), views of
+    `out` (uint8, eval_ap_bytes(T, num_cls), allocated when None); column 0 (background) is 0."""
+    _need_gpu(scores, classes, boxes, det_counts, gt_boxes, gt_classes, gt_counts)
+    N, K = scores.shape
+    G = gt_classes.shape[1]
+    if tuple(classes.shape) != (N, K) or tuple(boxes.shape) != (N, K, 4) or tuple(gt_boxes.shape) != (N, G, 4) or gt_classes.shape[0] != N:
+        raise FdError(f"eval_ap: shapes scores {tuple(scores.shape)} classes {tuple(classes.shape)} boxes {tuple(boxes.shape)} "
+                      f"gt_boxes {tuple(gt_boxes.shape)} gt_classes {tuple(gt_classes.shape)} do not agree")
+    if (scores.dtype != torch.float32 or classes.dtype != torch.int64 or boxes.dtype != torch.float32 or gt_boxes.dtype != torch.float32
+            or gt_classes.dtype != torch.int64):
+        raise FdError("eval_ap: scores / boxes must be fp32, classes int64")
+    for t in (scores, classes, boxes, gt_boxes, gt_classes, det_counts, gt_counts):
+        if t is not None and not t.is_contiguous():
+            raise FdError("eval_ap: inputs must be contiguous")
+    for t in (det_counts, gt_counts):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (N,)):
+            raise FdError("eval_ap: counts must be int32 [N]")
+    T = len(thresholds)
+    dev = scores.device
+    need = _lib.lib().fd_eval_ap_workspace_bytes(N, K, G, num_cls, T)
+    if need < 0:
+        check(_lib.lib().fd_eval_ap(None, None, None, None, N, K, None, None, None, G, num_cls, None, T, flags, None, None, None, None,
+                                    None, None), "fd_eval_ap")
+    # workspace per call (~25 bytes per detection row): evaluation runs once per epoch, so it is not kept in a module cache; it goes
+    # back to torch's caching allocator when the call's kernels are enqueued (torch.cuda.empty_cache() can then release it)
+    ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    if out is None:
+        out = torch.empty(eval_ap_bytes(T, num_cls), dtype=torch.uint8, device=dev)
+    ap, n_gt, n_pred, n_tp = eval_ap_views(out, T, num_cls)
+    thr = (C.c_float * T)(*[float(t) for t in thresholds])
+    check(_lib.lib().fd_eval_ap(scores.data_ptr(), classes.data_ptr(), boxes.data_ptr(),
+                                det_counts.data_ptr() if det_counts is not None else None, N, K, gt_boxes.data_ptr(), gt_classes.data_ptr(),
+                                gt_counts.data_ptr() if gt_counts is not None else None, G, num_cls, thr, T, int(flags), ap.data_ptr(),
+                                n_gt.data_ptr(), n_pred.data_ptr(), n_tp.data_ptr(), ws.data_ptr(), _stream()), "fd_eval_ap")
+    return ap, n_gt, n_pred, n_tp
