@@ -122,7 +122,7 @@ const char* fd_last_error(void);
                                 single-plane f16 instantiations of the other tiles, and activation maps stored as f16 (io_f16) go to LDS unconverted, 16 bytes per lane.  `w` = the
                                 fd_pack_conv_weight_f32 mode | 16 packing; Cin % 64 == 0, x_cs / x_co multiples of 8, 4-channel aligned output / residual views; ReLU / SiLU / none;
                                 any stride / dilation / pyramid / scatter; no split-K, gate, gn_stats, x2.  The library picks the block tile. */
-#define FD_TILE_COUNT 17
+#define FD_TILE_COUNT 19
 
 typedef struct fd_conv_params {
     const float* x;

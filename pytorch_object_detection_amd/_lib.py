@@ -7,7 +7,8 @@ import os
 FD_MAX_SEG = 8
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_EXP, ACT_SIGMOID = 0, 1, 2, 3, 4
 CONV_GENERIC, CONV_STEM = 0, 1
-PREC_F32, PREC_F16X3 = 0, 1
+PREC_F32, PREC_F16X3, PREC_F16 = 0, 1, 2     # include/fcosdet.h FD_PREC_*
+# include/fcosdet.h FD_TILE_*: the block tiles of the direct implicit-GEMM kernel (what autotune_conv chooses among) ...
 TILES = {1: (128, 128), 2: (128, 64), 3: (64, 128), 4: (64, 64), 5: (128, 32), 6: (128, 96),
          7: (128, 128), 8: (128, 64), 9: (64, 128),   # 7-9: single-LDS-buffer variants
          10: (256, 128), 11: (256, 128),             # 8-wave tile (11: single LDS buffer)
@@ -16,11 +17,11 @@ TILES = {1: (128, 128), 2: (128, 64), 3: (64, 128), 4: (64, 64), 5: (128, 32), 6
          15: (64, 64)}                               # wave-autonomous 64x64 tiles, one wave per workgroup (1x1 stride-1 layers, needs w_frag)
 PATCH_TILE = 13
 WAVE_TILE = 15
-NARROW_TILE = 17    # 3x3 stride-1 pad-1 convs with Cout <= 8 on the vector unit (fd_conv_narrow.hip; ops.pack_conv_weight_narrow); not a member of TILES
-F16K64_TILE = 18    # FD_PREC_F16 on K-tiles of 64 channels (fd_conv_f16.hip; ops.pack_conv_weight_f16k64); not a member of TILES
-WINO4_TILE = 16     # Winograd F(4x4, 3x3) kernel (own weight packing: ops.pack_conv_weight_wino4); not a member of TILES
-PREC_F32, PREC_F16X3, PREC_F16 = 0, 1, 2     # include/fcosdet.h FD_PREC_*
-WINO_TILE = 14      # Winograd F(2x2, 3x3) kernel (own weight packing: ops.pack_conv_weight_wino); not a member of TILES
+# ... and the kernels a tile id names, each with its own weight format (ops.WFormat); not members of TILES
+WINO_TILE = 14      # Winograd F(2x2, 3x3) kernel (ops.pack_conv_weight_wino)
+WINO4_TILE = 16     # Winograd F(4x4, 3x3) kernel (ops.pack_conv_weight_wino4)
+NARROW_TILE = 17    # 3x3 stride-1 pad-1 convs with Cout <= 8 on the vector unit (fd_conv_narrow.hip; ops.pack_conv_weight_narrow)
+F16K64_TILE = 18    # FD_PREC_F16 on K-tiles of 64 channels (fd_conv_f16.hip; ops.pack_conv_weight_f16k64)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FD_LIB: another build of the SAME library (development A/B runs: tools/gpu_ab.sh keeps its variants outside the package and never overwrites the product

@@ -696,7 +696,7 @@ int fd_launch_conv_wino4(const fd_conv_params* p, hipStream_t stream) {
         a.wpx = p->sk_wgs / 8;
         FD_REQUIRE((long)a.mt_per * a.ntiles * 16 < (1L << 30), FD_E_UNSUPPORTED, "fd_conv2d: sk_wgs: too many items per XCD");
         {   // pieces per remainder item: the choice that gets the remainder of the fullest XCD through in the least time -- ceil(rem * P / wpx) passes of
-            // (NC / P chunks + the fixed cost of a segment), in units of one chunk's time (fixed cost ~ 6.5 chunks: profiles/r05_wino4_fixed_cost.txt); the slots of an XCD
+            // (NC / P chunks + the fixed cost of a segment), in units of one chunk's time (fixed cost ~ 6.5 chunks: profiles/r05_wino4_fixed_cost_raw.txt, _phases.txt); the slots of an XCD
             // (rem * (P - 1)) must fit the workspace's wpx
             static const int force_p = getenv("FD_W4_SK_P") ? atoi(getenv("FD_W4_SK_P")) : 0;
             // (every XCD has its own remainder -- the last one owns fewer M tiles: the slot bound must hold for each, the time is the slowest XCD's)

@@ -28,10 +28,6 @@ import os as _os
 # conv except the 7x7 stem (K = 147 is too short to matter).  See include/fcosdet.h FD_PREC_*.
 CONV_PRECISION = _os.environ.get("FD_CONV_PRECISION", "f32")
 AUTOTUNE = True   # per-conv block-tile lookup / timing at plan-build time (see ops.autotune_conv, FD_AUTOTUNE)
-# FD_WINOGRAD: "1" (default) = 3x3 stride-1 'same' convs (dilation 1 / 2, Cin % 8 == 0) of an exact-fp32 plan run on the Winograd
-# F(2x2, 3x3) kernel (fd_conv_wino.hip: 2.25x fewer MFMAs, still fp32 arithmetic) where the map is large enough for it to win
-# (ops.wino_preferred: it has no split-K); "force" = wherever it applies; "0" = every conv on the direct implicit-GEMM kernel
-WINOGRAD = _os.environ.get("FD_WINOGRAD", "1") != "0"
 SE_GATE_IN_PROJECT = _os.environ.get("FD_SE_GATE_FUSED", "1") != "0"     # MBConv: SE gate applied by the project conv's loader ("0": a scaling pass)
 GN_FUSED_TOWER = _os.environ.get("FD_GN_FUSED_TOWER", "0") == "1"   # "1": the tower's statistics from its Winograd epilogue too (measured neutral, costs the tower launch 5 %)
 # "1": a head-tower F(4x4) launch whose grid is no multiple of the CU count runs as whole rounds of workgroups + a tail launch ("head.tower3x3.tail", after the mark):
@@ -99,13 +95,12 @@ class Plan:
         self.step_info: Dict[int, dict] = {}   # conv steps: kernel size / stride / which kernel family ran it (bench.py's family rooflines)
         self.marks: Dict[str, Tuple[int, int]] = {}
         self.autotune = AUTOTUNE        # time block-tile candidates per conv at plan-build time
+        # 'mixed' (opt-in): the 3x3 stride-1 layers stay on the exact-fp32 Winograd kernel, the GEMM-addressed 1x1 layers -- 48 % of the step,
+        # short K, epilogue-heavy -- take the split-f16 products (three f16 MFMAs per fp32 product = 3/16 of the matrix time, same 1e-4 bar): ops.choose_conv
         self.precision = precision or CONV_PRECISION
         if self.precision not in ("f32", "f16x3", "mixed"):
             raise FdError(f"unknown conv precision '{self.precision}' (f32 | f16x3 | mixed)")
         self.tiles: Dict[str, int] = {}
-        # 'mixed' (opt-in): the 3x3 stride-1 layers stay on the exact-fp32 Winograd kernel, the GEMM-addressed 1x1 layers -- 48 % of the step,
-        # short K, epilogue-heavy -- take the split-f16 products (three f16 MFMAs per fp32 product = 3/16 of the matrix time, same 1e-4 bar)
-        self.winograd = WINOGRAD and self.precision in ("f32", "mixed")
         self.pair_tuned = pair_tuned       # block tiles picked for throughput beside a second batch (pipeline.TwoLanePipeline)
 
     def add(self, name: str, fn: Callable[[], None]) -> None:
@@ -214,39 +209,24 @@ def add_conv(plan: Plan, name: str, x: Rows, segs: Segs, conv: torch.nn.Conv2d, 
         # the weights get matching zero input channels
         w = torch.nn.functional.pad(_dev(w, dev).detach(), (0, 0, 0, 0, 0, x.C - Cin))
         Cin = x.C
-    split = plan.precision == "f16x3" or (plan.precision == "mixed" and k == 1 and stride == 1 and gate is None and gn_stats is None
-                                           and Cin % 32 == 0)
-    # <= 8 output channels (the centre-ness / box predictor): the vector-unit kernel, where the map has enough tiles to fill the chip
-    # (a gate there is the preceding GroupNorm's affine: gate + gate_b, applied to the patch)
-    narrow = (ops.NARROW and plan.precision in ("f32", "mixed") and res is None and (gate is None or gate_b is not None) and gn_stats is None and w.shape[0] == co
-              and ops.narrow_ok(Cin, co, k, stride, pad, dil) and ops.narrow_tiles(segs) >= ops.NARROW_MIN_TILES)
-    if narrow:
-        split = False
-    wino, wino_ks = False, 1
-    if (not narrow and plan.winograd and ops.wino_ok(Cin, co, k, stride, pad, dil) and y.cs % 4 == 0 and y.co % 4 == 0 and
-            (res is None or (res.cs % 4 == 0 and res.co % 4 == 0))):
-        wino, wino_ks = ops.wino_choice(segs, Cin, co, dil)
-        wino = wino or tag == 1                   # (the head tower -- the roofline kernel -- always runs the Winograd kernel)
-    # F(4x4, 3x3) where its cost model beats F(2x2, 3x3) / the direct kernel: exact-fp32 plans only, no gate / statistics epilogue
-    wino4, w4_ks = False, 1
-    if (not narrow and plan.winograd and gate is None and gn_stats is None and ops.wino4_ok(Cin, co, k, stride, pad, dil) and y.cs % 4 == 0 and y.co % 4 == 0
-            and (res is None or (res.cs % 4 == 0 and res.co % 4 == 0))):
-        wino4, w4_ks = ops.wino4_choice(segs, Cin, co, dil)
+    aligned = y.cs % 4 == 0 and y.co % 4 == 0 and (res is None or (res.cs % 4 == 0 and res.co % 4 == 0))
+    fmt, wino_ks, prec = ops.choose_conv(segs, Cin, co, k, stride, pad, dil, plan.precision, narrow=w.shape[0] == co, res=res is not None,
+                                         gate=gate is not None, gate_b=gate_b is not None, gn_stats=gn_stats is not None, aligned=aligned,
+                                         force_wino=tag == 1)     # (the head tower -- the roofline kernel -- always runs a Winograd kernel)
+    WF = ops.WFormat
+    narrow, wino4 = fmt is WF.NARROW, fmt is WF.WINO4
+    wino = wino4 or fmt is WF.WINO
     if narrow:
         wp = ops.pack_conv_weight_narrow(_dev(w, dev))
-    elif wino4:
-        wino, wino_ks = True, w4_ks
-        wp = ops.pack_conv_weight_wino4(_dev(w, dev))
     elif wino:
-        wp = ops.pack_conv_weight_wino(_dev(w, dev))
+        wp = fmt.pack(_dev(w, dev))
     else:
-        wp = ops.pack_conv_weight_f16x3(_dev(w, dev)) if split else ops.pack_conv_weight(_dev(w, dev))
+        wp = ops.pack_conv_weight_f16x3(_dev(w, dev)) if fmt is WF.DIRECT_F16 else ops.pack_conv_weight(_dev(w, dev))
     # GEMM-addressed fp32 layers also get their weights in MFMA fragment order: the wave-autonomous tile (FD_TILE_WAVE64) becomes selectable
     wfrag = None
-    if (not wino and not narrow and not split and x2 is None and not res_up and WAVE_TILE and gate is None and ops.wave_ok(Cin, co, k, stride, pad) and act_c0 % 32 == 0
-            and act in (ACT_NONE, ACT_RELU, ACT_SILU) and y.cs % 4 == 0 and y.co % 4 == 0 and (res is None or (res.cs % 4 == 0 and res.co % 4 == 0))):
-        if w.shape[0] == co and w.shape[1] == Cin:
-            wfrag = ops.pack_conv_weight_wave(_dev(w, dev))
+    if (fmt is WF.DIRECT and x2 is None and not res_up and WAVE_TILE and gate is None and ops.wave_ok(Cin, co, k, stride, pad) and act_c0 % 32 == 0
+            and act in (ACT_NONE, ACT_RELU, ACT_SILU) and aligned and w.shape[0] == co and w.shape[1] == Cin):
+        wfrag = ops.pack_conv_weight_wave(_dev(w, dev))
     scale = shift = None
     if fold is not None:
         scale, shift = fold
@@ -262,8 +242,8 @@ def add_conv(plan: Plan, name: str, x: Rows, segs: Segs, conv: torch.nn.Conv2d, 
     if narrow:
         ws = None
     elif gn_stats is not None:
-        if wino and wino_ks > 1:
-            raise FdError("add_conv: gn_stats with a split-K Winograd launch (the caller checks ops.wino_choice first)")
+        if wino_ks > 1:
+            raise FdError("add_conv: gn_stats with a split-K Winograd launch (the caller checks ops.choose_conv first)")
         ws = None                  # (row-group statistics come out of the conv's own epilogue: no split-K, whose combine launch has none)
     elif wino:
         ws = plan.pool.get(wino_ks * out.rows, (co + 3) & ~3) if wino_ks > 1 else None
@@ -272,10 +252,8 @@ def add_conv(plan: Plan, name: str, x: Rows, segs: Segs, conv: torch.nn.Conv2d, 
     else:
         ws = plan.pool.get(ws_rows, (co + 3) & ~3) if (plan.autotune and ws_rows * ((co + 3) & ~3) <= 64 * 1024 * 1024) else None
     call = ops.conv_call(x, segs, wp, y, Cin=Cin - (x2.C if x2 is not None else 0), Cout=co, k=k, stride=stride, pad=pad, dil=dil, scale=scale,
-                         shift=shift, res=res, act=act, act_c0=act_c0, seg_param=seg_param, tag=tag,
-                         precision=1 if split else 0, workspace=ws.buf if ws is not None else None,
-                         tile=_lib.NARROW_TILE if narrow else ((_lib.WINO4_TILE if wino4 else _lib.WINO_TILE) if wino else 0), ksplit=wino_ks if wino else 1,
-                         gate=gate, w_frag=wfrag,
+                         shift=shift, res=res, act=act, act_c0=act_c0, seg_param=seg_param, tag=tag, precision=prec,
+                         workspace=ws.buf if ws is not None else None, tile=fmt.tile, ksplit=wino_ks, gate=gate, w_frag=wfrag,
                          gate_b=gate_b, gate_act=gate_act, gn_stats=gn_stats, gn_groups=gn_groups, x2=x2, x2_stride=x2_stride, x2_hw=x2_hw, res_up=res_up)
     tail = None
     sk = 0
@@ -283,8 +261,7 @@ def add_conv(plan: Plan, name: str, x: Rows, segs: Segs, conv: torch.nn.Conv2d, 
         # the persistent form of the F(4x4) launch (work queue per XCD, the last partial round of items cut into pieces) where it was measured faster
         if getattr(plan, "sk_ws", None) is None:
             plan.sk_ws = ops.sk_workspace(256, dev)         # one per plan: the launches of a plan are stream-ordered; every lane of the pipeline has its own plan
-        hw_ = "+".join(f"{h}x{w}" for h, w in segs.level_hw())
-        sk = ops.wino4_sk_choice(call, f"B{segs.batch}|{hw_}|{Cin}>{co}|d{dil}|res{int(res is not None)}", plan.sk_ws)
+        sk = ops.wino4_sk_choice(call, ops.tune_key(segs, Cin, co, dil=dil, res=res is not None, pre="w4sk"), plan.sk_ws)
         if sk:
             call = ops.conv_sk(call, sk, plan.sk_ws)
             plan.sk_of = getattr(plan, "sk_of", {})
@@ -304,34 +281,26 @@ def add_conv(plan: Plan, name: str, x: Rows, segs: Segs, conv: torch.nn.Conv2d, 
         plan.tail_of[name] = {"workgroups": total, "main": full, "live": live, "main_share": 1.0 - tail_share}
     if ws is not None:
         plan.pool.put(ws)
-    if narrow:
-        plan.tiles[name] = _lib.NARROW_TILE
-    elif wino:
-        plan.tiles[name] = (_lib.WINO4_TILE if wino4 else _lib.WINO_TILE) | ((wino_ks if wino_ks > 1 else 0) << 8)
+    if narrow or wino:
+        plan.tiles[name] = ops.tile_code(fmt.tile, wino_ks)
     elif gate is not None:
         plan.tiles[name] = 0                 # (the library picks the tile of a gated conv)
     elif plan.autotune:
-        hw = "+".join(f"{h}x{w}" for h, w in segs.level_hw())
         # (res_up: the quarter-size addend costs next to nothing -- the plain layer's measured tile, mapped below onto the tiles that form is built for)
-        key = f"B{segs.batch}|{hw}|{Cin}>{co}|k{k}s{stride}p{pad}d{dil}|res{int(res is not None and not res_up)}|xcs{x.cs}|ycs{y.cs}"
-        if split:
-            key = "f16x3|" + key
-        if x2 is not None:
-            key += f"|x2s{x2_stride}c{x2.C}"
+        key = ops.tune_key(segs, Cin, co, k, stride, pad, dil, res=res is not None and not res_up, xcs=x.cs, ycs=y.cs,
+                           pre="f16x3" if fmt is WF.DIRECT_F16 else "", x2=(x2_stride, x2.C) if x2 is not None else None)
         if res_up and key not in ops._tune_table():
             # a table MISS of a res_up layer is timed with res_mode 2 set, i.e. over the RUP tiles only: that restricted winner gets a key of its own and never
             # lands under the plain layer's key (which the unfused FD_FPN_UP_FUSED=0 lateral of the same shape reads).  A plain-key HIT is still mapped below.
             key += "|rup"
-        plan.tiles[name] = ops.autotune_conv(call, key, out.rows, co, -(-Cin // 32) * k * k, pair=plan.pair_tuned and tag != 1)
-        if res_up:
-            t = {1: 8, 2: 8, 3: 9, 4: 4, 7: 8, 8: 8, 9: 9}.get(plan.tiles[name] & 0xFF, 9)
+        code = plan.tiles[name] = ops.autotune_conv(call, key, out.rows, co, -(-Cin // 32) * k * k, pair=plan.pair_tuned and tag != 1)
+        if res_up or x2 is not None:
+            # res_up: the RUP tiles; x2: the dual-source loader is built for the tiles the bottleneck expansions use.  The choice is mapped onto them, no split-K
+            remap = {1: 8, 2: 8, 3: 9, 4: 4, 7: 8, 8: 8, 9: 9} if res_up else {1: 7, 2: 8, 3: 9, 4: 4, 7: 7, 8: 8, 9: 9}
+            t = remap.get(ops.tile_split(code)[0], 9 if res_up else 8)
             call.params.tile, call.params.ksplit = t, 1
             plan.tiles[name] = t
-        if x2 is not None:         # the dual-source loader is built for the tiles the bottleneck expansions use: map the choice onto them, no split-K
-            t = {1: 7, 2: 8, 3: 9, 4: 4, 7: 7, 8: 8, 9: 9}.get(plan.tiles[name] & 0xFF, 8)
-            call.params.tile, call.params.ksplit = t, 1
-            plan.tiles[name] = t
-        if gn_stats is not None and (plan.tiles[name] & 0xFF) not in (0, 2, 3, 4, 8, 9, _lib.WAVE_TILE):
+        if gn_stats is not None and ops.tile_split(plan.tiles[name])[0] not in (0, 2, 3, 4, 8, 9, _lib.WAVE_TILE):
             call.params.tile = plan.tiles[name] = 8      # the statistics epilogue exists for the one- / two-sub-tile tiles (and WAVE64 / Winograd)
     plan.flops += 2 * out.rows * co * Cin * k * k
     info = {"k": k, "stride": stride, "dil": dil, "Cin": Cin, "Cout": co, "rows": out.rows,
@@ -739,12 +708,15 @@ def build_his_fpn(plan: Plan, fpn, feats):
 
 
 # ------------------------------------------------------------------------------------------------ heads
-def _narrow_predictor(plan: Plan, head, segs: Segs, F: int) -> bool:
-    """Does the 1 + 4-wide centre-ness / box predictor of this plan run on the vector-unit kernel (FD_TILE_NARROW)?"""
+def _predictor_format(plan: Plan, head, segs: Segs, F: int, Cout: int = 5, wino4: bool = True) -> "ops.WFormat":
+    """ops.choose_conv's format (= kernel family) for the 1 + 4-wide centre-ness / box predictor of this plan, as add_conv will ask for it."""
     rp = head.reg_pred
     rp_pad = rp.dilation[0] * (rp.kernel_size[0] - 1) // 2 if isinstance(rp.padding, str) else rp.padding[0]
-    return bool(ops.NARROW and plan.precision in ("f32", "mixed") and ops.narrow_ok(F, 5, rp.kernel_size[0], rp.stride[0], rp_pad, rp.dilation[0])
-                and ops.narrow_tiles(segs) >= ops.NARROW_MIN_TILES)
+    return ops.choose_conv(segs, F, Cout, rp.kernel_size[0], rp.stride[0], rp_pad, rp.dilation[0], plan.precision, wino4=wino4).fmt
+
+
+def _narrow_predictor(plan: Plan, head, segs: Segs, F: int) -> bool:
+    return _predictor_format(plan, head, segs, F) is ops.WFormat.NARROW
 
 
 def _out_convs(plan: Plan, head, tower: Rows, segs: Segs, F: int, ncls: int, reg_gate=None):
@@ -758,12 +730,10 @@ def _out_convs(plan: Plan, head, tower: Rows, segs: Segs, F: int, ncls: int, reg
     w = torch.cat([head.cnt_logits.weight.detach(), head.reg_pred.weight.detach()], 0)
     b = torch.cat([head.cnt_logits.bias.detach(), head.reg_pred.bias.detach()], 0)
     scales = [float(s.scale.detach().reshape(-1)[0]) for s in head.scale_exp][:segs.nseg]
-    rp = head.reg_pred
-    rp_pad = rp.dilation[0] * (rp.kernel_size[0] - 1) // 2 if isinstance(rp.padding, str) else rp.padding[0]
-    narrow = _narrow_predictor(plan, head, segs, F)
-    if reg_gate is not None and not narrow:
+    if reg_gate is not None and not _narrow_predictor(plan, head, segs, F):
         raise FdError("_out_convs: a GroupNorm folded into the box predictor's loader needs the narrow kernel")
-    if not narrow and plan.winograd and ops.wino_ok(F, 8, rp.kernel_size[0], rp.stride[0], rp_pad, rp.dilation[0]) and ops.wino_choice(segs, F, 8, rp.dilation[0])[0]:
+    if _predictor_format(plan, head, segs, F, 8, wino4=False) is ops.WFormat.WINO:
+        # (where F(2x2) wins for the padded layer; add_conv may then still give it F(4x4))
         # the Winograd kernel writes whole float4s: three zero filters fill the 8-wide buffer (channels 5..7 hold exp(0) = 1, never read);
         # 0.27 -> 0.17 ms against the direct kernel's 128 x 32 tile at Cout = 5
         w = torch.cat([w, torch.zeros(3, *w.shape[1:], dtype=w.dtype, device=w.device)], 0)
@@ -865,7 +835,10 @@ def build_his_head(plan: Plan, head, pyr: Rows, segs: Segs):
     tower = pool.get(M, 2 * F)
     w = torch.cat([head.cls_conv[0].weight.detach(), head.reg_conv[0].weight.detach()], 0)
     tgn = [head.cls_conv[1], head.reg_conv[1]]
-    t_fused = (GN_FUSED_TOWER and _gn_fusable(plan, tgn, 2 * F) and plan.winograd and ops.wino_ok(F, 2 * F, 3, 1, 1, 1) and ops.wino_choice(segs, F, 2 * F, 1)[1] == 1)
+    t_fused = GN_FUSED_TOWER and _gn_fusable(plan, tgn, 2 * F)
+    if t_fused:          # (a statistics epilogue has no split-K form)
+        c = ops.choose_conv(segs, F, 2 * F, 3, 1, 1, 1, plan.precision, gn_stats=True, force_wino=True)
+        t_fused = c.fmt is ops.WFormat.WINO and c.ksplit == 1
     mark = len(plan.steps)
     if t_fused:
         Gt = sum(g.num_groups for g in tgn)

@@ -7,10 +7,12 @@ written in place (torch.cat in HISFcos.py:107,111 disappears) and slices are rea
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import json
 import os
+import re
 import sys
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -312,14 +314,13 @@ def conv_sk(run, sk_wgs: int, ws: torch.Tensor) -> Callable[[], None]:
 
 
 def wino4_sk_choice(run, key: str, ws: torch.Tensor, reps: int = 5) -> int:
-    """Plain launch (0) or the persistent form with 240 / 256 workgroups for one F(4x4) layer: the committed table first ("w4sk|" keys of
-    tuned/gfx950_tiles.json, measured on MI355X); a miss is timed on the spot under FD_AUTOTUNE, else stays plain.  The persistent form wins where the
+    """Plain launch (0) or the persistent form with 240 / 256 workgroups for one F(4x4) layer: the committed table first (key = tune_key(..., pre="w4sk")
+    of tuned/gfx950_tiles.json, measured on MI355X); a miss is timed on the spot under FD_AUTOTUNE, else stays plain.  The persistent form wins where the
     plain grid ends in a mostly idle round of workgroups and the chunk loop is long enough to carry the pieces' fixed cost (cls_logits, the dilated
     HisBlock conv4, the head tower); elsewhere it costs ~2 % (an extra barrier and a queue claim per item)."""
     if not W4_SK:
         return 0
     table = _tune_table()
-    key = "w4sk|" + key
     if _TUNE_MODE != "force" and key in table:
         return int(table[key])
     if _TUNE_MODE == "0":
@@ -435,8 +436,33 @@ def save_tune_table() -> None:
 
 
 KSPLIT_MAX = 8
-import re as _re
-_BKEY = _re.compile(r"^(f16x3\|)?B(\d+)(\|.*)$")
+_BKEY = re.compile(r"^(f16x3\|)?B(\d+)(\|.*)$")
+
+
+def tile_code(tile: int, ksplit: int = 1) -> int:
+    """The integer a tile table entry / plan.tiles holds for a launch: tile | ksplit << 8 (no split: the upper bits are zero)."""
+    return tile | ((ksplit if ksplit > 1 else 0) << 8)
+
+
+def tile_split(code: int) -> Tuple[int, int]:
+    """tile_code's inverse: (tile, ksplit >= 1)."""
+    return code & 0xFF, max(1, code >> 8)
+
+
+def tune_key(segs: Segs, Cin: int, Cout: int, k: int = 3, stride: int = 1, pad: int = 1, dil: int = 1, *, res: bool = False, xcs: int = 0,
+             ycs: int = 0, pre: str = "", x2: Optional[Tuple[int, int]] = None, rup: bool = False) -> str:
+    """Key of one conv launch in the tile table (tuned/gfx950_tiles.json): "[pre|]B<batch>|<HxW levels>|<Cin>><Cout>|k s p d|res|xcs|ycs" plus
+    "|x2s<stride>c<C>" for a K-concatenated second source and "|rup" for a res_up layer's own timing.  pre: "" (fp32), "f16x3" (split-f16 products),
+    "f16" (AMP), "pair" (autotune_conv(pair=True)); "w4sk" keys the persistent-F(4x4) choice by "B|levels|Cin>Cout|d|res" alone."""
+    hw = "+".join(f"{h}x{w}" for h, w in segs.level_hw())
+    if pre == "w4sk":
+        return f"w4sk|B{segs.batch}|{hw}|{Cin}>{Cout}|d{dil}|res{int(res)}"
+    key = f"B{segs.batch}|{hw}|{Cin}>{Cout}|k{k}s{stride}p{pad}d{dil}|res{int(res)}|xcs{xcs}|ycs{ycs}"
+    if pre:
+        key = f"{pre}|{key}"
+    if x2 is not None:
+        key += f"|x2s{x2[0]}c{x2[1]}"
+    return key + "|rup" if rup else key
 
 
 def heuristic_conv(M: int, Cout: int, KT: int, have_ws: bool) -> int:
@@ -462,7 +488,7 @@ def heuristic_conv(M: int, Cout: int, KT: int, have_ws: bool) -> int:
     if have_ws:
         while ks < KSPLIT_MAX and n * ks < 512 and KT >= 8 * ks:
             ks *= 2
-    return tiles | ((ks if ks > 1 else 0) << 8)
+    return tile_code(tiles, ks)
 
 
 _PAIR_STREAMS: list = []
@@ -505,7 +531,7 @@ def autotune_conv(run: Callable[[], None], key: str, M: int, Cout: int, KT: int,
 
     def apply(code: int) -> int:
         """Install a table / heuristic / timed code on the launch and return the code ACTUALLY applied (what plan.tiles records)."""
-        tile, ks = code & 0xFF, max(1, code >> 8)
+        tile, ks = tile_split(code)
         if tile == _lib.WAVE_TILE and not p.w_frag:
             # the key does not say whether the caller packed the weights in MFMA fragment order (train_ops._conv_launch never does, plans built
             # with FD_WAVE_TILE=0 neither): the wave-autonomous tile is then not available -- fall back to the library's heuristic tile
@@ -513,7 +539,7 @@ def autotune_conv(run: Callable[[], None], key: str, M: int, Cout: int, KT: int,
         if ks > 1 and (not p.workspace or p.gn_stats):        # (split-K needs the scratch; a row-statistics epilogue has no combine launch)
             ks = 1
         p.tile, p.ksplit = tile, ks
-        return tile | ((ks if ks > 1 else 0) << 8)
+        return tile_code(tile, ks)
 
     base = key
     if pair:                         # tiles chosen for throughput beside another batch: own table entries, serial ones as fallback
@@ -537,7 +563,7 @@ def autotune_conv(run: Callable[[], None], key: str, M: int, Cout: int, KT: int,
             if near:
                 _, b2, k2 = min(near)
                 code = int(table[k2])
-                if 0.5 <= b0 / b2 <= 2.0 and (code >> 8) <= 1:        # (split-K factors depend on the tile count: not transferred)
+                if 0.5 <= b0 / b2 <= 2.0 and tile_split(code)[1] == 1:        # (split-K factors depend on the tile count: not transferred)
                     return apply(code)
         return apply(heuristic_conv(M, Cout, KT, bool(p.workspace)))
     cands = [(0, 1)]
@@ -559,7 +585,7 @@ def autotune_conv(run: Callable[[], None], key: str, M: int, Cout: int, KT: int,
                         cands.append((tid, ks))
     best, best_t = 0, float("inf")
     for tid, ks in cands:
-        apply(tid | (ks << 8))
+        apply(tile_code(tid, ks))
         try:
             run()  # warm
         except FdError as e:          # a tile the library has no kernel for on this layer (FD_E_UNSUPPORTED): not a candidate
@@ -570,7 +596,7 @@ def autotune_conv(run: Callable[[], None], key: str, M: int, Cout: int, KT: int,
         for _ in range(3):
             t = min(t, _time_launches(run, reps, pair))
         if t < best_t * 0.985:  # an earlier (simpler) candidate wins near-ties
-            best, best_t = tid | ((ks if ks > 1 else 0) << 8), t
+            best, best_t = tile_code(tid, ks), t
     table[key] = best
     return apply(best)
 
@@ -607,16 +633,61 @@ def conv_wgrad(x: Rows, dy: Rows, segs_in: Segs, *, Cin: int, Cout: int, k: int,
     return dw
 
 
+class WFormat(enum.Enum):
+    """Weight formats of the conv kernels: the fd_pack_job.mode bits of the HIP packer that writes the format (| 1 for the flipped / transposed / per-Cout
+    scaled weights of the stride-1 data-gradient conv), the tile it implies (0: the direct kernel picks one) and the arithmetic it is packed for.  A conv
+    with dgrad=False outputs w.shape[0] channels, one with dgrad=True w.shape[1] (cout()).  NARROW is packed on the torch side (pack_conv_weight_narrow);
+    the plans pack DIRECT / DIRECT_F16 on the torch side too (pack_conv_weight / pack_conv_weight_f16x3)."""
+    DIRECT = (0, 0, _lib.PREC_F32)                       # [N][K/32][KH][KW][32] fp32
+    DIRECT_F16 = (4, 0, _lib.PREC_F16)                   # the (hi, lo) f16 pair [N][K/32][KH][KW][2][32] of FD_PREC_F16 (the plans: FD_PREC_F16X3)
+    F16K64 = (16, _lib.F16K64_TILE, _lib.PREC_F16)       # f16 [N][K/64][KH][KW][64]
+    WINO = (2, _lib.WINO_TILE, _lib.PREC_F32)            # Winograd F(2x2, 3x3): U = G g G^T (fd_wino_pack_weights_f32)
+    WINO4 = (8, _lib.WINO4_TILE, _lib.PREC_F32)          # Winograd F(4x4, 3x3) (fd_wino4_pack_weights_f32)
+    NARROW = (None, _lib.NARROW_TILE, _lib.PREC_F32)     # the vector-unit kernel of <= 8 output channels
+
+    def __init__(self, mode, tile, prec):
+        self.mode, self.tile, self.prec = mode, tile, prec
+
+    @staticmethod
+    def cout(shape, dgrad: bool) -> int:          # (the same rule for every format)
+        return shape[1] if dgrad else shape[0]
+
+    def pack(self, w: torch.Tensor, scale: Optional[torch.Tensor] = None, dgrad: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """OIHW fp32 weights -> this format, one HIP launch; dgrad=True: the data-gradient conv's weights (N = Cin, K = Cout) times the optional per-Cout
+        `scale`.  out: re-pack in place into an earlier result of the same call."""
+        wino = self in (WFormat.WINO, WFormat.WINO4)
+        w = w.detach().float().contiguous() if wino else w.detach().contiguous()
+        co, ci, kh, kw = w.shape
+        if out is None:
+            if wino:
+                _need_gpu(w, scale)
+                if kh != 3 or kw != 3:
+                    raise FdError("Winograd weights need a 3x3 filter")
+                n, k = (ci, co) if dgrad else (co, ci)
+                nbytes = (_lib.lib().fd_wino4_weight_bytes if self is WFormat.WINO4 else _lib.lib().fd_wino_weight_bytes)(n, k)
+                if nbytes < 0:
+                    raise FdError(f"Winograd weights need a reduction width that is a multiple of 8 (got {k})")
+                out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
+            elif self is WFormat.F16K64:         # (half the byte size of the fp32 packing, as an fp32-typed buffer)
+                out = torch.empty(co * ci * kh * kw // 2, dtype=torch.float32, device=w.device)
+            elif self.mode is not None:
+                out = torch.empty((ci, co // 32, kh, kw, 32) if dgrad else (co, ci // 32, kh, kw, 32), dtype=torch.float32, device=w.device)
+            else:
+                raise FdError(f"{self.name} weights have no HIP packer")
+        sp = scale.data_ptr() if (scale is not None and dgrad) else None
+        if wino:
+            name = "fd_wino4_pack_weights_f32" if self is WFormat.WINO4 else "fd_wino_pack_weights_f32"
+            check(getattr(_lib.lib(), name)(w.data_ptr(), sp, out.data_ptr(), co, ci, int(dgrad), _stream()), name)
+        else:
+            check(_lib.lib().fd_pack_conv_weight_f32(w.data_ptr(), sp, out.data_ptr(), co, ci, kh, kw, self.mode | int(dgrad), _stream()),
+                  "fd_pack_conv_weight_f32")
+        return out
+
+
 def pack_conv_weight_hip(w: torch.Tensor, scale: Optional[torch.Tensor] = None, dgrad: bool = False, f16: bool = False) -> torch.Tensor:
     """pack_conv_weight (dgrad=False) or dgrad_weight with a per-output-channel scale (dgrad=True) as one HIP launch; f16=True: the
     (hi, lo) f16 operand format of FD_PREC_F16 / FD_PREC_F16X3 (same byte size, returned as an fp32-typed buffer)."""
-    w = w.detach().contiguous()
-    co, ci, kh, kw = w.shape
-    out = torch.empty((ci, co // 32, kh, kw, 32) if dgrad else (co, ci // 32, kh, kw, 32), dtype=torch.float32, device=w.device)
-    check(_lib.lib().fd_pack_conv_weight_f32(w.data_ptr(), scale.data_ptr() if (scale is not None and dgrad) else None,
-                                             out.data_ptr(), co, ci, kh, kw, (1 if dgrad else 0) | (4 if f16 else 0), _stream()),
-          "fd_pack_conv_weight_f32")
-    return out
+    return (WFormat.DIRECT_F16 if f16 else WFormat.DIRECT).pack(w, scale, dgrad)
 
 
 F16K64 = os.environ.get("FD_AMP_K64", "1") != "0"       # "0": AMP convs stay on the K-tile-32 f16 instantiations of the fp32 kernel
@@ -627,52 +698,25 @@ def f16k64_ok(Cin: int, Cout: int) -> bool:
     return Cin % 64 == 0 and Cout % 4 == 0
 
 
+def amp_format(K: int, N: int) -> WFormat:
+    """Weight format of a dense AMP (FD_PREC_F16) conv of reduction width K and N outputs: FD_TILE_F16K64 wherever the widths allow."""
+    return WFormat.F16K64 if F16K64 and f16k64_ok(K, N) else WFormat.DIRECT_F16
+
+
 def pack_conv_weight_f16k64(w: torch.Tensor, scale: Optional[torch.Tensor] = None, dgrad: bool = False) -> torch.Tensor:
-    """OIHW fp32 -> FD_TILE_F16K64's operand: f16 [N][K/64][KH][KW][64] (dgrad=True: the flipped / transposed / per-Cout scaled weights of the data-gradient conv),
-    one HIP launch (fd_pack_conv_weight_f32 mode | 16); returned as an fp32-typed buffer of half the element count."""
-    w = w.detach().contiguous()
-    co, ci, kh, kw = w.shape
-    out = torch.empty(co * ci * kh * kw // 2, dtype=torch.float32, device=w.device)
-    check(_lib.lib().fd_pack_conv_weight_f32(w.data_ptr(), scale.data_ptr() if (scale is not None and dgrad) else None,
-                                             out.data_ptr(), co, ci, kh, kw, (1 if dgrad else 0) | 16, _stream()), "fd_pack_conv_weight_f32")
-    return out
+    """OIHW fp32 -> FD_TILE_F16K64's operand (WFormat.F16K64)."""
+    return WFormat.F16K64.pack(w, scale, dgrad)
 
 
 def pack_conv_weight_wino(w: torch.Tensor, scale: Optional[torch.Tensor] = None, dgrad: bool = False) -> torch.Tensor:
     """OIHW [Cout, Cin, 3, 3] -> the Winograd F(2x2, 3x3) operand of FD_TILE_WINOGRAD: U = G g G^T per (cout, cin), packed
-    [ceil(N/32)][K/8][16][32][8] (N = Cout, K = Cin; dgrad=True: the flipped / transposed weights of the data-gradient conv,
-    N = Cin, K = Cout, times an optional per-Cout scale).  One HIP launch (fd_wino_pack_weights_f32)."""
-    w = w.detach().float().contiguous()
-    _need_gpu(w, scale)
-    co, ci, kh, kw = w.shape
-    if kh != 3 or kw != 3:
-        raise FdError("Winograd weights need a 3x3 filter")
-    n, k = (ci, co) if dgrad else (co, ci)
-    nbytes = _lib.lib().fd_wino_weight_bytes(n, k)
-    if nbytes < 0:
-        raise FdError(f"Winograd weights need a reduction width that is a multiple of 8 (got {k})")
-    out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
-    check(_lib.lib().fd_wino_pack_weights_f32(w.data_ptr(), scale.data_ptr() if (scale is not None and dgrad) else None,
-                                              out.data_ptr(), co, ci, 1 if dgrad else 0, _stream()), "fd_wino_pack_weights_f32")
-    return out
+    [ceil(N/32)][K/8][16][32][8] (N = Cout, K = Cin; dgrad=True: N = Cin, K = Cout)."""
+    return WFormat.WINO.pack(w, scale, dgrad)
 
 
 def pack_conv_weight_wino4(w: torch.Tensor, scale: Optional[torch.Tensor] = None, dgrad: bool = False) -> torch.Tensor:
-    """OIHW [Cout, Cin, 3, 3] -> the Winograd F(4x4, 3x3) operand of FD_TILE_WINOGRAD4 (fd_wino4_pack_weights_f32), one HIP launch;
-    dgrad=True: the flipped / transposed weights of the data-gradient conv (N = Cin, K = Cout) times an optional per-Cout scale."""
-    w = w.detach().float().contiguous()
-    _need_gpu(w, scale)
-    co, ci, kh, kw = w.shape
-    if kh != 3 or kw != 3:
-        raise FdError("Winograd weights need a 3x3 filter")
-    n, k = (ci, co) if dgrad else (co, ci)
-    nbytes = _lib.lib().fd_wino4_weight_bytes(n, k)
-    if nbytes < 0:
-        raise FdError(f"Winograd weights need a reduction width that is a multiple of 8 (got {k})")
-    out = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
-    check(_lib.lib().fd_wino4_pack_weights_f32(w.data_ptr(), scale.data_ptr() if (scale is not None and dgrad) else None,
-                                               out.data_ptr(), co, ci, 1 if dgrad else 0, _stream()), "fd_wino4_pack_weights_f32")
-    return out
+    """OIHW [Cout, Cin, 3, 3] -> the Winograd F(4x4, 3x3) operand of FD_TILE_WINOGRAD4."""
+    return WFormat.WINO4.pack(w, scale, dgrad)
 
 
 NARROW = os.environ.get("FD_NARROW", "1") != "0"     # "0": layers of <= 8 output channels stay on the Winograd / direct MFMA kernels
@@ -702,8 +746,8 @@ def pack_conv_weight_narrow(w: torch.Tensor) -> torch.Tensor:
 
 
 def wino4_ok(Cin: int, Cout: int, k: int, stride: int, pad: int, dil: int) -> bool:
-    """Shapes FD_TILE_WINOGRAD4 covers."""
-    return k == 3 and stride == 1 and pad == dil and dil in (1, 2) and Cin % 8 == 0 and Cout % 4 == 0
+    """Shapes FD_TILE_WINOGRAD4 covers: those of FD_TILE_WINOGRAD."""
+    return wino_ok(Cin, Cout, k, stride, pad, dil)
 
 
 # FD_WINOGRAD4: "1" (default) = layers the F(4x4, 3x3) kernel covers run on it where wino4_choice's cost model says it beats F(2x2, 3x3);
@@ -752,8 +796,10 @@ def wino_tiles(segs: Segs, dil: int) -> int:
     return sum(segs.batch * dil * dil * ((-(-h // dil) + 1) // 2) * ((-(-w // dil) + 1) // 2) for h, w in segs.level_hw())
 
 
-# FD_WINOGRAD=force: every layer the Winograd kernel covers runs on it, whatever its size (tests exercise the kernel on small maps this way)
-WINO_FORCE = os.environ.get("FD_WINOGRAD", "1") == "force"
+# FD_WINOGRAD: "1" (default) = 3x3 stride-1 'same' convs (dilation 1 / 2, Cin % 8 == 0) of exact-fp32 arithmetic run on the Winograd F(2x2, 3x3) kernel
+# (fd_conv_wino.hip: 2.25x fewer MFMAs, still fp32 arithmetic) where wino_choice says it wins; "force" = wherever it applies, whatever the map size (tests exercise
+# the kernel on small maps this way); "0" = every conv on the direct implicit-GEMM kernel (and never on F(4x4) either)
+WINO_MODE = os.environ.get("FD_WINOGRAD", "1")
 
 
 def wino_choice(segs: Segs, Cin: int, Cout: int, dil: int, allow_split: bool = True) -> Tuple[bool, int]:
@@ -763,7 +809,7 @@ def wino_choice(segs: Segs, Cin: int, Cout: int, dil: int, allow_split: bool = T
     fitted to MI355X measurements (batch 1 .. 16 at 512^2 / 640^2: profiles/r02z_layer_times.tsv, r02z_bench_latency_b*.json):
       t_wino(ks) = (1.5 * Cin / 8 / ks + 3) us * max(1, ks * workgroups / (0.55 * resident slots))  [+ 7 us for the combine launch, ks > 1]
       t_direct   = max(21 us [narrow Cout <= 96: no split-K there, 1.9 us per K-tile], FLOPs / 95 TFLOP/s)"""
-    if WINO_FORCE:
+    if WINO_MODE == "force":
         return True, 1
     best_t, best_ks, t_d = _wino_times(segs, Cin, Cout, dil, allow_split)[1:]
     return best_t < t_d, best_ks
@@ -795,6 +841,42 @@ def wino_preferred(segs: Segs, Cin: int, Cout: int, dil: int) -> bool:
     return wino_choice(segs, Cin, Cout, dil, allow_split=False)[0]
 
 
+class ConvChoice(NamedTuple):
+    fmt: WFormat        # the weight format, which names the kernel family: NARROW / WINO / WINO4, or the direct kernel (DIRECT / DIRECT_F16 / F16K64)
+    ksplit: int         # the Winograd kernels' split-K factor (1 elsewhere: the direct kernel's split comes with its tile)
+    prec: int           # fd_conv_params.precision
+
+
+def choose_conv(segs: Segs, Cin: int, Cout: int, k: int, stride: int, pad: int, dil: int, arith: str = "f32", *, split_k: bool = True,
+                narrow: bool = True, wino4: bool = True, res: bool = False, gate: bool = False, gate_b: bool = False, gn_stats: bool = False, aligned: bool = True,
+                force_wino: bool = False) -> ConvChoice:
+    """Kernel family, weight format and Winograd split of one conv layer: the one rule of the inference plans (engine.add_conv and the pre-decisions of
+    its callers) and of the training nodes (train_ops).  Touches no tensor and no GPU.
+      arith: "f32" (exact fp32), "mixed" (the GEMM-addressed 1x1 layers on split-f16 products), "f16x3" (split-f16 products everywhere),
+             "amp" (FD_PREC_F16 operands: the AMP training step -- always the direct kernel)
+      what the caller offers: split_k (a split-K workspace), narrow (the vector-unit kernel), wino4 (the F(4x4) kernel), the epilogues it asks for (res, gate, gate_b: the gate is
+      a GroupNorm's affine, gn_stats), aligned (16-byte addressable output and residual views: the Winograd kernels' stores), force_wino (the head
+      tower, the roofline launch: Winograd whatever its cost model says)."""
+    if arith == "amp":
+        return ConvChoice(amp_format(Cin, Cout), 1, _lib.PREC_F16)
+    exact = arith in ("f32", "mixed")
+    # <= 8 output channels (the centre-ness / box predictor): the vector-unit kernel where the map has enough tiles to fill the chip
+    if (exact and narrow and NARROW and not res and (not gate or gate_b) and not gn_stats and narrow_ok(Cin, Cout, k, stride, pad, dil)
+            and narrow_tiles(segs) >= NARROW_MIN_TILES):
+        return ConvChoice(WFormat.NARROW, 1, _lib.PREC_F32)
+    if exact and WINO_MODE != "0" and aligned and wino_ok(Cin, Cout, k, stride, pad, dil):
+        if wino4 and not gate and not gn_stats:        # F(4x4) where its cost model beats F(2x2) / the direct kernel: no gate / statistics epilogue
+            use4, ks4 = wino4_choice(segs, Cin, Cout, dil, split_k)
+            if use4:
+                return ConvChoice(WFormat.WINO4, ks4, _lib.PREC_F32)
+        use, ks = wino_choice(segs, Cin, Cout, dil, split_k)
+        if use or force_wino:
+            return ConvChoice(WFormat.WINO, ks, _lib.PREC_F32)
+    if arith == "f16x3" or (arith == "mixed" and k == 1 and stride == 1 and not gate and not gn_stats and Cin % 32 == 0):
+        return ConvChoice(WFormat.DIRECT_F16, 1, _lib.PREC_F16X3)
+    return ConvChoice(WFormat.DIRECT, 1, _lib.PREC_F32)
+
+
 def strided_dgrad_classes(k: int, stride: int, pad: int):
     """Parity classes of the data gradient of a k x k conv with `stride`: for input rows h = stride*i + a only the taps
     r = r0 + stride*t contribute, and dY row = i + c - t.  Returns per class a: (r0, T taps, c) with r0 = (a + pad) % stride,
@@ -820,6 +902,7 @@ def conv_dgrad_strided(dy: Rows, w: torch.Tensor, scale: Optional[torch.Tensor],
         return False                      # (the class convs of k = 3 / pad 1 and k = 1 / pad 0 need no padding; others are not built)
     segs = Segs.make(N, [(Ho, Wo)])
     wd = w.detach()
+    fmt = amp_format(Cout, Cin) if precision else WFormat.DIRECT       # AMP: the class convs on FD_TILE_F16K64 where the widths allow
     for a, (r0, Ta, _) in enumerate(cls):
         Ia = len(range(a, H, stride))
         for b, (q0, Tb, _) in enumerate(cls):
@@ -827,12 +910,8 @@ def conv_dgrad_strided(dy: Rows, w: torch.Tensor, scale: Optional[torch.Tensor],
             if Ta == 0 or Tb == 0 or Ia == 0 or Jb == 0:
                 continue
             sub = wd[:, :, r0::stride, q0::stride].contiguous()                      # [Cout, Cin, Ta, Tb]
-            k64 = bool(precision) and F16K64 and f16k64_ok(Cout, Cin)               # AMP: the class convs on FD_TILE_F16K64 where the widths allow
-            out = torch.empty(Cin * Cout * Ta * Tb // (2 if k64 else 1), dtype=torch.float32, device=w.device)
-            check(_lib.lib().fd_pack_conv_weight_f32(sub.data_ptr(), scale.data_ptr() if scale is not None else None, out.data_ptr(),
-                                                     Cout, Cin, Ta, Tb, 1 | (16 if k64 else 4 if precision else 0), _stream()), "fd_pack_conv_weight_f32")
-            conv_call(dy, segs, out, dx, Cin=Cout, Cout=Cin, k=Ta, kw=Tb, stride=1, pad=0, res=res, res_mask=res_mask,
-                      out_hw=(Ia, Jb), scatter=(stride, stride, a, b, H, W), precision=precision, tile=_lib.F16K64_TILE if k64 else 0)()
+            conv_call(dy, segs, fmt.pack(sub, scale, dgrad=True), dx, Cin=Cout, Cout=Cin, k=Ta, kw=Tb, stride=1, pad=0, res=res, res_mask=res_mask,
+                      out_hw=(Ia, Jb), scatter=(stride, stride, a, b, H, W), precision=precision, tile=fmt.tile)()
     return True
 
 

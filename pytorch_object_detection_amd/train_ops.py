@@ -20,7 +20,7 @@ not keep).  Narrow outputs (class / centre-ness / box logits) are padded to 32 c
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -71,17 +71,6 @@ def amp_prec() -> int:
     if AMP_F16 and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.float16:
         return _lib.PREC_F16
     return _lib.PREC_F32
-
-
-AMP_K64 = os.environ.get("FD_AMP_K64", "1") != "0"      # "0": AMP convs stay on the single-plane f16 instantiations of the fp32 kernel (K-tiles of 32 channels)
-
-
-def amp_pack(prec: int, K: int, Cout: int = 4):
-    """PACKS.get's `f16` for a dense conv of reduction width K under the current arithmetic: False (fp32), True (the (hi, lo) f16 pair format of the fp32 kernel's f16
-    instantiations) or 2 (FD_TILE_F16K64: K-tiles of 64 channels, fd_conv_f16.hip -- whenever the layer's widths allow)."""
-    if not prec:
-        return False
-    return 2 if (AMP_K64 and ops.f16k64_ok(K, Cout)) else True
 
 
 _STOCK = os.environ.get("FD_TRAIN_STOCK_CONV") == "1"   # diagnostic: route every layer to the stock ops (timing comparisons)
@@ -214,6 +203,12 @@ def _act_id(act) -> int:
 
 
 # ------------------------------------------------------------------------------------------- dense convolution
+class Packed(NamedTuple):
+    w: torch.Tensor          # the packed weights
+    fmt: ops.WFormat         # their format (names the kernel and the arithmetic)
+    cout: int                # output channels of the conv they feed
+
+
 class _PackCache:
     """Packed conv weights of the model's PARAMETERS, kept across steps and refreshed by ONE launch per step.
 
@@ -226,68 +221,45 @@ class _PackCache:
     directly AND updates weights through `.data` must call PACKS.refresh() itself before the next forward."""
 
     def __init__(self):
-        self.entries: dict = {}     # key -> [weakref(param), scale, dgrad, out, version]
+        self.entries: dict = {}     # key -> [weakref(param), scale, dgrad, Packed, version]
         self.params: dict = {}      # data_ptr -> weakref(param)
         self.table = None           # (signature, device tensor of fd_pack_job, max_elems)
 
     @staticmethod
-    def _key(w, scale, dgrad, wino=0, f16=False):       # wino: 0 = direct kernel's packing, 1 = Winograd F(2x2, 3x3), 2 = Winograd F(4x4, 3x3); f16: False / True (hi, lo pair) / 2 (K-tile-64 f16)
-        return (w.data_ptr(), tuple(w.shape), bool(dgrad), scale.data_ptr() if (scale is not None and dgrad) else 0,
-                (16 if f16 == 2 else 2 if f16 else 0) + (1 if int(wino) == 1 else 0) + (8 if int(wino) == 2 else 0))
+    def _key(w, scale, dgrad, fmt):
+        return (w.data_ptr(), tuple(w.shape), bool(dgrad), scale.data_ptr() if (scale is not None and dgrad) else 0, fmt)
 
     @staticmethod
-    def _pack_now(w, scale, dgrad, wino, f16=False):
-        if not wino:
-            if f16 == 2:       # FD_TILE_F16K64's operand (fd_conv_f16.hip)
-                out = ops.pack_conv_weight_f16k64(w, scale, dgrad)
-                out._fd_prec, out._fd_k64, out._fd_cout = _lib.PREC_F16, True, (w.shape[1] if dgrad else w.shape[0])
-                return out
-            out = ops.pack_conv_weight_hip(w, scale, dgrad, f16)
-            out._fd_prec = _lib.PREC_F16 if f16 else _lib.PREC_F32
-            return out
-        out = ops.pack_conv_weight_wino4(w, scale, dgrad) if int(wino) == 2 else ops.pack_conv_weight_wino(w, scale, dgrad)
-        out._fd_wino = (w.shape[1] if dgrad else w.shape[0])       # marks the Winograd packing for _conv_launch (value = output channels)
-        out._fd_wino_tile = _lib.WINO4_TILE if int(wino) == 2 else _lib.WINO_TILE
-        return out
+    def _pack_now(w, scale, dgrad, fmt) -> Packed:
+        return Packed(fmt.pack(w, scale, dgrad), fmt, fmt.cout(w.shape, dgrad))
 
-    def get(self, w: torch.Tensor, scale: Optional[torch.Tensor] = None, dgrad: bool = False, wino: int = 0, f16: bool = False) -> torch.Tensor:
-        """Packed weights for the conv kernel: the direct kernel's layout, or (3x3 stride-1 'same' layers) the Winograd packing -- wino=1: F(2x2, 3x3)
-        of fd_conv_wino.hip, wino=2: F(4x4, 3x3) of fd_conv_wino4.hip; dgrad=True = the flipped / transposed / BN-scaled weights of the data gradient."""
+    def get(self, w: torch.Tensor, scale: Optional[torch.Tensor] = None, dgrad: bool = False, fmt: ops.WFormat = ops.WFormat.DIRECT) -> Packed:
+        """Weights packed in `fmt` (conv_format's choice); dgrad=True = the flipped / transposed / BN-scaled weights of the data gradient."""
         import weakref
         if isinstance(w, nn.Parameter) and w.is_contiguous():
             self.params[w.data_ptr()] = weakref.ref(w)
         ref = self.params.get(w.data_ptr())
         owner = ref() if ref is not None else None
         if owner is None or owner.data_ptr() != w.data_ptr() or owner.shape != w.shape or not w.is_contiguous():
-            return self._pack_now(w, scale, dgrad, wino, f16)             # a temporary (merged / padded weights): pack now
-        key = self._key(w, scale, dgrad, wino, f16)
+            return self._pack_now(w, scale, dgrad, fmt)                   # a temporary (merged / padded weights): pack now
+        key = self._key(w, scale, dgrad, fmt)
         e = self.entries.get(key)
         if e is not None and e[0]() is not owner:       # the address was recycled by another parameter: drop the old entry
             e = None
         if e is None:
-            out = self._pack_now(w, scale, dgrad, wino, f16)
+            out = self._pack_now(w, scale, dgrad, fmt)
             self.entries[key] = [ref, scale, dgrad, out, w._version]
             self.table = None
             return out
         if e[4] != w._version:                                            # changed since the last refresh: re-pack in place
-            co, ci, kh, kw = w.shape
-            sp = scale.data_ptr() if (scale is not None and dgrad) else None
-            if int(wino) == 2:
-                ops.check(_lib.lib().fd_wino4_pack_weights_f32(w.data_ptr(), sp, e[3].data_ptr(), co, ci, 1 if dgrad else 0, ops._stream()),
-                          "fd_wino4_pack_weights_f32")
-            elif wino:
-                ops.check(_lib.lib().fd_wino_pack_weights_f32(w.data_ptr(), sp, e[3].data_ptr(), co, ci, 1 if dgrad else 0, ops._stream()),
-                          "fd_wino_pack_weights_f32")
-            else:
-                ops.check(_lib.lib().fd_pack_conv_weight_f32(w.data_ptr(), sp, e[3].data_ptr(), co, ci, kh, kw, (1 if dgrad else 0) | (16 if f16 == 2 else 4 if f16 else 0),
-                                                             ops._stream()), "fd_pack_conv_weight_f32")
+            fmt.pack(w, scale, dgrad, out=e[3].w)
             e[4] = w._version
         return e[3]
 
     def refresh(self) -> None:
         import ctypes as C
         live = {}
-        newest: dict = {}        # (param address, shape) -> newest data-gradient entry: a re-folded frozen BN (load_state_dict) makes
+        newest: dict = {}        # (param address, shape, format) -> newest data-gradient entry: a re-folded frozen BN (load_state_dict) makes
         for key, e in self.entries.items():      # a new scale tensor and a new entry; the superseded one is dropped here
             if key[2]:
                 newest[(key[0], key[1], key[4])] = key
@@ -306,12 +278,11 @@ class _PackCache:
             mx = 0
             for j, (key, e) in zip(jobs, live.items()):
                 co, ci, kh, kw = key[1]
-                j.w, j.scale, j.out = key[0], (e[1].data_ptr() if (e[1] is not None and e[2]) else None), e[3].data_ptr()
-                j.Cout, j.Cin, j.KH, j.KW, j.mode = co, ci, kh, kw, ((8 if key[4] & 8 else 2 if key[4] & 1 else 0) + (1 if e[2] else 0)
-                                                                     + (4 if key[4] & 2 else 0) + (16 if key[4] & 16 else 0))
+                j.w, j.scale, j.out = key[0], (e[1].data_ptr() if (e[1] is not None and e[2]) else None), e[3].w.data_ptr()
+                j.Cout, j.Cin, j.KH, j.KW, j.mode = co, ci, kh, kw, key[4].mode | int(e[2])
                 mx = max(mx, co * ci * kh * kw)
             raw = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).clone()
-            dev = next(iter(live.values()))[3].device
+            dev = next(iter(live.values()))[3].w.device
             self.table = (raw.to(dev), len(live), mx)
         tab, n, mx = self.table
         ops.check(_lib.lib().fd_pack_conv_weights_batch_f32(tab.data_ptr(), n, mx, ops._stream()), "fd_pack_conv_weights_batch_f32")
@@ -322,76 +293,56 @@ class _PackCache:
 PACKS = _PackCache()
 
 
-def _wino(Cin: int, Cout: int, k: int, stride: int, pad: int, dil: int, segs: Segs, prec: int = 0) -> int:
-    """3x3 stride-1 'same' layers run on a Winograd kernel -- forward (Cin -> Cout) and, with the channel roles swapped, data
-    gradient -- unless FD_WINOGRAD=0 (the switch of the inference plans) or the map is so small that the direct kernel's split-K
-    wins (ops.wino_preferred, the rule of the inference plans).  Returns PACKS.get's `wino`: 0 = direct, 1 = F(2x2, 3x3), 2 = F(4x4, 3x3)
-    (ops.wino4_choice, the rule of the inference plans)."""
-    from . import engine
-    if prec != 0 or not engine.WINOGRAD:
-        return 0
-    if ops.wino4_ok(Cin, Cout, k, stride, pad, dil) and ops.wino4_choice(segs, Cin, Cout, dil, allow_split=False)[0]:      # (no workspace here)
-        return 2
-    return 1 if (ops.wino_ok(Cin, Cout, k, stride, pad, dil) and ops.wino_preferred(segs, Cin, Cout, dil)) else 0
+def conv_format(Cin: int, Cout: int, k: int, stride: int, pad: int, dil: int, segs: Segs, prec: int = 0) -> ops.WFormat:
+    """PACKS.get's `fmt` for a dense conv (forward Cin -> Cout, or a data gradient with the channel roles swapped) under the node's arithmetic: ops.choose_conv
+    with what the training nodes offer -- no split-K workspace, no vector-unit kernel.  3x3 stride-1 'same' fp32 layers go to a Winograd kernel as in the plans,
+    AMP (FD_PREC_F16) layers stay on the direct kernel (F16K64 where the widths allow)."""
+    return ops.choose_conv(segs, Cin, Cout, k, stride, pad, dil, "amp" if prec else "f32", split_k=False, narrow=False).fmt
+
 
 _TILE_CACHE: dict = {}
 
 
-def _conv_launch(x: torch.Tensor, segs: Segs, w_packed: torch.Tensor, y: torch.Tensor, *, k, stride, pad, dil, scale=None,
+def _conv_launch(x: torch.Tensor, segs: Segs, packed: Packed, y: torch.Tensor, *, k, stride, pad, dil, scale=None,
                  shift=None, res: Optional[torch.Tensor] = None, act=ACT_NONE, res_mask: bool = False) -> None:
-    """y = act(conv(x, w) * scale + shift + res) on contiguous rows buffers; w_packed from ops.pack_conv_weight_hip.
-    The block tile comes from the same table / heuristic / FD_AUTOTUNE timing as the inference plans (ops.autotune_conv),
-    remembered per shape for the process."""
-    wino_cout = getattr(w_packed, "_fd_wino", 0)
-    if wino_cout:        # the Winograd packing (PACKS.get(..., wino=True)): fd_conv_wino.hip, no tile choice
-        ops.conv_call(_r(x), segs, w_packed, _r(y), Cin=x.shape[1], Cout=wino_cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale,
-                      shift=shift, res=_r(res) if res is not None else None, act=act, res_mask=res_mask, tile=getattr(w_packed, "_fd_wino_tile", _lib.WINO_TILE))()
+    """y = act(conv(x, w) * scale + shift + res) on contiguous rows buffers; `packed` from PACKS.get.  Winograd / F16K64 formats name their kernel (the
+    library picks the block tile).  The direct kernel's tile comes from the same table as the inference plans', remembered per key for the process: fp32
+    launches take ops.autotune_conv's choice (table / shape heuristic / FD_AUTOTUNE timing); f16 launches (AMP) have own table entries ("f16|" keys, timed by
+    `FD_AUTOTUNE=1 FD_AMP=1 python tools/tune_train.py`), and a miss takes the library's tile -- the fp32 heuristic would name single-buffer tiles the f16
+    kernel is not built for -- unless FD_AUTOTUNE times it."""
+    w, fmt, Cout = packed
+    Cin = x.shape[1]
+    rx, ry, rr = _r(x), _r(y), (_r(res) if res is not None else None)
+    if fmt.tile:
+        ops.conv_call(rx, segs, w, ry, Cin=Cin, Cout=Cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale, shift=shift, res=rr, act=act,
+                      res_mask=res_mask, precision=fmt.prec, tile=fmt.tile)()
         return
-    if getattr(w_packed, "_fd_k64", False):      # AMP: f16 operands on K-tiles of 64 channels (the library picks the block tile)
-        ops.conv_call(_r(x), segs, w_packed, _r(y), Cin=x.shape[1], Cout=w_packed._fd_cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale, shift=shift,
-                      res=_r(res) if res is not None else None, act=act, res_mask=res_mask, precision=_lib.PREC_F16, tile=_lib.F16K64_TILE)()
-        return
-    Cin, Cout = x.shape[1], w_packed.shape[0]
+    f16 = fmt.prec == _lib.PREC_F16
     out_rows = y.shape[0]
-    prec = getattr(w_packed, "_fd_prec", 0)
-    KT = (Cin // 32) * k * k
-    hw = "+".join(f"{h}x{w}" for h, w in segs.level_hw())
-    key = f"B{segs.batch}|{hw}|{Cin}>{Cout}|k{k}s{stride}p{pad}d{dil}|res{int(res is not None)}|xcs{Cin}|ycs{Cout}"   # (mask / add: same cost)
-    if prec:
-        # f16 operands (AMP): own table entries ("f16|" keys, timed by `FD_AUTOTUNE=1 FD_AMP=1 python tools/tune_train.py`); a miss takes the
-        # library's tile choice (the fp32 heuristic would name single-buffer tiles the f16 kernel is not built for), or is timed with FD_AUTOTUNE=1
-        key = "f16|" + key
-        code = _TILE_CACHE.get(key)
-        if code is None:
-            code = ops._tune_table().get(key)
-            if code is None and ops._TUNE_MODE != "0":
-                nb = _lib.lib().fd_conv_workspace_bytes(out_rows, Cout, ops.KSPLIT_MAX)
-                ws = torch.empty(nb // 4, dtype=torch.float32, device=x.device) if 0 < nb <= 256 * 1024 * 1024 else None
-                probe = ops.conv_call(_r(x), segs, w_packed, _r(y), Cin=Cin, Cout=Cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale, shift=shift,
-                                      res=_r(res) if res is not None else None, act=act, workspace=ws, res_mask=res_mask, precision=prec)
-                code = ops.autotune_conv(probe, key, out_rows, Cout, KT)
-            code = _TILE_CACHE[key] = int(code or 0)
-        ws = None
-        if (code >> 8) > 1:
-            ws = torch.empty(_lib.lib().fd_conv_workspace_bytes(out_rows, Cout, code >> 8) // 4, dtype=torch.float32, device=x.device)
-        ops.conv_call(_r(x), segs, w_packed, _r(y), Cin=Cin, Cout=Cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale, shift=shift,
-                      res=_r(res) if res is not None else None, act=act, res_mask=res_mask, precision=prec, tile=code & 0xFF,
-                      ksplit=max(1, code >> 8), workspace=ws)()
-        return
+    key = ops.tune_key(segs, Cin, Cout, k, stride, pad, dil, res=res is not None, xcs=Cin, ycs=Cout, pre="f16" if f16 else "")   # (mask / add: same cost)
     code = _TILE_CACHE.get(key)
+    if code is None and f16:
+        code = ops._tune_table().get(key, 0 if ops._TUNE_MODE == "0" else None)
+        if code is not None:
+            code = _TILE_CACHE[key] = int(code)
+    ks = ops.tile_split(code)[1] if code is not None else 0
+    # split-K scratch: an f16 code's own split; else (fp32, or a code still to be tuned) the widest split, up to 256 MB
     ws = None
-    if code is None or (code >> 8) > 1:
+    if f16 and ks > 1:
+        ws = torch.empty(_lib.lib().fd_conv_workspace_bytes(out_rows, Cout, ks) // 4, dtype=torch.float32, device=x.device)
+    elif code is None or ks > 1:
         nb = _lib.lib().fd_conv_workspace_bytes(out_rows, Cout, ops.KSPLIT_MAX)
         if 0 < nb <= 256 * 1024 * 1024:
             ws = torch.empty(nb // 4, dtype=torch.float32, device=x.device)
-    call = ops.conv_call(_r(x), segs, w_packed, _r(y), Cin=Cin, Cout=Cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale,
-                         shift=shift, res=_r(res) if res is not None else None, act=act, workspace=ws, res_mask=res_mask)
-    if code is None:
-        code = _TILE_CACHE[key] = ops.autotune_conv(call, key, out_rows, Cout, KT)
-    p = call.params
-    p.tile, p.ksplit = code & 0xFF, max(1, code >> 8)
-    if p.ksplit > 1 and ws is None:
-        p.ksplit = 1
+    call = ops.conv_call(rx, segs, w, ry, Cin=Cin, Cout=Cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale, shift=shift, res=rr, act=act,
+                         workspace=ws, res_mask=res_mask, precision=fmt.prec)
+    if code is None:              # (autotune_conv installs the code it returns on the launch)
+        code = _TILE_CACHE[key] = ops.autotune_conv(call, key, out_rows, Cout, (Cin // 32) * k * k)
+    else:
+        p = call.params
+        p.tile, p.ksplit = ops.tile_split(code)
+        if p.ksplit > 1 and ws is None:
+            p.ksplit = 1
     call()
 
 
@@ -431,7 +382,7 @@ class _ConvRows(torch.autograd.Function):
         Cout, _, k, _ = weight.shape
         so = ops.conv_out_segs(segs, k, stride, pad, dil)
         y = torch.empty(so.rows, Cout, dtype=torch.float16 if (f16_io and out_f16) else torch.float32, device=x.device)
-        _conv_launch(x, segs, PACKS.get(weight, wino=_wino(x.shape[1], Cout, k, stride, pad, dil, segs, prec), f16=amp_pack(prec, x.shape[1], Cout)), y, k=k, stride=stride,
+        _conv_launch(x, segs, PACKS.get(weight, fmt=conv_format(x.shape[1], Cout, k, stride, pad, dil, segs, prec)), y, k=k, stride=stride,
                      pad=pad, dil=dil, scale=scale.float() if scale is not None else None, shift=shift.detach().float().contiguous() if shift is not None else None,
                      res=residual.contiguous() if residual is not None else None, act=act)
         ctx.res_dtype = residual.dtype if residual is not None else None
@@ -455,7 +406,7 @@ class _ConvRows(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             if stride == 1 and Cout % 32 == 0:
                 gx = torch.empty_like(x)
-                _conv_launch(g, so, PACKS.get(weight, scale, dgrad=True, wino=_wino(Cout, Cin, k, stride, dil * (k - 1) - pad, dil, so, prec), f16=amp_pack(prec, Cout, Cin)),
+                _conv_launch(g, so, PACKS.get(weight, scale, dgrad=True, fmt=conv_format(Cout, Cin, k, stride, dil * (k - 1) - pad, dil, so, prec)),
                              gx, k=k, stride=1, pad=dil * (k - 1) - pad, dil=dil)
             elif segs.nseg == 1 and stride > 1 and dil == 1 and (gx := _strided_dgrad(g, weight, scale, segs, k, stride, pad, prec=prec)) is not None:
                 pass                                   # strided layer: one exact-FLOP launch per parity class (ops.conv_dgrad_strided)
@@ -529,15 +480,15 @@ class _BottleneckRows(torch.autograd.Function):
         y1 = torch.empty(segs.rows, P, dtype=st, device=dev)
         y2 = torch.empty(so.rows, P, dtype=st, device=dev)
         out = torch.empty(so.rows, C4, dtype=st, device=dev)
-        _conv_launch(x, segs, PACKS.get(w1, f16=amp_pack(prec, w1.shape[1], w1.shape[0])), y1, k=1, stride=1, pad=0, dil=1, scale=c1[0], shift=c1[1], act=ACT_RELU)
-        _conv_launch(y1, segs, PACKS.get(w2, wino=_wino(P, P, 3, stride, 1, 1, segs, prec), f16=amp_pack(prec, P, P)), y2, k=3, stride=stride, pad=1, dil=1, scale=c2[0],
+        _conv_launch(x, segs, PACKS.get(w1, fmt=conv_format(w1.shape[1], P, 1, 1, 0, 1, segs, prec)), y1, k=1, stride=1, pad=0, dil=1, scale=c1[0], shift=c1[1], act=ACT_RELU)
+        _conv_launch(y1, segs, PACKS.get(w2, fmt=conv_format(P, P, 3, stride, 1, 1, segs, prec)), y2, k=3, stride=stride, pad=1, dil=1, scale=c2[0],
                      shift=c2[1], act=ACT_RELU)
         if wd is not None:
             idt = torch.empty(so.rows, C4, dtype=st, device=dev)
-            _conv_launch(x, segs, PACKS.get(wd, f16=amp_pack(prec, wd.shape[1], wd.shape[0])), idt, k=1, stride=stride, pad=0, dil=1, scale=cd[0], shift=cd[1])
+            _conv_launch(x, segs, PACKS.get(wd, fmt=conv_format(wd.shape[1], wd.shape[0], 1, stride, 0, 1, segs, prec)), idt, k=1, stride=stride, pad=0, dil=1, scale=cd[0], shift=cd[1])
         else:
             idt = x
-        _conv_launch(y2, so, PACKS.get(w3, f16=amp_pack(prec, w3.shape[1], w3.shape[0])), out, k=1, stride=1, pad=0, dil=1, scale=c3[0], shift=c3[1], res=idt,
+        _conv_launch(y2, so, PACKS.get(w3, fmt=conv_format(P, C4, 1, 1, 0, 1, so, prec)), out, k=1, stride=1, pad=0, dil=1, scale=c3[0], shift=c3[1], res=idt,
                      act=ACT_RELU)
         ctx.save_for_backward(x, y1, y2, out, w1, w2, w3, wd, c1[0], c2[0], c3[0], cd[0] if wd is not None else None)
         ctx.geom = (segs, so, stride, prec)
@@ -558,12 +509,12 @@ class _BottleneckRows(torch.autograd.Function):
         if ctx.needs_input_grad[3]:
             gw3 = wg(y2, g, so, P, C4, 1, 1, 0, s3)
         g2 = torch.empty_like(y2)                                                    # d/d(conv2 output), ReLU-masked in the epilogue
-        _conv_launch(g, so, PACKS.get(w3, s3, dgrad=True, f16=amp_pack(prec, w3.shape[0], w3.shape[1])), g2, k=1, stride=1, pad=0, dil=1, res=y2, res_mask=True)
+        _conv_launch(g, so, PACKS.get(w3, s3, dgrad=True, fmt=conv_format(C4, P, 1, 1, 0, 1, so, prec)), g2, k=1, stride=1, pad=0, dil=1, res=y2, res_mask=True)
         if ctx.needs_input_grad[2]:
             gw2 = wg(y1, g2, segs, P, P, 3, stride, 1, s2)
         if stride == 1:
             g1 = torch.empty_like(y1)
-            _conv_launch(g2, so, PACKS.get(w2, s2, dgrad=True, wino=_wino(w2.shape[0], w2.shape[1], 3, 1, 1, 1, so, prec), f16=amp_pack(prec, w2.shape[0], w2.shape[1])), g1, k=3, stride=1, pad=1,
+            _conv_launch(g2, so, PACKS.get(w2, s2, dgrad=True, fmt=conv_format(P, P, 3, 1, 1, 1, so, prec)), g1, k=3, stride=1, pad=1,
                          dil=1, res=y1, res_mask=True)
         elif (g1 := _strided_dgrad(g2, w2, s2, segs, 3, stride, 1, res=y1, res_mask=True, prec=prec)) is not None:
             pass    # strided 3x3: four parity-class launches on the conv kernel, ReLU mask of y1 applied in their epilogues
@@ -582,7 +533,7 @@ class _BottleneckRows(torch.autograd.Function):
                 gid = g                                                             # identity path
             elif stride == 1:
                 gid = torch.empty_like(x)
-                _conv_launch(g, so, PACKS.get(wd, sd, dgrad=True, f16=amp_pack(prec, wd.shape[0], wd.shape[1])), gid, k=1, stride=1, pad=0, dil=1)
+                _conv_launch(g, so, PACKS.get(wd, sd, dgrad=True, fmt=conv_format(wd.shape[0], wd.shape[1], 1, 1, 0, 1, so, prec)), gid, k=1, stride=1, pad=0, dil=1)
             elif (gid := _strided_dgrad(g, wd, sd, segs, 1, stride, 0, prec=prec)) is not None:
                 pass    # 1x1 stride-2 downsample: the (0, 0) parity class is a plain GEMM scattered into a zeroed dX
             else:
@@ -592,7 +543,7 @@ class _BottleneckRows(torch.autograd.Function):
                                                                    wd.detach() * sd.view(-1, 1, 1, 1), None, [stride, stride], [0, 0],
                                                                    [1, 1], False, [0, 0], 1, [True, False, False])[0])
             gx = torch.empty_like(x)                                                # conv1's data gradient + the identity gradient
-            _conv_launch(g1, segs, PACKS.get(w1, s1, dgrad=True, f16=amp_pack(prec, w1.shape[0], w1.shape[1])), gx, k=1, stride=1, pad=0, dil=1, res=gid)
+            _conv_launch(g1, segs, PACKS.get(w1, s1, dgrad=True, fmt=conv_format(P, Cin, 1, 1, 0, 1, segs, prec)), gx, k=1, stride=1, pad=0, dil=1, res=gid)
         return gx, gw1, gw2, gw3, gwd, None, None, None, None, None, None, None
 
 

@@ -1,6 +1,7 @@
 """CPU-side checks: the C-ABI library loads and exports every symbol of include/fcosdet.h, the ctypes structs match
 the C layout, host logic (config, builder, state_dict contract, weight packing, BN folding) and the no-fallback rule."""
 import ctypes
+import json
 import os
 import re
 import subprocess
@@ -289,6 +290,92 @@ def test_reference_checkpoint_layouts_load():
     f.load_state_dict({k[7:]: v for k, v in {"module." + k: v for k, v in f.state_dict().items()}.items()}, strict=True)
 
 
+_TUNE_KEY = re.compile(r"^(?:(f16x3|f16|pair)\|)?B(\d+)\|([\dx+]+)\|(\d+)>(\d+)\|k(\d+)s(\d+)p(\d+)d(\d+)\|res([01])\|xcs(\d+)\|ycs(\d+)"
+                       r"(?:\|x2s(\d+)c(\d+))?(\|rup)?$")
+_W4SK_KEY = re.compile(r"^w4sk\|B(\d+)\|([\dx+]+)\|(\d+)>(\d+)\|d(\d+)\|res([01])$")
+
+
+def test_tune_key_rebuilds_every_committed_key():
+    """ops.tune_key is the one builder of tile-table keys: every key of tuned/gfx950_tiles.json, parsed into its fields, comes back byte for byte."""
+    with open(os.path.join(os.path.dirname(ops.__file__), "tuned", "gfx950_tiles.json")) as f:
+        keys = list(json.load(f))
+    assert len(keys) > 300
+    seen = set()
+
+    def segs(b, hw):
+        return _lib.Segs.make(int(b), [tuple(int(v) for v in l.split("x")) for l in hw.split("+")])
+    for key in keys:
+        m = _W4SK_KEY.match(key)
+        if m:
+            b, hw, ci, co, d, r = m.groups()
+            got = ops.tune_key(segs(b, hw), int(ci), int(co), dil=int(d), res=r == "1", pre="w4sk")
+            seen.add("w4sk")
+        else:
+            m = _TUNE_KEY.match(key)
+            assert m, key
+            pre, b, hw, ci, co, k, s, p, d, r, xcs, ycs, x2s, x2c, rup = m.groups()
+            got = ops.tune_key(segs(b, hw), int(ci), int(co), int(k), int(s), int(p), int(d), res=r == "1", xcs=int(xcs), ycs=int(ycs), pre=pre or "",
+                               x2=(int(x2s), int(x2c)) if x2s else None, rup=bool(rup))
+            seen.add(pre or ("x2" if x2s else ""))
+        assert got == key
+    assert seen == {"", "f16x3", "f16", "pair", "w4sk", "x2"}
+    assert ops.tile_split(ops.tile_code(16, 2)) == (16, 2) and ops.tile_code(16, 1) == 16 and ops.tile_split(16) == (16, 1) == ops.tile_split(16 | 1 << 8)
+
+
+# The chooser's answer for every conv of the shipped HISFCOS-R50 plans (exact fp32, default switches), as the parent commit's plans recorded it (plan.tiles,
+# step_info): "<levels> <Cin>><Cout> k s p d [+flags] <format>[/<Winograd split>]"; flags: r res, g gate, b gate_b, s gn_stats, t force_wino (the head tower).
+_CHOICES_B16_640 = """
+160x160 64>64 k1s1p0d1 DIRECT | 160x160 64>64 k3s1p1d1 WINO4 | 160x160 128>256 k1s1p0d1 DIRECT | 160x160 256>64 k1s1p0d1 DIRECT
+160x160 128>128 k3s2p1d1 DIRECT | 80x80 384>512 k1s1p0d1 DIRECT | 80x80 512>128 k1s1p0d1 DIRECT | 80x80 128>128 k3s1p1d1 WINO4
+80x80 128>512 k1s1p0d1 +r DIRECT | 80x80 512>256 k1s1p0d1 DIRECT | 80x80 256>256 k3s2p1d1 DIRECT | 40x40 768>1024 k1s1p0d1 DIRECT
+40x40 1024>256 k1s1p0d1 DIRECT | 40x40 256>256 k3s1p1d1 WINO4 | 40x40 256>1024 k1s1p0d1 +r DIRECT | 40x40 1024>512 k1s1p0d1 DIRECT
+40x40 512>512 k3s2p1d1 DIRECT | 20x20 1536>2048 k1s1p0d1 DIRECT | 20x20 2048>512 k1s1p0d1 DIRECT | 20x20 512>512 k3s1p1d1 WINO4/2
+20x20 512>2048 k1s1p0d1 +r DIRECT | 20x20 2048>256 k1s1p0d1 DIRECT | 20x20 256>256 k1s1p0d1 DIRECT | 20x20 256>128 k3s1p1d1 WINO/4
+20x20 256>256 k3s1p2d2 WINO/2 | 40x40 1024>256 k1s1p0d1 +r DIRECT | 40x40 256>256 k1s1p0d1 DIRECT | 40x40 256>128 k3s1p1d1 WINO
+40x40 256>256 k3s1p2d2 WINO4 | 80x80 512>256 k1s1p0d1 +r DIRECT | 80x80 256>256 k1s1p0d1 DIRECT | 80x80 256>128 k3s1p1d1 WINO4
+80x80 256>256 k3s1p2d2 WINO4 | 10x10 256>256 k1s1p0d1 DIRECT | 10x10 256>128 k3s1p1d1 WINO/8 | 10x10 256>256 k3s1p2d2 DIRECT
+5x5 256>256 k1s1p0d1 DIRECT | 5x5 256>128 k3s1p1d1 WINO/8 | 5x5 256>256 k3s1p2d2 WINO/8 | 80x80+40x40+20x20+10x10+5x5 256>512 k1s1p0d1 +s DIRECT
+80x80+40x40+20x20+10x10+5x5 512>256 k1s1p0d1 +rgb DIRECT | 80x80+40x40+20x20+10x10+5x5 256>512 k3s1p1d1 +t WINO4
+80x80+40x40+20x20+10x10+5x5 256>80 k3s1p1d1 WINO4 | 80x80+40x40+20x20+10x10+5x5 256>5 k3s1p1d1 +gb NARROW
+"""
+_CHOICES_B1_512 = """
+128x128 64>64 k1s1p0d1 DIRECT | 128x128 64>64 k3s1p1d1 WINO | 128x128 128>256 k1s1p0d1 DIRECT | 128x128 256>64 k1s1p0d1 DIRECT
+128x128 64>256 k1s1p0d1 +r DIRECT | 128x128 256>128 k1s1p0d1 DIRECT | 128x128 128>128 k3s2p1d1 DIRECT | 64x64 384>512 k1s1p0d1 DIRECT
+64x64 512>128 k1s1p0d1 DIRECT | 64x64 128>128 k3s1p1d1 WINO/4 | 64x64 128>512 k1s1p0d1 +r DIRECT | 64x64 512>256 k1s1p0d1 DIRECT
+64x64 256>256 k3s2p1d1 DIRECT | 32x32 768>1024 k1s1p0d1 DIRECT | 32x32 1024>256 k1s1p0d1 DIRECT | 32x32 256>256 k3s1p1d1 WINO/8
+32x32 256>1024 k1s1p0d1 +r DIRECT | 32x32 1024>512 k1s1p0d1 DIRECT | 32x32 512>512 k3s2p1d1 DIRECT | 16x16 1536>2048 k1s1p0d1 DIRECT
+16x16 2048>512 k1s1p0d1 DIRECT | 16x16 512>512 k3s1p1d1 DIRECT | 16x16 512>2048 k1s1p0d1 +r DIRECT | 16x16 2048>256 k1s1p0d1 DIRECT
+16x16 256>256 k1s1p0d1 DIRECT | 16x16 256>128 k3s1p1d1 WINO/8 | 16x16 256>256 k3s1p2d2 WINO/8 | 32x32 1024>256 k1s1p0d1 +r DIRECT
+32x32 256>256 k1s1p0d1 DIRECT | 32x32 256>128 k3s1p1d1 WINO/8 | 32x32 256>256 k3s1p2d2 WINO/8 | 64x64 512>256 k1s1p0d1 +r DIRECT
+64x64 256>256 k1s1p0d1 DIRECT | 64x64 256>128 k3s1p1d1 WINO/4 | 64x64 256>256 k3s1p2d2 WINO/2 | 8x8 256>256 k1s1p0d1 DIRECT
+8x8 256>128 k3s1p1d1 WINO/8 | 8x8 256>256 k3s1p2d2 WINO/8 | 4x4 256>256 k1s1p0d1 DIRECT | 4x4 256>128 k3s1p1d1 WINO/8 | 4x4 256>256 k3s1p2d2 WINO/8
+64x64+32x32+16x16+8x8+4x4 256>512 k1s1p0d1 +s DIRECT | 64x64+32x32+16x16+8x8+4x4 512>256 k1s1p0d1 +rgb DIRECT
+64x64+32x32+16x16+8x8+4x4 256>512 k3s1p1d1 +t WINO | 64x64+32x32+16x16+8x8+4x4 256>80 k3s1p1d1 WINO/4
+64x64+32x32+16x16+8x8+4x4 256>8 k3s1p1d1 WINO/8
+"""
+
+
+@pytest.mark.parametrize("batch,table", [(16, _CHOICES_B16_640), (1, _CHOICES_B1_512)], ids=["16x640", "1x512"])
+def test_conv_chooser_pins_the_shipped_plans(batch, table, monkeypatch):
+    """ops.choose_conv is a pure function of the layer geometry and what the caller offers: it gives every layer of the bench plan (16 x 640^2) and of the
+    latency plan (1 x 512^2) the kernel family, weight format and Winograd split-K factor those plans ran before the chooser existed."""
+    for name, v in (("WINO_MODE", "1"), ("WINO4_MODE", "1"), ("NARROW", True)):
+        monkeypatch.setattr(ops, name, v)
+    n = 0
+    for item in table.replace("\n", " | ").split("|"):
+        if not item.strip():
+            continue
+        tok = item.split()
+        hw, (ci, co), geo, want = tok[0], tok[1].split(">"), re.match(r"k(\d+)s(\d+)p(\d+)d(\d+)$", tok[2]).groups(), tok[-1].split("/")
+        flags = tok[3][1:] if len(tok) == 5 else ""
+        segs = _lib.Segs.make(batch, [tuple(int(v) for v in l.split("x")) for l in hw.split("+")])
+        c = ops.choose_conv(segs, int(ci), int(co), *(int(v) for v in geo), "f32", res="r" in flags, gate="g" in flags, gate_b="b" in flags,
+                            gn_stats="s" in flags, force_wino="t" in flags)
+        assert (c.fmt.name, c.ksplit, c.prec) == (want[0], int(want[1]) if len(want) > 1 else 1, _lib.PREC_F32), item
+        n += 1
+    assert n > 40
+
+
 def test_tile_table_wave_entry_is_demoted_without_fragment_packed_weights(monkeypatch):
     """the committed tile table holds an FD_TILE_WAVE64 entry whose key does not say whether the caller packed its weights in MFMA
     fragment order (fd_conv_params.w_frag).  train_ops._conv_launch never does and plans built with FD_WAVE_TILE=0 do not either: the table
@@ -307,13 +394,13 @@ def test_tile_table_wave_entry_is_demoted_without_fragment_packed_weights(monkey
         p.w_frag = 4096                                                                # a (fake) fragment-packed weight pointer: the entry stands
         assert ops.autotune_conv(Run, k, 16 * 208 * 336, 192, 1) == _lib.WAVE_TILE and p.tile == _lib.WAVE_TILE
     # split-K bits are dropped, and reported as dropped, when the launch has no workspace or carries a row-statistics epilogue
-    monkeypatch.setattr(ops, "_TUNE_CACHE", {"k": 8 | (4 << 8)})
+    monkeypatch.setattr(ops, "_TUNE_CACHE", {"k": ops.tile_code(8, 4)})
     p.w_frag, p.workspace, p.gn_stats = None, None, None
     assert ops.autotune_conv(Run, "k", 1000, 64, 8) == 8 and p.ksplit == 1
     p.workspace, p.gn_stats = 4096, 8192
     assert ops.autotune_conv(Run, "k", 1000, 64, 8) == 8 and p.ksplit == 1
     p.gn_stats = None
-    assert ops.autotune_conv(Run, "k", 1000, 64, 8) == (8 | (4 << 8)) and p.ksplit == 4
+    assert ops.autotune_conv(Run, "k", 1000, 64, 8) == ops.tile_code(8, 4) == 8 | (4 << 8) and p.ksplit == 4
 
 
 def test_fderror_carries_the_numeric_return_code():
@@ -439,7 +526,9 @@ def test_round5_entry_points_validate_on_the_host():
     assert float(pk[0, 1, 1, 5, 2]) == float(we[5, 8 + 4 + 2, 0, 0]) and float(pk[1, 0, 0, 7, 3]) == float(we[39, 3, 0, 0]) and float(pk[1, 1, 1, 8, 0]) == 0.0
     # AMP packing choice
     from pytorch_object_detection_amd import train_ops as T
-    assert T.amp_pack(0, 256, 256) is False and T.amp_pack(_lib.PREC_F16, 256, 64) == 2 and T.amp_pack(_lib.PREC_F16, 32, 256) is True
+    seg, WF = _lib.Segs.make(16, [(64, 64)]), ops.WFormat
+    assert (T.conv_format(256, 256, 1, 1, 0, 1, seg, 0) is WF.DIRECT and T.conv_format(256, 64, 1, 1, 0, 1, seg, _lib.PREC_F16) is WF.F16K64
+            and T.conv_format(32, 256, 1, 1, 0, 1, seg, _lib.PREC_F16) is WF.DIRECT_F16)
     assert ops.f16k64_ok(128, 80) and not ops.f16k64_ok(96, 64)
 
 

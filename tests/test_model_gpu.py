@@ -120,10 +120,10 @@ def test_full_hisfcos_vs_oracle(shape, prec, monkeypatch):
     from pytorch_object_detection_amd import ops as _ops
     monkeypatch.setattr(_ops, "WINO4_MODE", "0")   # (the cost model keeps F(4x4) off maps this small anyway; pinned so the legs below are what they say)
     if prec == "f32-winograd-everywhere":      # small maps normally go to the direct kernel (ops.wino_preferred): force the Winograd
-        monkeypatch.setattr(_ops, "WINO_FORCE", True)           # kernel onto every 3x3 stride-1 layer, tiny levels and all
+        monkeypatch.setattr(_ops, "WINO_MODE", "force")          # kernel onto every 3x3 stride-1 layer, tiny levels and all
         prec = "f32"
     if prec == "f32-winograd4-everywhere":     # F(4x4, 3x3) on every dilation-1 3x3 stride-1 layer (the batch-16 bench plan's choice, forced
-        monkeypatch.setattr(_ops, "WINO_FORCE", True)           # onto the small maps of this test), F(2x2) on the dilated ones
+        monkeypatch.setattr(_ops, "WINO_MODE", "force")         # onto the small maps of this test), F(2x2) on the dilated ones
         monkeypatch.setattr(_ops, "WINO4_MODE", "force")
         prec = "f32"
     torch.manual_seed(0)

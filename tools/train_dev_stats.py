@@ -3,7 +3,7 @@ tests/test_train_gpu.py::test_train_step_matches_oracle_autograd), printed for t
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import torch_ref as R
-from pytorch_object_detection_amd import engine
+from pytorch_object_detection_amd import ops
 from pytorch_object_detection_amd.model.loss import FCOSLoss
 from pytorch_object_detection_amd.model.modules.head import FCOSGenTargets
 from pytorch_object_detection_amd.model.od import HalfInvertedStageFCOS
@@ -13,7 +13,7 @@ ranges = [[-1, 32], [32, 96], [96, 192], [192, 384], [384, 9999999]]
 gt = torch.tensor([[[10., 12., 60., 70.], [30., 30., 120., 110.], [-1, -1, -1, -1]], [[5., 5., 25., 30.], [0., 0., 127., 127.], [64., 20., 100., 90.]]])
 labels = torch.tensor([[3, 7, -1], [1, 20, 12]])
 for wino in [bool(int(c)) for c in os.environ.get("ORDER", "1001")]:
-    engine.WINOGRAD = wino
+    ops.WINO_MODE = "1" if wino else "0"
     torch.manual_seed(0)
     model = HalfInvertedStageFCOS([512, 1024, 2048], 20, 256)
     gen = torch.Generator().manual_seed(1)
