@@ -642,6 +642,36 @@ int32_t fd_eval_ap(const float* det_scores, const int64_t* det_classes, const fl
                    void* workspace, fd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
+/* COCO bbox evaluation: pycocotools COCOeval (iouType 'bbox', useCats) evaluate() + accumulate(), whole computation on the device.
+ * Inputs (device memory): detections scores [N][K] fp32, labels [N][K] int64 (1 .. num_cats; anything else takes no part), boxes
+ * [N][K][4] fp32 xywh, det_counts [N] int32 or NULL (= K); GT boxes [N][G][4] fp64 xywh, annotation area [N][G] fp64, iscrowd [N][G]
+ * uint8, labels [N][G] int64 (1 .. num_cats; -1 = padding); image_order [N] int32 or NULL: position p evaluates image image_order[p]
+ * (a permutation; positions order score ties across images).  HOST arrays: iou_thrs [n_thr] fp64, rec_thrs [n_rec] fp64 (ascending),
+ * area_rng [n_area][2] fp64 (inclusive), max_dets [n_maxdet] int32 (ascending).  Semantics, per (image, label):
+ *   - detections by descending score, stable over rows; only the first max_dets[-1] take part (the cut is per (image, label));
+ *   - IoU fp64 in maskApi bbIou's order: w = fmin(dx+dw, gx+gw) - fmax(dx, gx), h alike, <= 0 gives 0; u = da + ga - i with
+ *     w * h box areas, u = da for a crowd GT;
+ *   - per area range a GT row is ignored if crowd or its annotation area is outside the range; per threshold t (as min(t, 1-1e-10))
+ *     each detection in score order takes the LAST GT row with the maximal IoU >= t among the non-ignored rows not yet taken (crowd
+ *     rows are never taken), else among the ignored ones; matched to an ignored row, or unmatched with w * h outside the range:
+ *     ignored;
+ * then per (label, area, maxDet): each image's first maxDet detections in position order, stably sorted by descending score; fp64
+ * tp / fp cumulative sums over the non-ignored, rc = tp / npig, pr = tp / (fp + tp + 2^-52), the right-to-left envelope,
+ * precision[r] = pr at searchsorted(rc, rec_thrs[r], 'left') (0 past the end), recall = rc[-1] (0 without detections); npig == 0
+ * leaves -1 in both.
+ * Outputs (device): precision [n_thr][n_rec][num_cats][n_area][n_maxdet] fp64, recall [n_thr][num_cats][n_area][n_maxdet] fp64 (the
+ * layout of COCOeval.eval), n_gt [num_cats][n_area] int32 (npig).  Limits: K <= 1024, G <= 512, num_cats <= 128, n_thr <= 10, n_rec
+ * <= 128, n_area <= 4, n_maxdet <= 4, max_dets <= 1024, N * K < 2^31 (FD_E_UNSUPPORTED names the limit).  Deterministic.  det boxes
+ * 16-byte aligned, GT boxes 8-byte; workspace (fd_eval_coco_workspace_bytes: about 56 bytes per detection row) 256-byte aligned.
+ * 22 launches and 2 memsets on `stream`, no host synchronisation. */
+int64_t fd_eval_coco_workspace_bytes(int32_t N, int32_t K, int32_t G, int32_t num_cats);
+int32_t fd_eval_coco(const float* det_scores, const int64_t* det_labels, const float* det_boxes, const int32_t* det_counts, int32_t N,
+                     int32_t K, const double* gt_boxes, const double* gt_area, const uint8_t* gt_crowd, const int64_t* gt_labels, int32_t G,
+                     const int32_t* image_order, int32_t num_cats, const double* iou_thrs, int32_t n_thr, const double* rec_thrs,
+                     int32_t n_rec, const double* area_rng, int32_t n_area, const int32_t* max_dets, int32_t n_maxdet, double* precision,
+                     double* recall, int32_t* n_gt, void* workspace, fd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- */
 /* LTRB IoU / GIoU regression loss (reference model/loss.py:116-177), fused masked forward + backward.
  * pred/target [B][L][4], mask [B][L] (uint8, positives).  mode 0 = 'iou', 1 = 'giou'.
  * loss_per_image [B] = sum over positives (NOT yet divided by num_pos), num_pos [B] int32.

@@ -191,6 +191,9 @@ _SIGS = {
     "fd_bce_logits_loss_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "fd_eval_ap_workspace_bytes": (_L, [_I, _I, _I, _I, _I]),
     "fd_eval_ap": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, C.POINTER(_F), _I, _I, _P, _P, _P, _P, _P, _P]),
+    "fd_eval_coco_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "fd_eval_coco": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, C.POINTER(_D), _I, C.POINTER(_D), _I, C.POINTER(_D), _I,
+                          C.POINTER(_I), _I, _P, _P, _P, _P, _P]),
     "fd_fcos_gen_targets": (_I, [_P, _P, _I, C.POINTER(Segs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _F, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)

@@ -14,6 +14,7 @@ import re
 import sys
 from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1490,3 +1491,54 @@ def eval_ap(scores: torch.Tensor, classes: torch.Tensor, boxes: torch.Tensor, de
                                 gt_counts.data_ptr() if gt_counts is not None else None, G, num_cls, thr, T, int(flags), ap.data_ptr(),
                                 n_gt.data_ptr(), n_pred.data_ptr(), n_tp.data_ptr(), ws.data_ptr(), _stream()), "fd_eval_ap")
     return ap, n_gt, n_pred, n_tp
+
+
+COCO_IOU_THRS = tuple(float(t) for t in np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True))    # COCOeval Params
+COCO_REC_THRS = tuple(float(r) for r in np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True))
+COCO_AREA_RNG = ((0 ** 2, 1e5 ** 2), (0 ** 2, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e5 ** 2))
+COCO_MAX_DETS = (1, 10, 100)
+
+
+def eval_coco(scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor, det_counts: Optional[torch.Tensor], gt_boxes: torch.Tensor,
+              gt_area: torch.Tensor, gt_crowd: torch.Tensor, gt_labels: torch.Tensor, num_cats: int, image_order: Optional[torch.Tensor] = None,
+              iou_thrs: Sequence[float] = COCO_IOU_THRS, rec_thrs: Sequence[float] = COCO_REC_THRS,
+              area_rng: Sequence[Sequence[float]] = COCO_AREA_RNG, max_dets: Sequence[int] = COCO_MAX_DETS):
+    """COCOeval bbox evaluate + accumulate (fd_eval_coco, include/fcosdet.h) on the current stream.
+    scores [N,K] f32, labels [N,K] int64 (1 .. num_cats), boxes [N,K,4] f32 xywh, det_counts [N] int32 or None; gt_boxes [N,G,4] f64 xywh,
+    gt_area [N,G] f64, gt_crowd [N,G] uint8, gt_labels [N,G] int64 (-1 = padding); image_order [N] int32 or None.
+    -> (precision [T,R,num_cats,A,M] f64, recall [T,num_cats,A,M] f64, n_gt [num_cats,A] int32), device tensors."""
+    _need_gpu(scores, labels, boxes, det_counts, gt_boxes, gt_area, gt_crowd, gt_labels, image_order)
+    N, K = scores.shape
+    G = gt_labels.shape[1]
+    if (tuple(labels.shape) != (N, K) or tuple(boxes.shape) != (N, K, 4) or tuple(gt_boxes.shape) != (N, G, 4)
+            or tuple(gt_area.shape) != (N, G) or tuple(gt_crowd.shape) != (N, G) or gt_labels.shape[0] != N):
+        raise FdError("eval_coco: shapes of the detection / GT tensors do not agree")
+    if (scores.dtype != torch.float32 or labels.dtype != torch.int64 or boxes.dtype != torch.float32 or gt_boxes.dtype != torch.float64
+            or gt_area.dtype != torch.float64 or gt_crowd.dtype != torch.uint8 or gt_labels.dtype != torch.int64):
+        raise FdError("eval_coco: scores / boxes f32, GT boxes / area f64, iscrowd uint8, labels int64")
+    for t in (scores, labels, boxes, det_counts, gt_boxes, gt_area, gt_crowd, gt_labels, image_order):
+        if t is not None and not t.is_contiguous():
+            raise FdError("eval_coco: inputs must be contiguous")
+    for t in (det_counts, image_order):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (N,)):
+            raise FdError("eval_coco: det_counts / image_order must be int32 [N]")
+    T, R, A, M = len(iou_thrs), len(rec_thrs), len(area_rng), len(max_dets)
+    dev = scores.device
+    L = _lib.lib()
+    need = L.fd_eval_coco_workspace_bytes(N, K, G, int(num_cats))
+    if need < 0:
+        check(L.fd_eval_coco(None, None, None, None, N, K, None, None, None, None, G, None, int(num_cats), None, T, None, R, None, A, None, M,
+                             None, None, None, None, None), "fd_eval_coco")
+    ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)      # per call, as eval_ap's
+    precision = torch.empty((T, R, int(num_cats), A, M), dtype=torch.float64, device=dev)
+    recall = torch.empty((T, int(num_cats), A, M), dtype=torch.float64, device=dev)
+    n_gt = torch.empty((int(num_cats), A), dtype=torch.int32, device=dev)
+    thr = (C.c_double * T)(*[float(t) for t in iou_thrs])
+    rec = (C.c_double * R)(*[float(r) for r in rec_thrs])
+    ar = (C.c_double * (2 * A))(*[float(v) for rng in area_rng for v in rng])
+    md = (C.c_int32 * M)(*[int(m) for m in max_dets])
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    check(L.fd_eval_coco(ptr(scores), ptr(labels), ptr(boxes), ptr(det_counts), N, K, ptr(gt_boxes), ptr(gt_area), ptr(gt_crowd), ptr(gt_labels),
+                         G, ptr(image_order), int(num_cats), thr, T, rec, R, ar, A, md, M, precision.data_ptr(), recall.data_ptr(),
+                         n_gt.data_ptr(), ws.data_ptr(), _stream()), "fd_eval_coco")
+    return precision, recall, n_gt
