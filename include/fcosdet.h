@@ -335,8 +335,8 @@ int32_t fd_stem7x7_nchw3(const float* x, const float* w, const float* scale, con
 
 /* [N][3][H][W] fp32 (NCHW, the reference's input layout, dataset/voc.py:141-173) -> [N][H][W][4] (c=3 zero) */
 int32_t fd_nchw3_to_nhwc4(const float* x, float* y, int32_t N, int32_t H, int32_t W, fd_stream_t stream);
-/* Input pipeline tail on the device: uint8 [N][H][W][3] images, already resized and zero padded on
- * the host (cv2.resize is third-party arithmetic and stays there, dataset/voc.py:110-139) -> normalised fp32
+/* Input pipeline tail on the device: uint8 [N][H][W][3] images, already resized and zero padded
+ * (dataset/voc.py:110-139; on the host, or by fd_resize_u8 below) -> normalised fp32
  * [N][H][W][4] = ((u8/255) - mean) / std per channel (transforms.ToTensor + Normalize, voc.py:57-58,104,155),
  * channel 3 = 0: the stem conv's input, no NCHW detour.  mean3 / std3 are HOST pointers to 3 floats. */
 int32_t fd_preprocess_u8_nhwc4(const uint8_t* x, float* y, int32_t N, int32_t H, int32_t W, const float* mean3,
@@ -426,9 +426,45 @@ int32_t fd_stem_conv_nhwc4(const float* x4, const float* w, const float* scale, 
  * images_dev: DEVICE array of N device pointers to [h_n][w_n][3] uint8; hw_dev: DEVICE int32 [N][2] = (h_n, w_n);
  * H, W >= every (h_n, w_n): the batch canvas (the host picks max over n of h_n + 32 - h_n % 32, as the reference does).
  * Pixels outside an image are uint8 zeros BEFORE normalisation, i.e. (0 - mean) / std, exactly what the reference's
- * zero-pad-then-Normalize produces.  cv2.resize stays on the host.  mean3 / std3 are HOST pointers to 3 floats. */
+ * zero-pad-then-Normalize produces.  The images are ALREADY resized (on the host, or by fd_resize_u8); raw images go
+ * through fd_resize_collate_u8_nhwc4 below.  mean3 / std3 are HOST pointers to 3 floats. */
 int32_t fd_collate_u8_nhwc4(const uint8_t* const* images_dev, const int32_t* hw_dev, float* y, int32_t N, int32_t H,
                             int32_t W, const float* mean3, const float* std3, fd_stream_t stream);
+
+/* The resize of the input pipeline on the device: the cv2.resize call of preprocess_img_boxes
+ * (dataset/voc.py:110-139, Test_coco.py:76-105).  Bilinear, half-pixel geometry (that of cv2.INTER_LINEAR and of torch's
+ * align_corners=False), no antialiasing, 11-bit integer blending; per axis (source length S, destination length D, index d),
+ * in fp32 without FMA contraction:
+ *     x = (d + 0.5f) * ((float)S / (float)D) - 0.5f;  i0 = floor(x);  f = x - i0;
+ *     i0 < 0: i0 = 0, f = 0;   i0 >= S - 1: i0 = S - 1, f = 0;   i1 = min(i0 + 1, S - 1);
+ *     c1 = (int)floor(f * 2048.0f + 0.5f);  c0 = 2048 - c1;
+ *     level = (p00*cx0*cy0 + p01*cx1*cy0 + p10*cx0*cy1 + p11*cx1*cy1 + (1 << 21)) >> 22          (uint32, per channel)
+ * D == S is the identity.  The definition is this library's own and is unpinned against cv2 (third-party, absent here:
+ * bit parity with cv2.resize is not claimed); it stays within 0.875 levels of exact bilinear interpolation
+ * and tests/resize_ref.py restates it in numpy bit for bit.  The size rule (scale, int(scale * w), pad to 32) is host
+ * arithmetic in doubles and stays with the caller (utill.utills.resize_rule).
+ *
+ * fd_resize_u8: one uint8 [h][w][3] image -> uint8 [nh][nw][3]; every side in 1 .. 65536. */
+int32_t fd_resize_u8(const uint8_t* x, int32_t h, int32_t w, uint8_t* y, int32_t nh, int32_t nw, fd_stream_t stream);
+/* Resize + pad-to-canvas + ToTensor + Normalize of a whole mixed-size batch in ONE launch: N RAW uint8 images ->
+ * normalised fp32 [N][H][W][4], the stem's input layout.  images_dev: DEVICE array of N device pointers to [h_n][w_n][3]
+ * uint8, as for fd_collate_u8_nhwc4; src_hw_dev / dst_hw_dev: DEVICE int32 [N][2] = (h_n, w_n) / (nh_n, nw_n), the
+ * resized size of image n.  The output equals fd_collate_u8_nhwc4 on the images fd_resize_u8 produces, bit for bit:
+ * pixels outside nh_n x nw_n are uint8 zero BEFORE normalisation, i.e. (0 - mean) / std, channel 3 = 0.
+ * Checked here (FD_E_INVAL): pointers, alignment of y, N in 1 .. 65535, canvas sides in 1 .. 65536, non-zero std.  The
+ * size tables are device memory and are not read by the host: the caller guarantees h_n, w_n >= 1 and nh_n <= H, nw_n <= W
+ * (the Python wrapper checks); whatever they hold, the kernel reads inside [h_n][w_n][3] and writes inside the canvas only
+ * (an entry with a side < 1 yields an all-padding image).  mean3 / std3 are HOST pointers to 3 floats. */
+int32_t fd_resize_collate_u8_nhwc4(const uint8_t* const* images_dev, const int32_t* src_hw_dev, const int32_t* dst_hw_dev,
+                                   float* y, int32_t N, int32_t H, int32_t W, const float* mean3, const float* std3,
+                                   fd_stream_t stream);
+/* Boxes between resized and source coordinates, in place on padded detections [B][K][4] (16-byte aligned): image b uses
+ * scales_dev[b] (DEVICE fp32 [B]).  invert = 1: boxes / scale, IEEE fp32 division as fd_boxes_rescale_xywh and as
+ * `boxes /= scale` of Test_coco.py:147; invert = 0: boxes * scale, the ground-truth side (dataset/voc.py:137-138).
+ * xywh = 1: then xyxy -> xywh (Test_coco.py:150-151).  counts: DEVICE int32 [B] or NULL (all K rows); rows at or
+ * beyond counts[b] are left untouched. */
+int32_t fd_boxes_scale_batch(float* boxes, const int32_t* counts, const float* scales_dev, int32_t B, int32_t K,
+                             int32_t invert, int32_t xywh, fd_stream_t stream);
 
 /* GroupNorm(G, C) + activation (nn.GroupNorm in HISFCOSHead / HeadFCOS, HISFcos.py:190-204, Fcos.py:102-109).
  * Two launches: partial moments (fp64 accumulation, fixed order) then normalise+affine+act.

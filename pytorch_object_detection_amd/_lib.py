@@ -147,6 +147,9 @@ _SIGS = {
     "fd_dwconv_dilated_nhwc": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.POINTER(Segs), _P]),
     "fd_stem_conv_nhwc4": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fd_collate_u8_nhwc4": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),
+    "fd_resize_u8": (_I, [_P, _I, _I, _P, _I, _I, _P]),
+    "fd_resize_collate_u8_nhwc4": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),
+    "fd_boxes_scale_batch": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "fd_dwconv3x3_wgrad_workspace_bytes": (_L, [C.POINTER(Segs), _I]),
     "fd_dwconv3x3_bwd_weight_nhwc": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _I, C.POINTER(Segs), _P, _P]),
     "fd_groupnorm_workspace_bytes": (_L, [C.POINTER(Segs), _I]),

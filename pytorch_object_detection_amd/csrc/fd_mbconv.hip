@@ -208,8 +208,8 @@ extern "C" int32_t fd_stem_conv_nhwc4(const float* x4, const float* w, const flo
 // ------------------------------------------------------------------------------ mixed-aspect batch assembly
 // dataset/voc.py:128-132,141-156: every resized image is zero-padded (uint8 zeros) to the next multiple of 32, then in
 // collate_fn to the batch's largest (H, W) with 0. BEFORE Normalize -- so every padding pixel ends up as (0 - mean) / std, not 0.
-// One launch per batch: `src` is a device array of N pointers to the RESIZED uint8 [h_n][w_n][3] images (cv2.resize is
-// third-party arithmetic and stays on the host), hw = device int32 [N][2]; the output is the stem's [N][H][W][4] layout:
+// One launch per batch: `src` is a device array of N pointers to the RESIZED uint8 [h_n][w_n][3] images (resized on the
+// host or by fd_resize_u8; fd_resize.hip fuses the resize into this step for raw images), hw = device int32 [N][2]; the output is the stem's [N][H][W][4] layout:
 // ((u8 / 255) - mean) / std with u8 = 0 outside the image, channel 3 = 0.  Same fp32 op order as ToTensor + Normalize.
 __global__ __launch_bounds__(256) void collate_u8_kernel(const unsigned char* const* __restrict__ src, const int* __restrict__ hw,
                                                           float4* __restrict__ y, int H, int W, float m0, float m1, float m2,

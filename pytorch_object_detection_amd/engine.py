@@ -114,11 +114,11 @@ class Plan:
         For the launch-bound shapes (the reference's own: batch 1, 512 x 512, test.py:202-223 -- ~190 launches of ~10 us each).  The
         steps read plan-owned buffers at fixed addresses; the caller's image is staged into `static_in` (same shape / dtype as the
         tensor in image_ref at capture time) by run(), so any input tensor works afterwards.  Inputs whose ADDRESSES the steps bake in
-        per call (the mixed-aspect `collate` list) cannot be captured."""
+        per call (the mixed-aspect `collate` / `resize` lists) cannot be captured."""
         if self.graph is not None:
             return
-        if getattr(self, "input_mode", None) == "collate":
-            raise FdError("capture_graph: a 'collate' plan rebuilds its pointer table on every run and cannot be captured")
+        if getattr(self, "input_mode", None) in ("collate", "resize"):
+            raise FdError(f"capture_graph: a '{self.input_mode}' plan rebuilds its pointer table on every run and cannot be captured")
         src = self.image_ref[0]
         self.static_in = torch.empty_like(src).copy_(src)
         self.image_ref[0] = self.static_in
@@ -324,7 +324,9 @@ def add_input(plan: Plan, x4: Rows, batch: int, H: int, W: int, image_ref: List)
     """First step of a detector plan: fill the stem's [N][H][W][4] input from whatever the caller hands over
     (plan.input_mode): None = fp32 NCHW (the reference's tensor, dataset/voc.py:141-173); 'u8' = one uint8 [N,H,W,3] batch,
     normalised on the device; 'collate' = a list of resized uint8 [h_n, w_n, 3] images of different sizes, padded to the
-    batch canvas and normalised in one launch (voc.py:128-132,141-156).  (mean, std) = plan.input_u8."""
+    batch canvas and normalised in one launch (voc.py:128-132,141-156); 'resize' = a list of RAW uint8 [h_n, w_n, 3] images, resized to
+    plan.resized_hw[n] (set per call by PlannedModule.forward_raw from the reference's size rule), padded and normalised in one launch
+    (voc.py:110-156).  (mean, std) = plan.input_u8."""
     mode = getattr(plan, "input_mode", None) or ("u8" if getattr(plan, "input_u8", None) else None)
     if mode == "u8":
         mean, std = plan.input_u8
@@ -336,6 +338,15 @@ def add_input(plan: Plan, x4: Rows, batch: int, H: int, W: int, image_ref: List)
         def run():
             _, hold[0] = ops.collate_u8(image_ref[0], H, W, mean, std, out=x4.buf)   # `hold`: pointer table alive until the next run
         plan.add("input.collate_u8", run)
+    elif mode == "resize":
+        mean, std = plan.input_u8
+        hold = [None]
+        plan.resized_hw = None                                                       # [(nh_n, nw_n)] of the last call
+        plan.scales = torch.zeros(batch, dtype=torch.float32, device=plan.device)    # the size rule's scale of each image of the last call
+
+        def run():
+            _, hold[0] = ops.resize_collate_u8(image_ref[0], plan.resized_hw, H, W, mean, std, out=x4.buf)
+        plan.add("input.resize_collate_u8", run)
     else:
         plan.add("input.nchw3_to_nhwc4", lambda: ops.nchw3_to_nhwc4(image_ref[0], x4.buf))
 

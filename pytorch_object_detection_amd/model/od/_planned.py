@@ -164,6 +164,54 @@ class PlannedModule(nn.Module):
         plan.run(events)
         return self.outputs_of(plan)
 
+    def forward_raw(self, images, resize_size=(800, 1333), events=None):
+        """The whole input pipeline on the device: a list of RAW uint8 [h_n, w_n, 3] CUDA images of any size -> the reference's
+        preprocess_img_boxes (dataset/voc.py:110-139: short side to resize_size[0], long side capped at resize_size[1], bilinear
+        resize, pad to the next multiple of 32), collate to the batch maximum and ToTensor + Normalize in ONE launch
+        (ops.resize_collate_u8; the resize's arithmetic is DESIGN §4.2d, unpinned against cv2) -> the model.  Returns what
+        model(batch_imgs) returns.  The size rule runs on the host in Python doubles (utill.utills.resize_rule); of the last call,
+        `plan.scales` (device fp32 [B]), `plan.resized_hw` and `plan.canvas_hw` are readable from `raw_plan_for(images, resize_size)`."""
+        plan = self.raw_plan_for(images, resize_size)
+        plan.run(events)
+        return self.outputs_of(plan)
+
+    def raw_plan_for(self, images, resize_size=(800, 1333)):
+        """The cached 'resize' plan for a list of raw images, keyed by (B, H, W) of the batch canvas, with this batch's images, resized
+        sizes and scales installed (the pointer / size tables are rebuilt on every run: such a plan refuses capture_graph)."""
+        from ...utill.utills import pad32, resize_rule
+        self._check_eval()
+        images = list(images) if isinstance(images, (list, tuple)) else images
+        if not isinstance(images, list) or not images or any(
+                (not isinstance(t, torch.Tensor)) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3
+                or t.shape[0] < 1 or t.shape[1] < 1 for t in images):
+            raise FdError("forward_raw expects a non-empty list of CUDA uint8 [h, w, 3] images")
+        rules = [resize_rule(int(t.shape[0]), int(t.shape[1]), resize_size) for t in images]
+        if any(nh < 1 or nw < 1 for _, nh, nw in rules):
+            raise FdError("forward_raw: the size rule shrinks an image to nothing (an extreme aspect ratio)")
+        H, W = max(pad32(nh) for _, nh, _ in rules), max(pad32(nw) for _, _, nw in rules)
+        B, dev = len(images), images[0].device
+        plan = self._get_plan(("model_resize", B, H, W, str(dev)), lambda: self.build_plan(B, H, W, dev, "resize"))
+        plan.image_ref[0] = [t.contiguous() for t in images]
+        plan.resized_hw = [(nh, nw) for _, nh, nw in rules]
+        plan.scales.copy_(torch.tensor([s for s, _, _ in rules], dtype=torch.float32))    # each double rounded once to fp32
+        return plan
+
+    def detect_raw(self, images, head, resize_size=(800, 1333), clip=True, source_coords=True, xywh=False):
+        """Raw images in, detections in the raw images' coordinates out (Test_coco.py:138-151 without its host steps): forward_raw ->
+        FCOSHead.detect_padded -> ClipBoxes against the batch canvas (the tensor the reference clips against) -> boxes / scale of each
+        image (ops.boxes_scale_batch_), optionally -> xywh.  Returns (scores [B,K], classes [B,K] int64, boxes [B,K,4], counts [B] int32,
+        scales [B] fp32 on the device); rows at or beyond counts[b] are zero.  `scales` is plan-owned (overwritten by the next call)."""
+        from ... import ops
+        plan = self.raw_plan_for(images, resize_size)
+        plan.run()
+        scores, classes, boxes, counts = head.detect_padded(self.outputs_of(plan))
+        boxes = boxes.contiguous()
+        if clip:
+            ops.clip_boxes_(boxes, plan.canvas_hw[0], plan.canvas_hw[1])
+        if source_coords or xywh:      # (canvas coordinates as xywh: the same launch with unit scales)
+            ops.boxes_scale_batch_(boxes, plan.scales if source_coords else torch.ones_like(plan.scales), counts, invert=True, xywh=xywh)
+        return scores, classes, boxes, counts, plan.scales
+
     def _check_eval(self) -> None:
         if self.training:
             raise FdError("the HIP plan implements the frozen-BN inference forward; call model.eval() first")

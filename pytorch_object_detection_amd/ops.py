@@ -1055,6 +1055,73 @@ def collate_u8(images: Sequence[torch.Tensor], H: int, W: int, mean, std, out: O
     return out, (ptrs, hw, tuple(images))
 
 
+def _check_raw_image(t, what: str) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise FdError(f"{what}: expected a CUDA tensor (the HIP path runs on the GPU only; there is no CPU fallback)")
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or not t.is_contiguous() or t.shape[0] < 1 or t.shape[1] < 1:
+        raise FdError(f"{what}: images must be contiguous CUDA uint8 [h, w, 3] with h, w >= 1")
+
+
+def resize_u8(img: torch.Tensor, nh: int, nw: int) -> torch.Tensor:
+    """Raw uint8 [h, w, 3] CUDA image -> uint8 [nh, nw, 3]: the cv2.resize call of preprocess_img_boxes (dataset/voc.py:126,
+    Test_coco.py:92) on the device.  Bilinear, half-pixel geometry, integer blending; unpinned against cv2."""
+    _check_raw_image(img, "resize_u8")
+    nh, nw = int(nh), int(nw)
+    if nh < 1 or nw < 1:
+        raise FdError(f"resize_u8: destination size must be >= 1 x 1 (got {nh} x {nw})")
+    out = torch.empty(nh, nw, 3, dtype=torch.uint8, device=img.device)
+    check(_lib.lib().fd_resize_u8(img.data_ptr(), img.shape[0], img.shape[1], out.data_ptr(), nh, nw, _stream()), "fd_resize_u8")
+    return out
+
+
+def resize_collate_u8(images: Sequence[torch.Tensor], dst_hw, H: int, W: int, mean, std, out: Optional[torch.Tensor] = None):
+    """RAW uint8 [h_n, w_n, 3] CUDA images -> resized to dst_hw[n] = (nh_n, nw_n), padded to the H x W canvas and normalised:
+    one [N*H*W, 4] fp32 batch in ONE launch (preprocess_img_boxes + collate_fn + Normalize, dataset/voc.py:110-156, on the
+    device).  Bit-identical to collate_u8 on the images resize_u8 produces.  Returns (batch rows tensor, keep-alive tuple)."""
+    images = list(images)
+    N = len(images)
+    if N < 1:
+        raise FdError("resize_collate_u8: empty image list")
+    for t in images:
+        _check_raw_image(t, "resize_collate_u8")
+    dst = [(int(a), int(b)) for a, b in dst_hw]
+    if len(dst) != N or any(a < 1 or b < 1 or a > H or b > W for a, b in dst):
+        raise FdError("resize_collate_u8: dst_hw must hold one (nh, nw) per image with 1 <= nh <= H and 1 <= nw <= W")
+    dev = images[0].device
+    if out is None:
+        out = torch.empty(N * H * W, 4, dtype=torch.float32, device=dev)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != N * H * W * 4:
+        raise FdError("resize_collate_u8: out must be a contiguous CUDA fp32 tensor of N * H * W * 4 elements")
+    ptrs = torch.tensor([t.data_ptr() for t in images], dtype=torch.int64).to(dev)
+    # one table, one copy: rows 0..N-1 = source sizes, rows N..2N-1 = resized sizes
+    hw = torch.tensor([[t.shape[0], t.shape[1]] for t in images] + [list(d) for d in dst], dtype=torch.int32).to(dev)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s_ = (C.c_float * 3)(*[float(v) for v in std])
+    check(_lib.lib().fd_resize_collate_u8_nhwc4(ptrs.data_ptr(), hw.data_ptr(), hw.data_ptr() + 8 * N, out.data_ptr(), N, H, W, m, s_, _stream()),
+          "fd_resize_collate_u8_nhwc4")
+    return out, (ptrs, hw, tuple(images))
+
+
+def boxes_scale_batch_(boxes: torch.Tensor, scales: torch.Tensor, counts: Optional[torch.Tensor] = None, invert: bool = True,
+                       xywh: bool = False) -> torch.Tensor:
+    """In place on padded [B, K, 4] boxes, image b by scales[b] (CUDA fp32 [B]): invert -> boxes / scale (detections back to the
+    source image, Test_coco.py:147), else boxes * scale (ground truth onto the resized image, dataset/voc.py:137-138); xywh ->
+    then (x1, y1, x2, y2) -> (x, y, w, h) (Test_coco.py:150-151).  Rows at or beyond counts[b] (CUDA int32 [B]) stay untouched."""
+    for t, what in ((boxes, "boxes"), (scales, "scales"), (counts, "counts")):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda):
+            raise FdError(f"boxes_scale_batch_: {what} must be a CUDA tensor (there is no CPU fallback)")
+    if boxes.dtype != torch.float32 or boxes.dim() != 3 or boxes.shape[2] != 4 or not boxes.is_contiguous():
+        raise FdError("boxes_scale_batch_: boxes must be contiguous fp32 [B, K, 4]")
+    B, K = int(boxes.shape[0]), int(boxes.shape[1])
+    if scales.dtype != torch.float32 or scales.dim() != 1 or scales.shape[0] != B or not scales.is_contiguous():
+        raise FdError(f"boxes_scale_batch_: scales must be contiguous fp32 [{B}] (one per image)")
+    if counts is not None and (counts.dtype != torch.int32 or counts.dim() != 1 or counts.shape[0] != B or not counts.is_contiguous()):
+        raise FdError(f"boxes_scale_batch_: counts must be contiguous int32 [{B}]")
+    check(_lib.lib().fd_boxes_scale_batch(boxes.data_ptr(), counts.data_ptr() if counts is not None else None, scales.data_ptr(), B, K,
+                                          1 if invert else 0, 1 if xywh else 0, _stream()), "fd_boxes_scale_batch")
+    return boxes
+
+
 def dwconv3x3_wgrad(x: Rows, dy: Rows, segs: Segs, scale: Optional[torch.Tensor] = None, torch_layout: bool = False) -> torch.Tensor:
     """Weight gradient of the depthwise 3x3 conv (stride 1, pad 1) given dy: [9][C], or [C][1][3][3] with torch_layout."""
     dev = x.buf.device

@@ -19,6 +19,24 @@ def coords_origin_fcos(feature: torch.Tensor, strides: int) -> torch.Tensor:
     return torch.stack([xs.reshape(-1), ys.reshape(-1)], -1) + strides // 2
 
 
+def resize_rule(h: int, w: int, resize_size=(800, 1333)):
+    """(scale, nh, nw) of the reference's preprocess_img_boxes (dataset/voc.py:117-125, Test_coco.py:83-91) for a raw
+    h x w image: the short side is scaled to min_side, the long side capped at max_side, the sizes truncated.  Python
+    doubles in the reference's order of operations -- the truncation depends on it (289 x 333 -> 799 x 921, not 800)."""
+    min_side, max_side = resize_size
+    smallest_side = min(w, h)
+    largest_side = max(w, h)
+    scale = min_side / smallest_side
+    if largest_side * scale > max_side:
+        scale = max_side / largest_side
+    return scale, int(scale * h), int(scale * w)
+
+
+def pad32(n: int) -> int:
+    """Padded side of dataset/voc.py:128-131: n + 32 - n % 32 (a full extra 32 when n is already a multiple of 32)."""
+    return n + 32 - n % 32
+
+
 def load_config(cfg: str = os.path.join(_PKG, 'config', 'main.yaml')) -> dict:
     """main.yaml names the dataset + model; the dataset yaml holds one block per model.  Result keys as in the
     reference: dataset_setting, <MODEL> blocks, model{dataset,name,amp,ddp,persistent,prefetch}, savename.
