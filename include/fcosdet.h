@@ -466,6 +466,78 @@ int32_t fd_resize_collate_u8_nhwc4(const uint8_t* const* images_dev, const int32
 int32_t fd_boxes_scale_batch(float* boxes, const int32_t* counts, const float* scales_dev, int32_t B, int32_t K,
                              int32_t invert, int32_t xywh, fd_stream_t stream);
 
+/* The training-side augmentations on the device: the reference's flip (dataset/voc.py:12-20), Transforms
+ * (data/augment.py: colorJitter, random_rotation, random_crop_resize), preprocess_img_boxes and collate_fn of a batch of
+ * RAW uint8 [h][w][3] images.  The random decisions and the box arithmetic are host work (data/augment.py of the Python
+ * package); the device gets one PARAMETER RECORD of FD_AUG_WORDS 32-bit words per image, in device memory:
+ *
+ *   FD_AUG_H, FD_AUG_W          raw image size
+ *   FD_AUG_FLIP                 1: the image is mirrored left-right first (column x -> w - 1 - x)
+ *   FD_AUG_ROT_ON               1: rotated by PIL's img.rotate (NEAREST, no expand, centre (w/2, h/2)) with the six 16.16
+ *   FD_AUG_ROT0 .. +5           fixed-point integers (A0, A1, X0, A3, A4, Y0): destination (x, y) takes source pixel
+ *                               ((X0 + A0*x + A1*y) >> 16, (Y0 + A3*x + A4*y) >> 16), black when that is outside.  The host
+ *                               forms them in doubles as PIL does: angle = -radians(d mod 360), cos / sin rounded to 15
+ *                               digits, a2 = cx - a0*cx - a1*cy (same for a5), FIX(v) = (int)(v * 65536 + (v < 0 ? -0.5 : 0.5)),
+ *                               X0 = FIX(a2 + a0/2 + a1/2).  Sides <= 16384 and |d| < 90 keep every coordinate below 2^31 in
+ *                               magnitude; the device forms the sums in 64-bit integers.
+ *   FD_AUG_CROP_X, _Y, _W, _H   crop rectangle inside the (rotated) image; the whole image when there is no crop
+ *   FD_AUG_NH, FD_AUG_NW        size the crop is resized to (bilinear, the arithmetic of fd_resize_u8)
+ *   FD_AUG_NOPS                 length 0 .. FD_AUG_MAX_OPS of the colour chain, applied to the raw pixel in this order:
+ *   FD_AUG_OP0 .. +3            FD_AUG_OP_* of each operation
+ *   FD_AUG_ARG0 .. +3           its argument: the bits of the fp32 factor f, or for FD_AUG_OP_HUE the uint8 added to H
+ *   FD_AUG_MEAN_L               the contrast operation's grey level int(mean(L) + 0.5); fd_jitter_l_sums fills it in
+ *   remaining words             reserved, zero
+ *
+ * Colour arithmetic (each operation rounds to uint8, as PIL does between operations; fp32, no FMA contraction):
+ *   brightness / contrast / saturation: level = clip((int)(deg + f * (pix - deg)), 0, 255) with deg = 0 / FD_AUG_MEAN_L /
+ *   L of the pixel, L = (19595 R + 38470 G + 7471 B + 32768) >> 16 -- PIL's ImageEnhance.Brightness / Contrast / Color;
+ *   hue: RGB -> HSV, H = (H + shift) & 255, HSV -> RGB with PIL's conversions.  All four are exact against PIL
+ *   (tests/augment_ref.py restates them; checked over the whole 2^24 colour cube).
+ *
+ * fd_augment_resize_collate_u8: ONE launch per batch.  images_dev: DEVICE array of N device pointers; recs_dev: DEVICE
+ * int32 [N][FD_AUG_WORDS]; y: PLANAR fp32 [N][3][H][W], what collate_fn returns and a model takes in train() mode.  Canvas
+ * pixel (dy, dx) inside NH x NW: the four taps and 11-bit weights of the CROP_H x CROP_W -> NH x NW resize; each tap
+ * + (CROP_Y, CROP_X) -> rotation map -> mirrored column -> raw bytes -> colour chain; blended, then Normalize with the
+ * expression of fd_collate_u8_nhwc4.  Outside NH x NW: level 0 before Normalize.  The host side cannot read the records:
+ * the caller validates them (the Python wrapper does); whatever they hold, a tap is loaded only after its final (row,
+ * column) has been checked against [h][w] and only canvas pixels are written.  mean3 / std3 are HOST pointers.
+ *
+ * fd_jitter_l_sums: for every image whose chain holds FD_AUG_OP_CONTRAST, sums_dev[n] (DEVICE uint64 [N], cleared here) =
+ * sum over the raw image of L after the operations that PRECEDE contrast, and FD_AUG_MEAN_L of its record =
+ * (int)((double)sum / (h*w) + 0.5), PIL's ImageStat mean.  Integer sums, one 64-bit vector atomic per workgroup: exact
+ * and order-independent.  max_pixels: the largest h*w of the batch (sizes the grid).  Run it before the fused launch when
+ * any chain holds contrast.  Allocates nothing.
+ *
+ * fd_color_jitter_u8: one image through the chain of ONE record (device) -> uint8 [h][w][3]; x == y is allowed.
+ * fd_rotate_u8: one image -> uint8 [h][w][3] by the six integers (HOST pointer); sides in 1 .. 16384, x != y. */
+#define FD_AUG_WORDS 32
+#define FD_AUG_H 0
+#define FD_AUG_W 1
+#define FD_AUG_FLIP 2
+#define FD_AUG_ROT_ON 3
+#define FD_AUG_ROT0 4
+#define FD_AUG_CROP_X 10
+#define FD_AUG_CROP_Y 11
+#define FD_AUG_CROP_W 12
+#define FD_AUG_CROP_H 13
+#define FD_AUG_NH 14
+#define FD_AUG_NW 15
+#define FD_AUG_NOPS 16
+#define FD_AUG_OP0 17
+#define FD_AUG_ARG0 21
+#define FD_AUG_MEAN_L 25
+#define FD_AUG_MAX_OPS 4
+#define FD_AUG_OP_BRIGHTNESS 1
+#define FD_AUG_OP_CONTRAST 2
+#define FD_AUG_OP_SATURATION 3
+#define FD_AUG_OP_HUE 4
+int32_t fd_augment_resize_collate_u8(const uint8_t* const* images_dev, const int32_t* recs_dev, float* y, int32_t N,
+                                     int32_t H, int32_t W, const float* mean3, const float* std3, fd_stream_t stream);
+int32_t fd_jitter_l_sums(const uint8_t* const* images_dev, int32_t* recs_dev, uint64_t* sums_dev, int32_t N,
+                         int64_t max_pixels, fd_stream_t stream);
+int32_t fd_color_jitter_u8(const uint8_t* x, int32_t h, int32_t w, uint8_t* y, const int32_t* rec_dev, fd_stream_t stream);
+int32_t fd_rotate_u8(const uint8_t* x, int32_t h, int32_t w, uint8_t* y, const int32_t* fixed6, fd_stream_t stream);
+
 /* GroupNorm(G, C) + activation (nn.GroupNorm in HISFCOSHead / HeadFCOS, HISFcos.py:190-204, Fcos.py:102-109).
  * Two launches: partial moments (fp64 accumulation, fixed order) then normalise+affine+act.
  * workspace: fd_groupnorm_workspace_bytes(segs, G). x and y may alias. */

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import enum
 import json
+import math
 import os
 import re
 import sys
@@ -1120,6 +1121,201 @@ def boxes_scale_batch_(boxes: torch.Tensor, scales: torch.Tensor, counts: Option
     check(_lib.lib().fd_boxes_scale_batch(boxes.data_ptr(), counts.data_ptr() if counts is not None else None, scales.data_ptr(), B, K,
                                           1 if invert else 0, 1 if xywh else 0, _stream()), "fd_boxes_scale_batch")
     return boxes
+
+
+# ---------------------------------------------------------------------------------------------- training augmentations
+AUG_WORDS = 32                                   # include/fcosdet.h FD_AUG_*: the per-image parameter record
+AUG_OP_BRIGHTNESS, AUG_OP_CONTRAST, AUG_OP_SATURATION, AUG_OP_HUE = 1, 2, 3, 4
+AUG_MAX_OPS = 4
+AUG_MAX_ROT_SIDE = 16384
+_AUG_H, _AUG_W, _AUG_FLIP, _AUG_ROT_ON, _AUG_ROT0, _AUG_CROP, _AUG_NH, _AUG_NW, _AUG_NOPS, _AUG_OP0, _AUG_ARG0, _AUG_MEAN_L = 0, 1, 2, 3, 4, 10, 14, 15, 16, 17, 21, 25
+
+
+def _fix16(v: float) -> int:
+    return int(v * 65536.0 + (-0.5 if v < 0 else 0.5))
+
+
+def rotation_fixed(d: float, h: int, w: int) -> Tuple[int, int, int, int, int, int]:
+    """The six 16.16 integers (A0, A1, X0, A3, A4, Y0) of PIL's img.rotate(d) (NEAREST, no expand, centre (w/2, h/2)) on an
+    h x w image: destination (x, y) takes source pixel ((X0 + A0*x + A1*y) >> 16, (Y0 + A3*x + A4*y) >> 16).  Doubles in PIL's
+    order of operations.  |d| < 90 and sides <= 16384: every |coordinate| stays below (side / 2) * (1 + sqrt 2) * 65536 < 2^31
+    (checked here on the four corners), the device adds in 64-bit integers."""
+    d, h, w = float(d), int(h), int(w)
+    if not abs(d) < 90.0:
+        raise FdError(f"rotation_fixed: |d| must be below 90 degrees (got {d})")
+    if h < 1 or w < 1 or h > AUG_MAX_ROT_SIDE or w > AUG_MAX_ROT_SIDE:
+        raise FdError(f"rotation_fixed: sides must be in 1 .. {AUG_MAX_ROT_SIDE} on the rotation path (got {h} x {w})")
+    angle = -math.radians(d % 360.0)
+    a0, a1 = round(math.cos(angle), 15), round(math.sin(angle), 15)
+    a3, a4 = round(-math.sin(angle), 15), round(math.cos(angle), 15)
+    cx, cy = w / 2.0, h / 2.0
+    a2 = a0 * -cx + a1 * -cy + 0.0
+    a5 = a3 * -cx + a4 * -cy + 0.0
+    a2 += cx
+    a5 += cy
+    fx = (_fix16(a0), _fix16(a1), _fix16(a2 + a0 * 0.5 + a1 * 0.5), _fix16(a3), _fix16(a4), _fix16(a5 + a3 * 0.5 + a4 * 0.5))
+    for x in (0, w - 1):
+        for y in (0, h - 1):
+            if abs(fx[2] + fx[0] * x + fx[1] * y) >= 2 ** 31 or abs(fx[5] + fx[3] * x + fx[4] * y) >= 2 ** 31:
+                raise FdError("rotation_fixed: fixed-point coordinate beyond 31 bits")      # unreachable within the limits above
+    return fx
+
+
+def hue_shift(hue: float) -> int:
+    """The uint8 added to H (with wrap) for a hue factor in [-0.5, 0.5]: truncation toward zero, modulo 256."""
+    hue = float(hue)
+    if not -0.5 <= hue <= 0.5:
+        raise FdError(f"hue factor must be in [-0.5, 0.5] (got {hue})")
+    return int(hue * 255) & 255
+
+
+def _f32_bits(f: float) -> int:
+    return int(np.array([f], np.float32).view(np.int32)[0])
+
+
+def _check_chain(chain, what: str):
+    chain = [(int(op), arg) for op, arg in chain]
+    if len(chain) > AUG_MAX_OPS:
+        raise FdError(f"{what}: a colour chain holds at most {AUG_MAX_OPS} operations (got {len(chain)})")
+    ids = [op for op, _ in chain]
+    if any(op not in (AUG_OP_BRIGHTNESS, AUG_OP_CONTRAST, AUG_OP_SATURATION, AUG_OP_HUE) for op in ids) or len(set(ids)) != len(ids):
+        raise FdError(f"{what}: chain operations must be distinct AUG_OP_* ids (got {ids})")
+    out = []
+    for op, arg in chain:
+        if op == AUG_OP_HUE:
+            arg = int(arg)
+            if not 0 <= arg <= 255:
+                raise FdError(f"{what}: the hue argument is the uint8 shift 0 .. 255 (ops.hue_shift(factor)); got {arg}")
+            out.append((op, arg))
+        else:
+            f = float(arg)
+            if not (math.isfinite(f) and f >= 0.0):
+                raise FdError(f"{what}: factor must be finite and >= 0 (got {f})")
+            out.append((op, _f32_bits(f)))
+    return out
+
+
+def augment_record(h: int, w: int, *, flip: bool = False, chain=(), d: float = 0.0, crop=None, nh: Optional[int] = None, nw: Optional[int] = None,
+                   what: str = "augment_record") -> List[int]:
+    """One validated parameter record (include/fcosdet.h FD_AUG_*) as a list of AUG_WORDS ints.  chain: [(AUG_OP_*, factor or
+    uint8 hue shift)] in application order; d: rotation in degrees (0: off); crop: (x, y, cw, ch) inside the image or None;
+    nh, nw: resized size of the crop (default: the crop's own size)."""
+    h, w = int(h), int(w)
+    if h < 1 or w < 1 or h > 65536 or w > 65536:
+        raise FdError(f"{what}: image sides must be in 1 .. 65536 (got {h} x {w})")
+    x, y, cw, ch = (0, 0, w, h) if crop is None else (int(v) for v in crop)
+    if cw < 1 or ch < 1 or x < 0 or y < 0 or x + cw > w or y + ch > h:
+        raise FdError(f"{what}: crop {(x, y, cw, ch)} (x, y, w, h) is not inside the {h} x {w} image")
+    nh, nw = ch if nh is None else int(nh), cw if nw is None else int(nw)
+    if nh < 1 or nw < 1:
+        raise FdError(f"{what}: resized size must be >= 1 x 1 (got {nh} x {nw})")
+    ops_ = _check_chain(chain, what)
+    rec = [0] * AUG_WORDS
+    rec[_AUG_H], rec[_AUG_W], rec[_AUG_FLIP] = h, w, 1 if flip else 0
+    if float(d) != 0.0:
+        rec[_AUG_ROT_ON] = 1
+        rec[_AUG_ROT0:_AUG_ROT0 + 6] = rotation_fixed(d, h, w)
+    rec[_AUG_CROP:_AUG_CROP + 4] = [x, y, cw, ch]
+    rec[_AUG_NH], rec[_AUG_NW], rec[_AUG_NOPS] = nh, nw, len(ops_)
+    for k, (op, bits) in enumerate(ops_):
+        rec[_AUG_OP0 + k], rec[_AUG_ARG0 + k] = op, bits
+    return rec
+
+
+def _has_contrast(rec) -> bool:
+    return AUG_OP_CONTRAST in rec[_AUG_OP0:_AUG_OP0 + rec[_AUG_NOPS]]
+
+
+def jitter_l_sums(images: Sequence[torch.Tensor], recs_dev: torch.Tensor, ptrs: torch.Tensor, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fd_jitter_l_sums: per image with contrast in its chain, the integer sum of L in front of the contrast operation
+    (int64 CUDA [N]) and the contrast mean into the records (recs_dev: int32 CUDA [N, AUG_WORDS], ptrs: int64 CUDA [N])."""
+    N = len(images)
+    _need_gpu(recs_dev, ptrs, *images)
+    if recs_dev.dtype != torch.int32 or tuple(recs_dev.shape) != (N, AUG_WORDS) or not recs_dev.is_contiguous() or ptrs.dtype != torch.int64 or ptrs.numel() != N:
+        raise FdError("jitter_l_sums: recs_dev must be contiguous int32 [N, AUG_WORDS] and ptrs int64 [N]")
+    if sums is None:
+        sums = torch.empty(N, dtype=torch.int64, device=recs_dev.device)
+    elif not sums.is_cuda or sums.dtype != torch.int64 or sums.numel() != N or not sums.is_contiguous():
+        raise FdError("jitter_l_sums: sums must be a contiguous CUDA int64 tensor of N elements")
+    mp = max(int(t.shape[0]) * int(t.shape[1]) for t in images)
+    check(_lib.lib().fd_jitter_l_sums(ptrs.data_ptr(), recs_dev.data_ptr(), sums.data_ptr(), N, mp, _stream()), "fd_jitter_l_sums")
+    return sums
+
+
+def augment_resize_collate_u8(images: Sequence[torch.Tensor], params, H: int, W: int, mean, std, out: Optional[torch.Tensor] = None):
+    """RAW uint8 [h_n, w_n, 3] CUDA images -> flipped / colour-jittered / rotated / cropped as params[n] says, resized, padded to
+    the H x W canvas and normalised: the planar fp32 [N, 3, H, W] batch of the reference's collate_fn in ONE launch (plus the
+    L-sum launch when a chain holds contrast).  params[n]: dict(flip=, chain=, d=, crop=, nh=, nw=), the keywords of
+    augment_record.  Returns (batch, keep-alive tuple).  Does not synchronise."""
+    images = list(images)
+    N = len(images)
+    if N < 1:
+        raise FdError("augment_resize_collate_u8: empty image list")
+    for t in images:
+        _check_raw_image(t, "augment_resize_collate_u8")
+    params = list(params)
+    if len(params) != N:
+        raise FdError("augment_resize_collate_u8: one parameter set per image")
+    H, W = int(H), int(W)
+    recs = []
+    for t, p in zip(images, params):
+        rec = augment_record(int(t.shape[0]), int(t.shape[1]), what="augment_resize_collate_u8", **p)
+        if rec[_AUG_NH] > H or rec[_AUG_NW] > W:
+            raise FdError(f"augment_resize_collate_u8: resized size {rec[_AUG_NH]} x {rec[_AUG_NW]} exceeds the {H} x {W} canvas")
+        recs.append(rec)
+    dev = images[0].device
+    if out is None:
+        out = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != N * 3 * H * W:
+        raise FdError("augment_resize_collate_u8: out must be a contiguous CUDA fp32 tensor of N * 3 * H * W elements")
+    # one table, one copy: the N image pointers (two int32 words each) in front, then the N records
+    table = np.empty(N * (AUG_WORDS + 2), np.int32)
+    table[:2 * N] = np.array([t.data_ptr() for t in images], np.int64).view(np.int32)
+    table[2 * N:] = np.array(recs, np.int64).astype(np.int32).reshape(-1)
+    tab = torch.from_numpy(table).to(dev, non_blocking=True)
+    ptrs, recs_dev = tab[:2 * N].view(torch.int64), tab[2 * N:].view(N, AUG_WORDS)
+    sums = None
+    if any(_has_contrast(r) for r in recs):
+        sums = jitter_l_sums(images, recs_dev, ptrs)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s_ = (C.c_float * 3)(*[float(v) for v in std])
+    check(_lib.lib().fd_augment_resize_collate_u8(ptrs.data_ptr(), recs_dev.data_ptr(), out.data_ptr(), N, H, W, m, s_, _stream()),
+          "fd_augment_resize_collate_u8")
+    return out.view(N, 3, H, W), (tab, sums, tuple(images))
+
+
+def rotate_u8(img: torch.Tensor, d: float) -> torch.Tensor:
+    """PIL's img.rotate(d) (NEAREST, no expand) of a raw uint8 [h, w, 3] CUDA image, exact: 16.16 fixed-point integer
+    arithmetic on the device (random_rotation, data/augment.py:26-30).  d == 0 is the identity; |d| >= 90 is refused."""
+    _check_raw_image(img, "rotate_u8")
+    d = float(d)
+    if not abs(d) < 90.0:
+        raise FdError(f"rotate_u8: |d| must be below 90 degrees (got {d})")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    if d == 0.0:
+        return img.clone()
+    fx = (C.c_int32 * 6)(*rotation_fixed(d, h, w))
+    out = torch.empty_like(img)
+    check(_lib.lib().fd_rotate_u8(img.data_ptr(), h, w, out.data_ptr(), fx, _stream()), "fd_rotate_u8")
+    return out
+
+
+def color_jitter_u8(img: torch.Tensor, chain) -> torch.Tensor:
+    """One raw uint8 [h, w, 3] CUDA image through a colour chain [(AUG_OP_*, factor or uint8 hue shift), ...] -> uint8:
+    PIL's ImageEnhance Brightness / Contrast / Color and the HSV hue shift, exact."""
+    _check_raw_image(img, "color_jitter_u8")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    rec = augment_record(h, w, chain=chain, what="color_jitter_u8")
+    table = np.empty(AUG_WORDS + 2, np.int32)
+    table[:2] = np.array([img.data_ptr()], np.int64).view(np.int32)
+    table[2:] = np.array(rec, np.int64).astype(np.int32)
+    tab = torch.from_numpy(table).to(img.device, non_blocking=True)
+    ptrs, rec_dev = tab[:2].view(torch.int64), tab[2:].view(1, AUG_WORDS)
+    if _has_contrast(rec):
+        jitter_l_sums([img], rec_dev, ptrs)
+    out = torch.empty_like(img)
+    check(_lib.lib().fd_color_jitter_u8(img.data_ptr(), h, w, out.data_ptr(), rec_dev.data_ptr(), _stream()), "fd_color_jitter_u8")
+    return out
 
 
 def dwconv3x3_wgrad(x: Rows, dy: Rows, segs: Segs, scale: Optional[torch.Tensor] = None, torch_layout: bool = False) -> torch.Tensor:
