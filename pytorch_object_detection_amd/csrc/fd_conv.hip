@@ -731,9 +731,8 @@ static int dispatch_conv(const fd_conv_params* p, ConvArgs& a, bool stem, hipStr
         }
     }
     // GEMM-addressed fp32 layers (1x1, stride 1, no padding, Cin % 32 == 0, no gate): the loader compiled without the tap / bounds arithmetic
-    static const int gemm_on = getenv("FD_CONV_GEMM") ? atoi(getenv("FD_CONV_GEMM")) : 1;
     const bool pointwise = !stem && p->KH == 1 && p->KW == 1 && p->pad == 0;     // any stride: one input address per output row
-    if (gemm_on && pointwise && p->Cin % 32 == 0 && !a.gate && !a.sc_on) {
+    if (pointwise && p->Cin % 32 == 0 && !a.gate && !a.sc_on) {
         switch (p->tile) {
             case FD_TILE_128x128: return launch_conv<2, 2, 2, 2, false, false, 0, false, false, false, false, true>(a, stream);
             case FD_TILE_128x64: return launch_conv<2, 2, 2, 1, false, false, 0, false, false, false, false, true>(a, stream);

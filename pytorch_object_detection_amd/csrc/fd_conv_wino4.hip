@@ -698,7 +698,6 @@ int fd_launch_conv_wino4(const fd_conv_params* p, hipStream_t stream) {
         {   // pieces per remainder item: the choice that gets the remainder of the fullest XCD through in the least time -- ceil(rem * P / wpx) passes of
             // (NC / P chunks + the fixed cost of a segment), in units of one chunk's time (fixed cost ~ 6.5 chunks: profiles/r05_wino4_fixed_cost_raw.txt, _phases.txt); the slots of an XCD
             // (rem * (P - 1)) must fit the workspace's wpx
-            static const int force_p = getenv("FD_W4_SK_P") ? atoi(getenv("FD_W4_SK_P")) : 0;
             // (every XCD has its own remainder -- the last one owns fewer M tiles: the slot bound must hold for each, the time is the slowest XCD's)
             int best = 1; double best_t = 1e30; bool any_rem = false;
             for (int P = 1; P <= 4 && P <= a.NC; ++P) {          // (more than 4 pieces: the finisher's serial slot reads cost more than the pieces save -- layer1.conv2 at P = 8: 0.176 against 0.145 ms)
@@ -715,12 +714,6 @@ int fd_launch_conv_wino4(const fd_conv_params* p, hipStream_t stream) {
                 if (ok && t < best_t - 1e-9) { best_t = t; best = P; }
             }
             a.sk_P = any_rem ? best : 1;
-            bool force_ok = force_p > 0 && force_p <= a.NC && force_p <= 16;
-            for (int x = 0; x < 8 && force_ok; ++x) {
-                const int cx = (a.mtiles >> 3) + (x < (a.mtiles & 7) ? 1 : 0);
-                if (cx > 0 && force_p > 1 && (cx * a.ntiles % a.wpx) * (force_p - 1) > a.wpx) force_ok = false;
-            }
-            if (force_ok) a.sk_P = force_p;
         }
         const int64_t need = fd_wino4_sk_workspace_bytes_impl(p->sk_wgs);
         FD_REQUIRE(p->workspace && ((uintptr_t)p->workspace & 255) == 0 && p->workspace_bytes >= need, FD_E_INVAL,

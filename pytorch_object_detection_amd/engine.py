@@ -28,25 +28,11 @@ import os as _os
 # conv except the 7x7 stem (K = 147 is too short to matter).  See include/fcosdet.h FD_PREC_*.
 CONV_PRECISION = _os.environ.get("FD_CONV_PRECISION", "f32")
 AUTOTUNE = True   # per-conv block-tile lookup / timing at plan-build time (see ops.autotune_conv, FD_AUTOTUNE)
-SE_GATE_IN_PROJECT = _os.environ.get("FD_SE_GATE_FUSED", "1") != "0"     # MBConv: SE gate applied by the project conv's loader ("0": a scaling pass)
-GN_FUSED_TOWER = _os.environ.get("FD_GN_FUSED_TOWER", "0") == "1"   # "1": the tower's statistics from its Winograd epilogue too (measured neutral, costs the tower launch 5 %)
-# "1": a head-tower F(4x4) launch whose grid is no multiple of the CU count runs as whole rounds of workgroups + a tail launch ("head.tower3x3.tail", after the mark):
-# TwoLanePipeline releases the other lane when the whole rounds are done, so the tail round (60 % of the chip idle at 16 x 640 x 640) has company
-TOWER_TAIL_SPLIT = _os.environ.get("FD_TOWER_TAIL_SPLIT", "1") != "0"
-# "1": an MBConv block's expand conv and depthwise conv run as ONE launch where the shapes allow (fd_mbconv_expand_dw_nhwc: Cin <= 48, k in {3, 5}); "0": separate launches
-MBCONV_FUSED = _os.environ.get("FD_MBCONV_FUSED", "1") != "0"
-FPN_UP_FUSED = _os.environ.get("FD_FPN_UP_FUSED", "1") != "0"   # "0": the top-down path's x2 upsample + add as its own pass over the finer map (else in the lateral conv's epilogue)
-TOWER_GN_SPLIT = _os.environ.get("FD_TOWER_GN_SPLIT", "1") != "0"   # "0": the tower's GroupNorm normalises both halves in its own pass (else the box half in the narrow predictor's loader)
 GN_FUSED = _os.environ.get("FD_GN_FUSED", "1") != "0"       # "0": HISFCOSHead's GroupNorms as three-pass launches (statistics / finalise / normalise)
-WAVE_TILE = _os.environ.get("FD_WAVE_TILE", "1") != "0"       # "0": the 1x1 layers never see FD_TILE_WAVE64 (wave-autonomous tiles, fd_conv_wave.hip)
-B2B_MIN_ROWS = int(_os.environ.get("FD_B2B_MIN_ROWS", str(64 * 1024)))   # fewer rows than 1 024 waves of 64: the seam stays two workgroup-tiled launches
-DUAL_DS = _os.environ.get("FD_DUAL_DS", "1") != "0"      # "0": a block's downsample conv as its own launch, its output read back as conv3's residual
-# FD_B2B: the trunk layers (digits) whose conv3 -> next-block conv1 seams run as ONE back-to-back launch (fd_conv1x1_b2b_f32: the 4 * planes wide map is
-# written once and never read back); "" = none
-B2B_LAYERS = _os.environ.get("FD_B2B", "1")
-STEM_NCHW = _os.environ.get("FD_STEM_NCHW", "1") != "0"         # "0": an fp32 NCHW input batch is first copied to the [N][H][W][4] layout (fd_nchw3_to_nhwc4) instead of being read by the stem's loader
-STEM_POOL = _os.environ.get("FD_STEM_POOL", "1") != "0"         # "0": the stem's 3x3 s2 max-pool as its own launch (the 64-channel stride-2 map written and read back)
-STEM_KERNEL = _os.environ.get("FD_STEM_KERNEL", "1") != "0"     # "0": the ResNet stem through the generic conv kernel's FD_CONV_STEM mode
+B2B_MIN_ROWS = 64 * 1024   # fewer rows than 1 024 waves of 64: the seam stays two workgroup-tiled launches
+# the trunk layers (digits) whose conv3 -> next-block conv1 seams run as ONE back-to-back launch (fd_conv1x1_b2b_f32: the 4 * planes wide map is
+# written once and never read back)
+B2B_LAYERS = "1"
 
 
 class PRows(Rows):
@@ -224,7 +210,7 @@ def add_conv(plan: Plan, name: str, x: Rows, segs: Segs, conv: torch.nn.Conv2d, 
         wp = ops.pack_conv_weight_f16x3(_dev(w, dev)) if fmt is WF.DIRECT_F16 else ops.pack_conv_weight(_dev(w, dev))
     # GEMM-addressed fp32 layers also get their weights in MFMA fragment order: the wave-autonomous tile (FD_TILE_WAVE64) becomes selectable
     wfrag = None
-    if (fmt is WF.DIRECT and x2 is None and not res_up and WAVE_TILE and gate is None and ops.wave_ok(Cin, co, k, stride, pad) and act_c0 % 32 == 0
+    if (fmt is WF.DIRECT and x2 is None and not res_up and gate is None and ops.wave_ok(Cin, co, k, stride, pad) and act_c0 % 32 == 0
             and act in (ACT_NONE, ACT_RELU, ACT_SILU) and aligned and w.shape[0] == co and w.shape[1] == Cin):
         wfrag = ops.pack_conv_weight_wave(_dev(w, dev))
     scale = shift = None
@@ -266,7 +252,9 @@ def add_conv(plan: Plan, name: str, x: Rows, segs: Segs, conv: torch.nn.Conv2d, 
             call = ops.conv_sk(call, sk, plan.sk_ws)
             plan.sk_of = getattr(plan, "sk_of", {})
             plan.sk_of[name] = sk
-    if tag == 1 and wino4 and wino_ks <= 1 and TOWER_TAIL_SPLIT and not sk:
+    if tag == 1 and wino4 and wino_ks <= 1 and not sk:
+        # a head-tower F(4x4) launch whose grid is no multiple of the CU count runs as whole rounds of workgroups + a tail launch ("head.tower3x3.tail", after the
+        # mark): TwoLanePipeline releases the other lane when the whole rounds are done, so the tail round (60 % of the chip idle at 16 x 640 x 640) has company
         ncu = torch.cuda.get_device_properties(dev).multi_processor_count
         total, live = ops.conv_workgroups(call)
         full = total // ncu * ncu          # (one workgroup of that kernel owns a CU; ncu % 8 == 0: the slice starts on an XCD boundary)
@@ -291,7 +279,7 @@ def add_conv(plan: Plan, name: str, x: Rows, segs: Segs, conv: torch.nn.Conv2d, 
                            pre="f16x3" if fmt is WF.DIRECT_F16 else "", x2=(x2_stride, x2.C) if x2 is not None else None)
         if res_up and key not in ops._tune_table():
             # a table MISS of a res_up layer is timed with res_mode 2 set, i.e. over the RUP tiles only: that restricted winner gets a key of its own and never
-            # lands under the plain layer's key (which the unfused FD_FPN_UP_FUSED=0 lateral of the same shape reads).  A plain-key HIT is still mapped below.
+            # lands under the plain layer's key (which a plain lateral of the same shape, without the upsample-add in its epilogue, reads).  A plain-key HIT is still mapped below.
             key += "|rup"
         code = plan.tiles[name] = ops.autotune_conv(call, key, out.rows, co, -(-Cin // 32) * k * k, pair=plan.pair_tuned and tag != 1)
         if res_up or x2 is not None:
@@ -355,10 +343,11 @@ def add_input(plan: Plan, x4: Rows, batch: int, H: int, W: int, image_ref: List)
 def build_resnet50(plan: Plan, trunk, batch: int, H: int, W: int, image_ref: List[torch.Tensor]):
     """torchvision-style ResNet-50 v1.5 trunk -> (C3, C4, C5) as (Rows, Segs).  `trunk` has conv1, bn1, layer1..4."""
     dev, pool = plan.device, plan.pool
-    stem_own = STEM_KERNEL and plan.precision in ("f32", "mixed") and tuple(trunk.conv1.weight.shape) == (64, 3, 7, 7)
+    # the dedicated stem kernels (fd_stem.hip: patch + filters staged in LDS); other precisions and filter shapes take the generic conv kernel's FD_CONV_STEM mode
+    stem_own = plan.precision in ("f32", "mixed") and tuple(trunk.conv1.weight.shape) == (64, 3, 7, 7)
     mode = getattr(plan, "input_mode", None) or ("u8" if getattr(plan, "input_u8", None) else None)
     # the reference's fp32 NCHW batch is read by the stem's own patch loader (fd_stem7x7_nchw3): no [N][H][W][4] copy, no conversion launch
-    nchw_in = STEM_NCHW and stem_own and mode is None
+    nchw_in = stem_own and mode is None
     x4 = None
     if not nchw_in:
         x4 = pool.get(batch * H * W, 4)
@@ -371,7 +360,6 @@ def build_resnet50(plan: Plan, trunk, batch: int, H: int, W: int, image_ref: Lis
     H1, W1 = s1.H[0], s1.W[0]
     H2, W2 = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
     s2 = Segs.make(batch, [(H2, W2)])
-    fused_pool = STEM_POOL and stem_own
 
     def nchw_image() -> torch.Tensor:
         x = image_ref[0]
@@ -379,7 +367,8 @@ def build_resnet50(plan: Plan, trunk, batch: int, H: int, W: int, image_ref: Lis
             raise FdError(f"plan input: expected a [{batch}, 3, {H}, {W}] batch, got {tuple(x.shape)}")
         return x
 
-    if fused_pool:
+    y1 = None
+    if stem_own:
         # conv1 + bn1 + relu + maxpool as ONE launch (fd_stem7x7_pool_nhwc4): the 64-channel stride-2 map is never written (resnet50.py:68-80)
         wp = ops.pack_stem7_weight(_dev(trunk.conv1.weight, dev))
         y2 = pool.get(s2.rows, 64)
@@ -387,30 +376,17 @@ def build_resnet50(plan: Plan, trunk, batch: int, H: int, W: int, image_ref: Lis
             plan.add("backbone.conv1+maxpool", lambda: ops.stem7x7_nchw(nchw_image(), wp, y2, sc, sf, pool=True))
         else:
             plan.add("backbone.conv1+maxpool", lambda: ops.stem7x7_pool(x4, wp, y2, batch, H, W, sc, sf))
-        plan.keep += [wp, sc, sf]
-        plan.flops += 2 * s1.rows * 64 * 147
-        plan.step_flops[len(plan.steps) - 1] = 2 * s1.rows * 64 * 147
-        if x4 is not None:
-            pool.put(x4)
-    y1 = pool.get(s1.rows, 64) if not fused_pool else None
-    if fused_pool:
-        pass
-    elif stem_own:
-        wp = ops.pack_stem7_weight(_dev(trunk.conv1.weight, dev))      # the dedicated stem kernel (fd_stem.hip): patch + filters staged in LDS
-        if nchw_in:
-            plan.add("backbone.conv1", lambda: ops.stem7x7_nchw(nchw_image(), wp, y1, sc, sf, ACT_RELU))
-        else:
-            plan.add("backbone.conv1", lambda: ops.stem7x7(x4, wp, y1, batch, H, W, sc, sf, ACT_RELU))
     else:
         wp = ops.pack_stem_weight(_dev(trunk.conv1.weight, dev))
+        y1 = pool.get(s1.rows, 64)
         plan.add("backbone.conv1", ops.conv_call(x4, s_in, wp, y1, Cin=4, Cout=64, k=7, stride=2, pad=3, scale=sc, shift=sf,
                                                  act=ACT_RELU, stem=True))
-    if not fused_pool:
-        plan.keep += [wp, sc, sf]
-        plan.flops += 2 * s1.rows * 64 * 147
-        plan.step_flops[len(plan.steps) - 1] = 2 * s1.rows * 64 * 147
-        if x4 is not None:
-            pool.put(x4)
+    plan.keep += [wp, sc, sf]
+    plan.flops += 2 * s1.rows * 64 * 147
+    plan.step_flops[len(plan.steps) - 1] = 2 * s1.rows * 64 * 147
+    if x4 is not None:
+        pool.put(x4)
+    if y1 is not None:
         y2 = pool.get(s2.rows, 64)
         plan.add("backbone.maxpool", lambda: ops.maxpool(y1, y2, batch, H1, W1, 3, 2, 1))
         pool.put(y1)
@@ -431,7 +407,7 @@ def build_resnet50(plan: Plan, trunk, batch: int, H: int, W: int, image_ref: Lis
         o2 = pool.get(so.rows, planes)
         add_conv(plan, nm + ".conv2", o1, sx, blk.conv2, o2, bn=blk.bn2, act=ACT_RELU)
         pool.put(o1)
-        dual = (DUAL_DS and ds is not None and plan.precision == "f32" and ds[0].kernel_size[0] == 1 and ds[0].bias is None and blk.conv3.bias is None
+        dual = (ds is not None and plan.precision == "f32" and ds[0].kernel_size[0] == 1 and ds[0].bias is None and blk.conv3.bias is None
                 and planes % 32 == 0 and x.C % 32 == 0 and x.cs % 4 == 0 and x.co % 4 == 0 and ds[0].stride[0] == blk.conv2.stride[0])
         if dual:
             # out = relu(bn3(conv3(o2)) + bn_d(downsample(x))) as ONE GEMM over K = planes + inplanes: the BatchNorm scales go into the two filter banks,
@@ -543,7 +519,7 @@ def build_efficientnet(plan: Plan, net, batch: int, H: int, W: int, image_ref: L
         # and the SE pooling comes out of the same kernel as per-tile partial sums)
         # (k = 5 at stride 2 stays separate: a 6 x 6 output tile needs a 15 x 15 patch -- 1.56 x the expand GEMM and a depthwise stage that fills 56 % of its threads:
         #  0.70 ms fused against 0.60 ms for B3's block 5, profiles/r05_layer_times_fcos_b3_mbconv_fused.tsv)
-        fused = (MBCONV_FUSED and blk.expand != 1 and plan.precision == "f32" and blk._expand_conv.bias is None and not (blk.kernel == 5 and blk.stride == 2)
+        fused = (blk.expand != 1 and plan.precision == "f32" and blk._expand_conv.bias is None and not (blk.kernel == 5 and blk.stride == 2)
                  and ops.mbconv_fused_ok(x.C, mid, blk.kernel, blk.stride) and x.C == blk._expand_conv.weight.shape[1])
         d = pool.get(so.rows, mid)
         wd = ops.pack_dwk_weight(_dev(blk._depthwise_conv.weight, dev))
@@ -579,7 +555,7 @@ def build_efficientnet(plan: Plan, net, batch: int, H: int, W: int, image_ref: L
         sews = ops.se_workspace(batch, ho * wo, mid, dev)
         plan.keep += [wd, w1, b1, w2, b2, sews]
         out = pool.get(so.rows, blk.cout)
-        if SE_GATE_IN_PROJECT and plan.precision in ("f32", "mixed"):
+        if plan.precision in ("f32", "mixed"):
             # the gate is multiplied in by the project conv's loader: no scaling pass (a read and a write of the expanded map) at all
             if pool_part is not None:       # ... and its pooling came out of the fused expand + depthwise launch: no pass over the map at all
                 plan.add(nm + "._se", lambda pp=pool_part, nt=ntile, w1=w1, b1=b1, w2=w2, b2=b2, sews=sews, hw=ho * wo, mid=mid:
@@ -682,7 +658,7 @@ def build_his_fpn(plan: Plan, fpn, feats):
     _his_block(plan, "fpn.HisBlock1", fpn.HisBlock1, a, s5, t3)
     pool.put(a)
     l4 = pool.get(s4.rows, F)
-    up_fused = FPN_UP_FUSED and plan.precision == "f32" and all(h % 2 == 0 and w % 2 == 0 for h, w in hw[:2]) and fpn.tf2.weight.shape[1] % 32 == 0 and fpn.tf3.weight.shape[1] % 32 == 0
+    up_fused = plan.precision == "f32" and all(h % 2 == 0 and w % 2 == 0 for h, w in hw[:2]) and fpn.tf2.weight.shape[1] % 32 == 0 and fpn.tf3.weight.shape[1] % 32 == 0
     if up_fused:       # relu(gn2(tf2(c4))) + Up_sample1(t3) in one launch: the coarser level is read at (i / 2, j / 2) by the lateral's epilogue (HISFcos.py:155-159)
         add_conv(plan, "fpn.tf2+up1_add", c4, s4, fpn.tf2, l4, bn=fpn.gn2, act=ACT_RELU, res=t3, res_up=True)
     else:
@@ -761,7 +737,7 @@ def _out_convs(plan: Plan, head, tower: Rows, segs: Segs, F: int, ncls: int, reg
 
 
 def _flush_tail_steps(plan: Plan) -> None:
-    """The tail launches add_conv set aside (TOWER_TAIL_SPLIT) become steps of their own -- called right AFTER the caller closed its mark, so that the mark
+    """The tail launches add_conv set aside (a tower grid split into whole rounds + tail) become steps of their own -- called right AFTER the caller closed its mark, so that the mark
     (= what TwoLanePipeline keeps exclusive and bench.py times as the roofline launch) covers the whole rounds only."""
     for nm, fn, fl, info in getattr(plan, "tail_steps", []):
         plan.add(nm, fn)
@@ -771,15 +747,20 @@ def _flush_tail_steps(plan: Plan) -> None:
     plan.tail_steps = []
 
 
-def _fused_gn(plan: Plan, name: str, x: Rows, segs: Segs, gns, act: int) -> None:
-    """k GroupNorm(32, F) over k adjacent F-channel slices == one GroupNorm(32k, kF) with concatenated affine."""
+def _gn_params(plan: Plan, gns, segs: Segs):
+    """k GroupNorm(32, F) over k adjacent F-channel slices == one GroupNorm(32k, kF) with concatenated affine: -> (gamma, beta, G, eps, workspace)."""
     dev = plan.device
     gamma = torch.cat([_dev(g.weight, dev) for g in gns]).contiguous()
     beta = torch.cat([_dev(g.bias, dev) for g in gns]).contiguous()
     G = sum(g.num_groups for g in gns)
     ws = ops.groupnorm_workspace(segs, G, dev)
-    eps = gns[0].eps
     plan.keep += [gamma, beta, ws]
+    return gamma, beta, G, gns[0].eps, ws
+
+
+def _fused_gn(plan: Plan, name: str, x: Rows, segs: Segs, gns, act: int) -> None:
+    """The GroupNorm(s) `gns` + activation over adjacent channel slices of x, in place, as one launch."""
+    gamma, beta, G, eps, ws = _gn_params(plan, gns, segs)
     plan.add(name, lambda: ops.groupnorm_act(x, gamma, beta, x, segs, G, act, ws, eps))
 
 
@@ -791,17 +772,19 @@ def _gn_fusable(plan: Plan, gns, Cc: int) -> bool:
             and Cc % 32 == 0 and 256 % (2 * G) == 0 and Cc <= 1024 and 256 % (Cc // 4) == 0 and ((Cc // 4) % 64 == 0 or 64 % (Cc // 4) == 0))
 
 
-def _gn_from_rowstats(plan: Plan, name: str, rgs, segs: Segs, gns, Cc: int, want_coef: bool):
-    """The reduction step behind a producer that left row-group sums in `rgs`: -> (workspace, gamma, beta, G, eps, coef | None)."""
-    dev = plan.device
-    gamma = torch.cat([_dev(g.weight, dev) for g in gns]).contiguous()
-    beta = torch.cat([_dev(g.bias, dev) for g in gns]).contiguous()
-    G, eps = sum(g.num_groups for g in gns), gns[0].eps
-    ws = ops.groupnorm_workspace(segs, G, dev)
-    coef = torch.empty(segs.nseg * segs.batch, 2, Cc, dtype=torch.float32, device=dev) if want_coef else None
-    plan.keep += [gamma, beta, ws, coef]
+def _gn_coef(plan: Plan, segs: Segs, Cc: int) -> torch.Tensor:
+    """Buffer for the per-(level, image) [scale | shift] rows that the consumer of a GroupNorm over Cc channels applies in its loader."""
+    coef = torch.empty(segs.nseg * segs.batch, 2, Cc, dtype=torch.float32, device=plan.device)
+    plan.keep.append(coef)
+    return coef
+
+
+def _gn_from_rowstats(plan: Plan, name: str, rgs, segs: Segs, gns, Cc: int) -> torch.Tensor:
+    """The reduction step behind a producer that left row-group sums in `rgs` -> the normalisation coefficients (_gn_coef)."""
+    gamma, beta, G, eps, ws = _gn_params(plan, gns, segs)
+    coef = _gn_coef(plan, segs, Cc)
     plan.add(name, lambda: ops.groupnorm_from_rowstats(rgs.buf, Cc, G, eps, gamma, beta, segs, ws, coef))
-    return ws, gamma, beta, G, eps, coef
+    return coef
 
 
 def build_his_head(plan: Plan, head, pyr: Rows, segs: Segs):
@@ -810,8 +793,8 @@ def build_his_head(plan: Plan, head, pyr: Rows, segs: Segs):
     GroupNorm is folded into its neighbours (FD_GN_FUSED=1, exact-fp32 plans): the producing conv's epilogue leaves per-row group sums
     (fd_conv_params.gn_stats), a small reduction turns them into per-(level, image) statistics, and the CONSUMER normalises on its way in
     -- dw1 reads ReLU(GN1(.)) in its window loads, pw2 reads SiLU(GN2(.)) in its operand loader -- so the pre-block is
-    pw1 | dw1 | pw2 over HBM (4 passes over a 512-channel map instead of 10).  The tower's GroupNorm keeps its one normalise pass
-    (its consumers are the Winograd predictors) but loses its statistics pass."""
+    pw1 | dw1 | pw2 over HBM (4 passes over a 512-channel map instead of 10).  The tower's GroupNorm keeps a statistics pass; its box half is
+    normalised in the narrow predictor's loader where that kernel runs, so only the class half (read by a Winograd predictor) keeps a normalise pass."""
     dev, pool = plan.device, plan.pool
     M = segs.rows
     F = head.pw1.weight.shape[1]
@@ -824,12 +807,12 @@ def build_his_head(plan: Plan, head, pyr: Rows, segs: Segs):
         G1, G2 = head.gn1.num_groups, head.gn2.num_groups
         rgs1 = pool.get(M, 2 * G1)
         add_conv(plan, "head.pw1", pyr, segs, head.pw1, h1, gn_stats=rgs1.buf, gn_groups=G1)
-        coef1 = _gn_from_rowstats(plan, "head.gn1.stats", rgs1, segs, [head.gn1], 2 * F, True)[5]
+        coef1 = _gn_from_rowstats(plan, "head.gn1.stats", rgs1, segs, [head.gn1], 2 * F)
         pool.put(rgs1)
         h2 = pool.get(M, 2 * F)
         rgs2 = pool.get(M, 2 * G2)
         plan.add("head.dw1", lambda: ops.dwconv3x3_gn(h1, wd, h2, segs, coef1, ACT_RELU, rgs2.buf, G2))
-        coef2 = _gn_from_rowstats(plan, "head.gn2.stats", rgs2, segs, [head.gn2], 2 * F, True)[5]
+        coef2 = _gn_from_rowstats(plan, "head.gn2.stats", rgs2, segs, [head.gn2], 2 * F)
         pool.put(rgs2); pool.put(h1)
         z = pool.get(M, F)
         add_conv(plan, "head.pw2", h2, segs, head.pw2, z, res=pyr, gate=coef2[:, 0], gate_b=coef2[:, 1], gate_act=ACT_SILU)
@@ -846,48 +829,22 @@ def build_his_head(plan: Plan, head, pyr: Rows, segs: Segs):
     tower = pool.get(M, 2 * F)
     w = torch.cat([head.cls_conv[0].weight.detach(), head.reg_conv[0].weight.detach()], 0)
     tgn = [head.cls_conv[1], head.reg_conv[1]]
-    t_fused = GN_FUSED_TOWER and _gn_fusable(plan, tgn, 2 * F)
-    if t_fused:          # (a statistics epilogue has no split-K form)
-        c = ops.choose_conv(segs, F, 2 * F, 3, 1, 1, 1, plan.precision, gn_stats=True, force_wino=True)
-        t_fused = c.fmt is ops.WFormat.WINO and c.ksplit == 1
     mark = len(plan.steps)
-    if t_fused:
-        Gt = sum(g.num_groups for g in tgn)
-        rgs3 = pool.get(M, 2 * Gt)
-        add_conv(plan, "head.tower3x3", z, segs, head.cls_conv[0], tower, weight=w, Cout=2 * F, tag=1, gn_stats=rgs3.buf, gn_groups=Gt)
-        plan.marks["head.tower3x3"] = (mark, len(plan.steps))
-        _flush_tail_steps(plan)
-        reg_in_loader = TOWER_GN_SPLIT and _narrow_predictor(plan, head, segs, F)
-        ws, gamma, beta, G, eps, coef = _gn_from_rowstats(plan, "head.tower_gn.stats", rgs3, segs, tgn, 2 * F, reg_in_loader)
-        pool.put(rgs3)
-        if reg_in_loader:
-            # the box half of the tower is normalised inside the narrow predictor's patch loader; only the class half (whose consumer is the
-            # F(4x4) kernel: no registers for an affine in its loader) keeps a normalise pass -- over half the bytes
-            tc = tower.slice(0, F)
-            plan.add("head.tower_gn", lambda: ops.coef_apply(tc, coef[:, 0, :F], coef[:, 1, :F], tc, segs, ACT_RELU))
-            pool.put(z)
-            return _out_convs(plan, head, tower, segs, F, ncls, reg_gate=(coef[:, 0, F:], coef[:, 1, F:], ACT_RELU))
-        plan.add("head.tower_gn", lambda: ops.groupnorm_apply(tower, gamma, beta, tower, segs, G, ACT_RELU, ws, eps))
-    else:
-        add_conv(plan, "head.tower3x3", z, segs, head.cls_conv[0], tower, weight=w, Cout=2 * F, tag=1)
-        plan.marks["head.tower3x3"] = (mark, len(plan.steps))
-        _flush_tail_steps(plan)
-        if TOWER_GN_SPLIT and _narrow_predictor(plan, head, segs, F) and 256 % (F // 4) == 0:
-            # statistics of both halves in one pass; the class half keeps a normalise pass (over half the bytes), the box half is normalised inside
-            # the narrow predictor's patch loader (fd_conv_params.gate_b on FD_TILE_NARROW): same arithmetic, bit-identical outputs
-            gamma = torch.cat([_dev(g.weight, dev) for g in tgn]).contiguous()
-            beta = torch.cat([_dev(g.bias, dev) for g in tgn]).contiguous()
-            G, eps = sum(g.num_groups for g in tgn), tgn[0].eps
-            ws = ops.groupnorm_workspace(segs, G, dev)
-            coef = torch.empty(segs.nseg * segs.batch, 2, 2 * F, dtype=torch.float32, device=dev)
-            plan.keep += [gamma, beta, ws, coef]
-            plan.add("head.tower_gn.stats", lambda: ops.groupnorm_stats(tower, gamma, beta, segs, G, ws, eps, coef))
-            tc = tower.slice(0, F)
-            plan.add("head.tower_gn", lambda: ops.coef_apply(tc, coef[:, 0, :F], coef[:, 1, :F], tc, segs, ACT_RELU))
-            pool.put(z)
-            return _out_convs(plan, head, tower, segs, F, ncls, reg_gate=(coef[:, 0, F:], coef[:, 1, F:], ACT_RELU))
-        _fused_gn(plan, "head.tower_gn", tower, segs, tgn, ACT_RELU)
+    add_conv(plan, "head.tower3x3", z, segs, head.cls_conv[0], tower, weight=w, Cout=2 * F, tag=1)
+    plan.marks["head.tower3x3"] = (mark, len(plan.steps))
+    _flush_tail_steps(plan)
     pool.put(z)
+    if _narrow_predictor(plan, head, segs, F) and 256 % (F // 4) == 0:
+        # statistics of both halves in one pass; the class half (whose consumer is the F(4x4) kernel: no registers for an affine in its loader) keeps a
+        # normalise pass (over half the bytes), the box half is normalised inside the narrow predictor's patch loader (fd_conv_params.gate_b on
+        # FD_TILE_NARROW): same arithmetic, bit-identical outputs
+        gamma, beta, G, eps, ws = _gn_params(plan, tgn, segs)
+        coef = _gn_coef(plan, segs, 2 * F)
+        plan.add("head.tower_gn.stats", lambda: ops.groupnorm_stats(tower, gamma, beta, segs, G, ws, eps, coef))
+        tc = tower.slice(0, F)
+        plan.add("head.tower_gn", lambda: ops.coef_apply(tc, coef[:, 0, :F], coef[:, 1, :F], tc, segs, ACT_RELU))
+        return _out_convs(plan, head, tower, segs, F, ncls, reg_gate=(coef[:, 0, F:], coef[:, 1, F:], ACT_RELU))
+    _fused_gn(plan, "head.tower_gn", tower, segs, tgn, ACT_RELU)
     return _out_convs(plan, head, tower, segs, F, ncls)
 
 

@@ -12,7 +12,6 @@ import json
 import math
 import os
 import re
-import sys
 from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -328,16 +327,8 @@ def wino4_sk_choice(run, key: str, ws: torch.Tensor, reps: int = 5) -> int:
     if _TUNE_MODE == "0":
         return 0
     best, best_t = 0, float("inf")
-    trace = os.environ.get("FD_W4_SK_TRACE")
     for wgs in (0, 256, 240):
         call = conv_sk(run, wgs, ws) if wgs else run
-        if trace:
-            p_ = run.params
-            print(f"[w4sk] {key} sk_wgs {wgs} x_cs {p_.x_cs} x_co {p_.x_co} y_cs {p_.y_cs} y_co {p_.y_co} res {bool(p_.res)} act {p_.act} tag {p_.tag} ksplit {p_.ksplit} "
-                  f"wg_count {p_.wg_count}", file=sys.stderr, flush=True)
-            call()
-            torch.cuda.synchronize()
-            print("[w4sk]   ok", file=sys.stderr, flush=True)
         try:
             call()
         except FdError as e:
@@ -535,8 +526,8 @@ def autotune_conv(run: Callable[[], None], key: str, M: int, Cout: int, KT: int,
         """Install a table / heuristic / timed code on the launch and return the code ACTUALLY applied (what plan.tiles records)."""
         tile, ks = tile_split(code)
         if tile == _lib.WAVE_TILE and not p.w_frag:
-            # the key does not say whether the caller packed the weights in MFMA fragment order (train_ops._conv_launch never does, plans built
-            # with FD_WAVE_TILE=0 neither): the wave-autonomous tile is then not available -- fall back to the library's heuristic tile
+            # the key does not say whether the caller packed the weights in MFMA fragment order (train_ops._conv_launch never does, nor
+            # does add_conv for a layer whose shape or epilogue rules the tile out): the wave-autonomous tile is then not available -- fall back to the library's heuristic tile
             tile, ks = 0, 1
         if ks > 1 and (not p.workspace or p.gn_stats):        # (split-K needs the scratch; a row-statistics epilogue has no combine launch)
             ks = 1
@@ -721,7 +712,6 @@ def pack_conv_weight_wino4(w: torch.Tensor, scale: Optional[torch.Tensor] = None
     return WFormat.WINO4.pack(w, scale, dgrad)
 
 
-NARROW = os.environ.get("FD_NARROW", "1") != "0"     # "0": layers of <= 8 output channels stay on the Winograd / direct MFMA kernels
 NARROW_MIN_TILES = 128     # below this many 16 x 16 tiles (batch-1 plans) the MFMA kernels' split-K forms are the lower-latency choice
 
 
@@ -863,7 +853,7 @@ def choose_conv(segs: Segs, Cin: int, Cout: int, k: int, stride: int, pad: int, 
         return ConvChoice(amp_format(Cin, Cout), 1, _lib.PREC_F16)
     exact = arith in ("f32", "mixed")
     # <= 8 output channels (the centre-ness / box predictor): the vector-unit kernel where the map has enough tiles to fill the chip
-    if (exact and narrow and NARROW and not res and (not gate or gate_b) and not gn_stats and narrow_ok(Cin, Cout, k, stride, pad, dil)
+    if (exact and narrow and not res and (not gate or gate_b) and not gn_stats and narrow_ok(Cin, Cout, k, stride, pad, dil)
             and narrow_tiles(segs) >= NARROW_MIN_TILES):
         return ConvChoice(WFormat.NARROW, 1, _lib.PREC_F32)
     if exact and WINO_MODE != "0" and aligned and wino_ok(Cin, Cout, k, stride, pad, dil):

@@ -181,7 +181,7 @@ def test_abi_argument_errors_without_gpu():
 def test_winograd4_grid_queries_without_gpu():
     """fd_conv_workgroups / fd_conv_workgroups_live are host arithmetic: the HISFCOS head tower at 16 x 640 x 640 (256 -> 512 over 80 / 40 / 20 / 10 / 5) is
     8 608 tiles = 269 M tiles x 8 cout tiles = 2 152 workgroups in a grid of 2 176 (eight XCD shares of 34 M tiles); its first 2 048 workgroups -- 8 whole
-    rounds on 256 CUs, what engine.TOWER_TAIL_SPLIT launches as the main launch -- hold 2 040 of them."""
+    rounds on 256 CUs, what engine.add_conv launches as the main launch -- hold 2 040 of them."""
     lib = _lib.lib()
     p = _lib.ConvParams()
     p.segs = _lib.Segs.make(16, [(80, 80), (40, 40), (20, 20), (10, 10), (5, 5)])
@@ -359,7 +359,7 @@ _CHOICES_B1_512 = """
 def test_conv_chooser_pins_the_shipped_plans(batch, table, monkeypatch):
     """ops.choose_conv is a pure function of the layer geometry and what the caller offers: it gives every layer of the bench plan (16 x 640^2) and of the
     latency plan (1 x 512^2) the kernel family, weight format and Winograd split-K factor those plans ran before the chooser existed."""
-    for name, v in (("WINO_MODE", "1"), ("WINO4_MODE", "1"), ("NARROW", True)):
+    for name, v in (("WINO_MODE", "1"), ("WINO4_MODE", "1")):
         monkeypatch.setattr(ops, name, v)
     n = 0
     for item in table.replace("\n", " | ").split("|"):
@@ -378,7 +378,7 @@ def test_conv_chooser_pins_the_shipped_plans(batch, table, monkeypatch):
 
 def test_tile_table_wave_entry_is_demoted_without_fragment_packed_weights(monkeypatch):
     """the committed tile table holds an FD_TILE_WAVE64 entry whose key does not say whether the caller packed its weights in MFMA
-    fragment order (fd_conv_params.w_frag).  train_ops._conv_launch never does and plans built with FD_WAVE_TILE=0 do not either: the table
+    fragment order (fd_conv_params.w_frag).  train_ops._conv_launch never does, nor does a plan layer whose shape or epilogue rules the wave tile out: the table
     entry -- also through the nearest-batch transfer -- must then come out as the heuristic tile, not as a launch the library refuses."""
     key = "B16|208x336|32>192|k1s1p0d1|res0|xcs32|ycs192"
     monkeypatch.setattr(ops, "_TUNE_MODE", "0")

@@ -1490,7 +1490,7 @@ def test_conv3x3_winograd_f4x4_at_the_start_of_an_allocation():
 @pytest.mark.parametrize("case", [(64, 128, [(40, 40), (20, 20), (10, 10), (5, 5), (3, 3)], 3, 1), (32, 80, [(48, 36)], 2, 2), (64, 64, [(24, 20)], 1, 1)])
 def test_conv3x3_winograd_f4x4_as_slices_of_its_grid(case):
     """fd_conv_params.wg_first / wg_count: an F(4x4) layer launched as several slices of its workgroup grid (the head tower as whole rounds on 256 CUs + a
-    tail launch, engine.TOWER_TAIL_SPLIT).  Any partition of [0, fd_conv_workgroups) at multiples of 8 must give, BIT FOR BIT, the one-launch result, every
+    tail launch, engine.add_conv).  Any partition of [0, fd_conv_workgroups) at multiples of 8 must give, BIT FOR BIT, the one-launch result, every
     slice must write only its own tiles, the non-empty workgroup counts of the slices must add up, and ranges outside the grid / off an XCD boundary /
     on another tile are clean errors."""
     from pytorch_object_detection_amd import _lib
