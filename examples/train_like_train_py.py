@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's train.py:97-181 loop on the MI355X path, with synthetic VOC-shaped batches.
 
-    python examples/train_like_train_py.py [--steps 20] [--amp]
+    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_like_train_py.py   # DDP / RCCL
 
 Same objects and call order as the reference: HalfInvertedStageFCOS([512, 1024, 2048], 20, 256), FCOSGenTargets,
@@ -9,6 +9,8 @@ FCOSLoss('giou'), SGD, DistributedDataParallel(find_unused_parameters=True), aut
 In model.train() the forward is an autograd graph of HIP kernels (train_ops.py); target assignment and the losses are HIP
 kernels; under autocast the dense convolutions run on the f16 MFMA with fp32 accumulation (forward, data and weight gradients:
 the reference's AMP arithmetic), normalisation and losses in fp32; under DDP the FPN's BatchNorms are SyncBatchNorm on the HIP statistics path.
+--model MNFCOS (what the reference's config/main.yaml selects) builds MNFCOS([2048, 1024, 512], 20, 256) and opts in to its HIP training nodes
+with model.enable_training() (which also freezes the Cin = 3 stem: the optimizer is built after it).
 """
 import argparse
 import os
@@ -21,7 +23,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_object_detection_amd.model.loss import FCOSLoss  # noqa: E402
 from pytorch_object_detection_amd.model.modules.head import FCOSGenTargets  # noqa: E402
-from pytorch_object_detection_amd.model.od import HalfInvertedStageFCOS  # noqa: E402
+from pytorch_object_detection_amd.model.od import MNFCOS, HalfInvertedStageFCOS  # noqa: E402
 
 
 def main():
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--amp", action="store_true")
+    ap.add_argument("--model", choices=["HISFCOS", "MNFCOS"], default="HISFCOS")
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
     torch.cuda.set_device(local)
@@ -38,7 +41,10 @@ def main():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
     torch.manual_seed(0)
-    model = HalfInvertedStageFCOS([512, 1024, 2048], 20, 256).to(dev)                               # train.py:97
+    if args.model == "MNFCOS":
+        model = MNFCOS([2048, 1024, 512], 20, 256).enable_training().to(dev)                        # config/main.yaml:2, mnfcos.yaml
+    else:
+        model = HalfInvertedStageFCOS([512, 1024, 2048], 20, 256).to(dev)                           # train.py:97
     gen_target = FCOSGenTargets(strides=[8, 16, 32, 64, 128],
                                 limit_range=[[-1, 64], [64, 128], [128, 256], [256, 512], [512, 999999]])   # train.py:98
     if world > 1:

@@ -387,6 +387,17 @@ int32_t fd_dwconv_dilated_nhwc(const float* x, int32_t x_cs, int32_t x_co, const
                                float* y, int32_t y_cs, int32_t y_co, int32_t C, int32_t K, int32_t dil, int32_t act,
                                const fd_segs* segs, fd_stream_t stream);
 
+/* Weight gradient of the dilated depthwise conv above: dw[t][c] = sum_m x[pix(m, t; dil)][c] * dy[m][c], t = K*r + q, over every level of the
+ * segment table; k in {3, 5, 7}, 1 <= dil <= 8, C % 4 == 0.  layout 0 = [K*K][C] (the layout of `w`), 1 = torch's [C][1][K][K]; optional scale[C]
+ * multiplies the result per channel (a frozen BatchNorm folded into the forward).  The data gradient is fd_dwconv_dilated_nhwc itself with the taps
+ * reversed (w'[t] = w[K*K-1-t]: k is odd, the padding symmetric).  The backward of MNBlock.DilatedDepthWiseConv (modules.py:195-216) in the reference's
+ * train step (train.py:175-181).  Deterministic: fixed row partition, fixed-order fp64 final sum of the chunk partials.  Allocates nothing:
+ * workspace = fd_dwconv_dilated_wgrad_workspace_bytes(segs, C, K) bytes, 16-byte aligned (-1: bad table, C or K). */
+int64_t fd_dwconv_dilated_wgrad_workspace_bytes(const fd_segs* segs, int32_t C, int32_t K);
+int32_t fd_dwconv_dilated_bwd_weight_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co,
+                                          float* dw, int32_t C, int32_t K, int32_t dil, const float* scale, int32_t layout,
+                                          const fd_segs* segs, void* workspace, fd_stream_t stream);
+
 /* Depthwise k x k convolution with stride and asymmetric zero padding, y = act(dw(x)*scale + shift): the depthwise
  * stage of an EfficientNet MBConv block (efficientnet_pytorch 0.7.1 MBConvBlock._depthwise_conv + _bn1 + swish, wrapped by
  * the reference's model/backbone/efficientnetv1.py:11-26; Conv2dStaticSamePadding pads (pad//2, pad - pad//2), i.e. more at

@@ -154,6 +154,8 @@ _SIGS = {
     "fd_jitter_l_sums": (_I, [_P, _P, _P, _I, _L, _P]),
     "fd_color_jitter_u8": (_I, [_P, _I, _I, _P, _P, _P]),
     "fd_rotate_u8": (_I, [_P, _I, _I, _P, C.POINTER(_I), _P]),
+    "fd_dwconv_dilated_wgrad_workspace_bytes": (_L, [C.POINTER(Segs), _I, _I]),
+    "fd_dwconv_dilated_bwd_weight_nhwc": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _P, _I, C.POINTER(Segs), _P, _P]),
     "fd_dwconv3x3_wgrad_workspace_bytes": (_L, [C.POINTER(Segs), _I]),
     "fd_dwconv3x3_bwd_weight_nhwc": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _I, C.POINTER(Segs), _P, _P]),
     "fd_groupnorm_workspace_bytes": (_L, [C.POINTER(Segs), _I]),

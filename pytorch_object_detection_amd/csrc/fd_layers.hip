@@ -673,9 +673,9 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_partial_kernel(const floa
     }
 }
 
-__global__ __launch_bounds__(256) void dwconv3x3_wgrad_final_kernel(const float* __restrict__ part, float* __restrict__ dw,
+__global__ __launch_bounds__(256) void dw_wgrad_final_kernel(const float* __restrict__ part, float* __restrict__ dw,
                                                                      int n, int nchunk, const float* __restrict__ scale,
-                                                                     int layout, int C) {
+                                                                     int layout, int C, int T) {
     // 16 outputs x 16 chunk lanes per workgroup: lane j adds chunks j, j+16, ... in order, lanes are combined in order
     __shared__ double red[256];
     const int o = threadIdx.x & 15, j = threadIdx.x >> 4;
@@ -691,7 +691,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_final_kernel(const float*
         const int tap = i / C, c = i - tap * C;
         float v = (float)t;
         if (scale) v *= scale[c];
-        dw[layout ? c * 9 + tap : i] = v;
+        dw[layout ? c * T + tap : i] = v;
     }
 }
 
@@ -724,9 +724,106 @@ extern "C" int32_t fd_dwconv3x3_bwd_weight_nhwc(const float* x, int32_t x_cs, in
     hipLaunchKernelGGL(dwconv3x3_wgrad_partial_kernel, dim3(nchunk, C4 / QW), dim3(256), 0, (hipStream_t)stream, x, x_cs, x_co,
                        dy, dy_cs, dy_co, C, QW, chunk_rows, tab, (float*)workspace);
     FD_CHECK_LAUNCH("fd_dwconv3x3_bwd_weight_nhwc (partial)");
-    hipLaunchKernelGGL(dwconv3x3_wgrad_final_kernel, dim3((9 * C + 15) / 16), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)workspace, dw, 9 * C, nchunk, scale, layout, C);
+    hipLaunchKernelGGL(dw_wgrad_final_kernel, dim3((9 * C + 15) / 16), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)workspace, dw, 9 * C, nchunk, scale, layout, C, 9);
     FD_CHECK_LAUNCH("fd_dwconv3x3_bwd_weight_nhwc (final)");
+    return FD_OK;
+}
+
+// ---- dilated depthwise k x k weight gradient (k in {3, 5, 7}, stride 1, 'same' padding, any pyramid): dw[t][c] = sum_m x[pix(m, t; dil)][c] * dy[m][c],
+// t = r * K + q -- the weight gradient of dwconv_dilated_kernel (its data gradient is that kernel itself with the taps reversed: k is odd and the padding
+// symmetric).  Same scheme as the 3x3 kernel above, but a thread cannot keep K * K = 49 float4 tap sums without cutting occupancy, so the taps are tiled by
+// KERNEL ROW: one workgroup = (row chunk, kernel row r), a thread owns one channel quad and every R-th row of the chunk and keeps the K tap sums of row r
+// (at most 7 float4).  The K workgroups of a chunk read the same dy rows and overlapping x rows; their block ids are congruent mod 8 so that they tend to
+// share an L2 (a speed hint only: the result does not depend on where a workgroup runs).  partial[chunk][K*K][C], then dw_wgrad_final_kernel.
+template <int K>
+__global__ __launch_bounds__(256) void dwconv_dilated_wgrad_partial_kernel(const float* __restrict__ x, int x_cs, int x_co,
+                                                                            const float* __restrict__ dy, int dy_cs, int dy_co,
+                                                                            int C, int QW, int dil, long chunk_rows, int nchunk, SegTab tab,
+                                                                            float* __restrict__ part) {
+    __shared__ float4 red[256];
+    const int id = blockIdx.x;
+    const int r = (id >> 3) % K;                                 // kernel row of this workgroup
+    const int chunk = ((id >> 3) / K) * 8 + (id & 7);
+    if (chunk >= nchunk) return;                                 // (the grid is rounded up to 8 chunks; uniform per workgroup)
+    const int tid = threadIdx.x;
+    const int R = 256 / QW;                                      // row lanes
+    const int ql = tid % QW, rl = tid / QW;
+    const int q = blockIdx.y * QW + ql;                          // channel quad
+    const bool live = 4 * q < C;
+    const long rows = tab.s.m_start[tab.s.nseg];
+    const long m0 = (long)chunk * chunk_rows;
+    const long m1 = min(rows, m0 + chunk_rows);
+    constexpr int half = (K - 1) / 2;
+    float4 acc[K];
+#pragma unroll
+    for (int c = 0; c < K; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live)
+        for (long m = m0 + rl; m < m1; m += R) {
+            int H, W, h, w;
+            long r0;
+            seg_decode(tab.s, m, H, W, r0, h, w);
+            const int hi = h + (r - half) * dil;
+            if ((unsigned)hi >= (unsigned)H) continue;
+            const float4 g = *reinterpret_cast<const float4*>(dy + m * dy_cs + dy_co + 4 * q);
+            const float* xrow = x + (r0 + (long)hi * W) * x_cs + x_co + 4 * q;
+#pragma unroll
+            for (int c = 0; c < K; ++c) {
+                const int wi = w + (c - half) * dil;
+                if ((unsigned)wi >= (unsigned)W) continue;
+                const float4 u = *reinterpret_cast<const float4*>(xrow + (long)wi * x_cs);
+                float4& a = acc[c];
+                a.x = fmaf(u.x, g.x, a.x); a.y = fmaf(u.y, g.y, a.y);
+                a.z = fmaf(u.z, g.z, a.z); a.w = fmaf(u.w, g.w, a.w);
+            }
+        }
+#pragma unroll
+    for (int c = 0; c < K; ++c) {
+        red[tid] = acc[c];
+        __syncthreads();
+        if (rl == 0 && live) {
+            float4 v = red[ql];
+            for (int j = 1; j < R; ++j) {
+                const float4 u = red[j * QW + ql];
+                v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
+            }
+            *reinterpret_cast<float4*>(part + ((long)chunk * (K * K) + r * K + c) * C + 4 * q) = v;
+        }
+        __syncthreads();
+    }
+}
+
+extern "C" int64_t fd_dwconv_dilated_wgrad_workspace_bytes(const fd_segs* segs, int32_t C, int32_t K) {
+    if (!fd_segs_ok(segs) || C < 4 || C % 4 || !(K == 3 || K == 5 || K == 7)) return -1;
+    return (int64_t)dw_wgrad_chunks(segs->m_start[segs->nseg]) * K * K * C * 4;
+}
+
+extern "C" int32_t fd_dwconv_dilated_bwd_weight_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs,
+                                                     int32_t dy_co, float* dw, int32_t C, int32_t K, int32_t dil, const float* scale,
+                                                     int32_t layout, const fd_segs* segs, void* workspace, fd_stream_t stream) {
+    FD_REQUIRE(fd_segs_ok(segs), FD_E_INVAL, "fd_dwconv_dilated_bwd_weight: bad segment table");
+    FD_REQUIRE((K == 3 || K == 5 || K == 7) && dil >= 1 && dil <= 8, FD_E_UNSUPPORTED,
+               "fd_dwconv_dilated_bwd_weight: k in {3, 5, 7}, 1 <= dilation <= 8 (k=%d dil=%d)", K, dil);
+    FD_REQUIRE(view_ok(x, x_cs, x_co, C) && view_ok(dy, dy_cs, dy_co, C) && dw && workspace && ((uintptr_t)workspace & 15) == 0,
+               FD_E_INVAL, "fd_dwconv_dilated_bwd_weight: channel views must be 4-aligned, dw and a 16-byte aligned workspace given (C=%d)", C);
+    FD_REQUIRE(layout == 0 || layout == 1, FD_E_INVAL, "fd_dwconv_dilated_bwd_weight: layout 0 ([K*K][C]) or 1 ([C][1][K][K]) (got %d)", layout);
+    const int C4 = C / 4;
+    int QW = 1;                                              // channel quads per workgroup: a power of two <= 256 (the rest of the 256 threads are row lanes)
+    while (QW < C4 && QW < 256) QW *= 2;
+    const long rows = segs->m_start[segs->nseg];
+    const int nchunk = dw_wgrad_chunks(rows);
+    const long chunk_rows = (rows + nchunk - 1) / nchunk;
+    SegTab tab; tab.s = *segs;
+    const dim3 grid((nchunk + 7) / 8 * 8 * K, (C4 + QW - 1) / QW);
+#define FD_DWD_WGRAD(KK)                                                                                                              \
+    hipLaunchKernelGGL(dwconv_dilated_wgrad_partial_kernel<KK>, grid, dim3(256), 0, (hipStream_t)stream, x, x_cs, x_co, dy, dy_cs,   \
+                       dy_co, C, QW, dil, chunk_rows, nchunk, tab, (float*)workspace)
+    if (K == 3) FD_DWD_WGRAD(3); else if (K == 5) FD_DWD_WGRAD(5); else FD_DWD_WGRAD(7);
+#undef FD_DWD_WGRAD
+    FD_CHECK_LAUNCH("fd_dwconv_dilated_bwd_weight_nhwc (partial)");
+    hipLaunchKernelGGL(dw_wgrad_final_kernel, dim3((K * K * C + 15) / 16), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)workspace, dw, K * K * C, nchunk, scale, layout, C, K * K);
+    FD_CHECK_LAUNCH("fd_dwconv_dilated_bwd_weight_nhwc (final)");
     return FD_OK;
 }
 

@@ -97,7 +97,13 @@ class MNBlock(nn.Module):
     (model/od/MNFcos.py:222-297).  As shipped the reference pads the depthwise conv with `dilated`, which keeps the map size only for
     k = 3, so its own residual add raises for the k = 5 / 7 blocks; here the padding is 'same' (dilated * (kernel - 1) / 2): identical
     for k = 3, the evident intent for 5 / 7.  Inside a detector plan the block is three HIP launches (engine.add_mn_block); called on
-    its own (eval, no gradient) it runs the same launches."""
+    its own (eval, no gradient) it runs the same launches.
+
+    Training is opt-in: with `hip_train = True` (set by `enable_training()` of MNFCOS / its FPN / its head, or directly) a forward in
+    train() -- or one that wants a gradient -- builds an autograd graph of HIP rows nodes (train_ops.mn_block_rows: the dilated depthwise
+    conv with its data and weight gradient kernels, BatchNorm folded when frozen or on batch statistics, the two 1x1 convs, SiLU)."""
+
+    hip_train = False
 
     def __init__(self, in_ch: int, out_ch: int, kernel: int, dilated: int, alpha: int = 1):
         super().__init__()
@@ -112,7 +118,11 @@ class MNBlock(nn.Module):
         from ..._lib import Segs
         T._need_cuda(x)
         if self.training or (torch.is_grad_enabled() and (x.requires_grad or self.PW1.weight.requires_grad)):
-            raise FdError("MNBlock has a HIP forward only (MNFCOS is inference-only on the HIP path): call .eval() and run it under torch.no_grad()")
+            if not self.hip_train:
+                raise FdError("MNBlock has a HIP forward only (MNFCOS is inference-only on the HIP path): call .eval() and run it under torch.no_grad(), "
+                              "or opt in to the HIP training nodes with hip_train = True (MNFCOS.enable_training())")
+            B, C, H, W = x.shape
+            return T.from_rows(T.mn_block_rows(self, T.to_rows(x), Segs.make(B, [(H, W)])), B, H, W)
         if x.dtype != torch.float32 or x.shape[1] % 4 or self.PW2.weight.shape[0] != x.shape[1]:
             raise FdError("MNBlock: fp32 input with C % 4 == 0 and out_ch == in_ch (the residual add) expected")
         B, C, H, W = x.shape

@@ -1322,6 +1322,32 @@ def dwconv3x3_wgrad(x: Rows, dy: Rows, segs: Segs, scale: Optional[torch.Tensor]
     return dw
 
 
+def pack_dwk_weight_reversed(w: torch.Tensor, scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[C,1,K,K] -> [K*K][C] with the taps reversed (and scaled per channel): the weights with which a stride-1 'same' depthwise conv -- odd K, symmetric
+    padding -- computes its own data gradient (dx = dw(dy, w'), w'[t] = w[K*K-1-t] * scale)."""
+    w = w.detach().float()
+    if scale is not None:
+        w = w * scale.view(-1, 1, 1, 1)
+    return w.flip(2, 3).reshape(w.shape[0], -1).t().contiguous()
+
+
+def dwconv_dilated_wgrad(x: Rows, dy: Rows, segs: Segs, K: int, dil: int, scale: Optional[torch.Tensor] = None,
+                         torch_layout: bool = False) -> torch.Tensor:
+    """Weight gradient of the dilated depthwise K x K conv (stride 1, 'same' padding, over a pyramid) given dy: [K*K][C], or [C][1][K][K] with
+    torch_layout; `scale` multiplies it per channel (a frozen BatchNorm folded into the forward).  Deterministic; two launches, no host sync."""
+    dev = x.buf.device
+    _need_gpu(x.buf, dy.buf, scale)
+    nb = _lib.lib().fd_dwconv_dilated_wgrad_workspace_bytes(C.byref(segs), x.C, K)
+    if nb < 0:
+        raise FdError(f"fd_dwconv_dilated_wgrad_workspace_bytes: bad arguments (C={x.C}, K={K})")
+    ws = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+    dw = torch.empty((x.C, 1, K, K) if torch_layout else (K * K, x.C), dtype=torch.float32, device=dev)
+    check(_lib.lib().fd_dwconv_dilated_bwd_weight_nhwc(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, dw.data_ptr(), x.C, K, dil,
+                                                       scale.data_ptr() if scale is not None else None, 1 if torch_layout else 0,
+                                                       C.byref(segs), ws.data_ptr(), _stream()), "fd_dwconv_dilated_bwd_weight_nhwc")
+    return dw
+
+
 def groupnorm_workspace(segs: Segs, G: int, device) -> torch.Tensor:
     n = _lib.lib().fd_groupnorm_workspace_bytes(C.byref(segs), G)
     if n < 0:

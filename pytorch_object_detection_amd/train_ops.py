@@ -10,6 +10,8 @@ over the whole pyramid exactly as at inference.
                             elementwise pass from the saved output), data gradient = the same conv kernel on dY with
                             flipped / transposed weights (stride-1 layers), weight gradient = fd_conv2d_bwd_weight_f32.
   dw_rows                   depthwise 3x3: fd_dwconv3x3_nhwc forward and data gradient, fd_dwconv3x3_bwd_weight_nhwc.
+  dw_dilated_rows           dilated depthwise k x k (MNBlock): fd_dwconv_dilated_nhwc forward and data gradient, fd_dwconv_dilated_bwd_weight_nhwc;
+                            mn_block_rows = the whole MNBlock (depthwise, BatchNorm frozen or on batch statistics, PW1 + SiLU, PW2 + residual).
   groupnorm_rows            GroupNorm + ReLU / SiLU: fd_groupnorm_act_nhwc / fd_groupnorm_act_bwd_nhwc.
 
 What the kernels do not cover falls back to stock PyTorch-ROCm ops on the GPU: the data gradient of strided layers,
@@ -612,6 +614,79 @@ def dw_rows(m: nn.Conv2d, x: torch.Tensor, segs: Segs, bn: Optional[nn.Module] =
     if bn is not None:
         scale, shift = _bn_fold(bn)
     return _DwRows.apply(x, m.weight, scale, shift, segs, act)
+
+
+# ------------------------------------------------------------------------- dilated depthwise k x k (MNBlock)
+def _dw_dilated_ok(m: nn.Conv2d, x: torch.Tensor) -> bool:
+    k, d = m.kernel_size[0], m.dilation[0]
+    return (m.groups == m.in_channels == m.out_channels and m.in_channels % 4 == 0 and _square(m) and k in (3, 5, 7) and 1 <= d <= 8
+            and m.stride == (1, 1) and _pad_of(m) == d * (k - 1) // 2 and m.bias is None and _f32(x) and m.weight.dtype == torch.float32)
+
+
+class _DwDilatedRows(torch.autograd.Function):
+    """Dilated depthwise k x k (k in {3, 5, 7}, stride 1, 'same' padding, no bias) over a pyramid: y = dw(x, w) * scale + shift, scale / shift
+    constants (a frozen BatchNorm).  Data gradient: the forward launch on dy with reversed, scaled taps (k odd, padding symmetric: exact); weight
+    gradient: fd_dwconv_dilated_bwd_weight_nhwc.  fp32 under autocast, like the 3x3 depthwise node."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, weight, scale, shift, segs, K, dil):
+        x = x.contiguous()
+        y = torch.empty_like(x)
+        ops.dwconv_dilated(_r(x), ops.pack_dwk_weight(weight), _r(y), segs, K, dil, scale, shift, ACT_NONE)
+        ctx.save_for_backward(x, weight, scale)
+        ctx.geom = (segs, K, dil)
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        x, weight, scale = ctx.saved_tensors
+        segs, K, dil = ctx.geom
+        g = resolve_pending(gy).contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            ops.dwconv_dilated(_r(g), ops.pack_dwk_weight_reversed(weight, scale), _r(gx), segs, K, dil)
+        if ctx.needs_input_grad[1]:
+            gw = ops.dwconv_dilated_wgrad(_r(x), _r(g), segs, K, dil, scale, torch_layout=True)
+        return gx, gw, None, None, None, None, None
+
+
+def dw_dilated_rows(m: nn.Conv2d, x: torch.Tensor, segs: Segs, bn: Optional[nn.Module] = None) -> torch.Tensor:
+    """bn(m(x)) on a rows buffer for a dilated depthwise conv `m` and a FROZEN BatchNorm (folded into scale / shift), or m(x) with bn=None."""
+    if not _dw_dilated_ok(m, x):
+        raise FdError(f"dilated depthwise conv {tuple(m.weight.shape)} dilation {m.dilation} padding {m.padding}: the HIP kernels cover "
+                      "k in {3, 5, 7}, stride 1, 'same' padding, 1 <= dilation <= 8, C % 4 == 0, no bias, fp32")
+    scale = shift = None
+    if bn is not None:
+        scale, shift = _bn_fold(bn)
+    return _DwDilatedRows.apply(x, m.weight, scale, shift, segs, m.kernel_size[0], m.dilation[0])
+
+
+def mn_block_rows(blk: nn.Module, x: torch.Tensor, segs: Segs) -> torch.Tensor:
+    """MNBlock (modules.py:195-216) on NHWC rows -- one level or a whole pyramid -- with every op a differentiable HIP node:
+    x + PW2(SiLU(PW1(BN(dilated depthwise(x))))).  A frozen BatchNorm folds into the depthwise launch.  One in training mode runs on batch statistics
+    (batchnorm_train_rows), PER LEVEL on slices of the rows when `segs` holds a pyramid: the reference calls a shared block once per level
+    (MNFcos.py:285-297), so the statistics are per level and the running statistics move once per level, in level order."""
+    dw, bn = blk.DilatedDepthWiseConv, blk.BN
+    if not (_dense_ok(blk.PW1, x) and _dense_ok(blk.PW2, x) and blk.PW1.out_channels % 32 == 0 and blk.PW2.out_channels == x.shape[1]
+            and blk.PW1.kernel_size == (1, 1) and blk.PW2.kernel_size == (1, 1) and isinstance(blk.ACT1, nn.SiLU)):
+        raise FdError("MNBlock: the HIP training nodes cover fp32 1x1 convs with C % 32 == 0 and out_ch == in_ch (the residual add)")
+    if bn_is_frozen(bn):
+        t = dw_dilated_rows(dw, x, segs, bn)
+    elif _bn_train_ok(bn, x):
+        t = dw_dilated_rows(dw, x, segs)
+        if segs.nseg == 1:
+            t = batchnorm_train_rows(bn, t)
+        else:
+            per_level = t.split([segs.m_start[i + 1] - segs.m_start[i] for i in range(segs.nseg)], 0)
+            t = torch.cat([batchnorm_train_rows(bn, u) for u in per_level], 0)
+    else:
+        raise FdError(f"MNBlock.BN ({type(bn).__name__}, training={bn.training}): the HIP nodes cover a frozen BatchNorm2d or one in training mode "
+                      "with affine parameters, running statistics and C / 4 dividing 256")
+    h = act_rows(conv_rows(blk.PW1, t, segs), ACT_SILU)
+    return conv_rows(blk.PW2, h, segs, residual=x)
 
 
 # --------------------------------------------------------------------------------------- GroupNorm + activation
