@@ -825,6 +825,58 @@ int32_t fd_fcos_gen_targets(const float* gt_boxes, const int64_t* labels, int32_
                             const int32_t* strides, const int32_t* range_lo, const int32_t* range_hi, float radius_ratio,
                             int64_t* cls_target, float* cnt_target, float* reg_target, fd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------- */
+/* Anchor targets and detections (DataEncoder.encode / decode, utill/utills.py:100-199).
+ *
+ * fd_anchor_params describes the anchor set of one input size; the HOST fills it (DataEncoder._anchor_params of the Python
+ * package) and every kernel derives its anchors from the row index -- no anchor table is read from memory:
+ *   fm_w / fm_h [level]    feature-map size ceil(input / 2^(level+3)), >= 1
+ *   grid_w / grid_h        fp32 input / fm (NOT the stride: 100 / 13 = 7.69... at level 0)
+ *   wh [level][k][2]       the 9 (w, h) pairs of the level, computed in doubles and rounded once to fp32
+ *   num_anchors            A = 9 * sum fm_w * fm_h, checked against the `A` argument of every call
+ * Row order: level, y, x, k.  Anchor row = (cx, cy, w, h) with cx = ((float)x + 0.5f) * grid_w, cy alike. */
+#define FD_ANCHOR_LEVELS 5
+#define FD_ANCHOR_PER_CELL 9
+#define FD_ANCHOR_MAX_GT 256      /* fd_anchor_encode: ground-truth rows per image, padding included */
+#define FD_ANCHOR_MAX_CLASSES 128 /* fd_anchor_decode */
+#define FD_ANCHOR_MAX_CAND 1024   /* fd_anchor_decode: max_candidates (the limit of fd_box_nms_plus1) */
+typedef struct fd_anchor_params {
+    int32_t fm_w[FD_ANCHOR_LEVELS];
+    int32_t fm_h[FD_ANCHOR_LEVELS];
+    float grid_w[FD_ANCHOR_LEVELS];
+    float grid_h[FD_ANCHOR_LEVELS];
+    float wh[FD_ANCHOR_LEVELS][FD_ANCHOR_PER_CELL][2];
+    int32_t num_anchors;
+} fd_anchor_params;
+
+/* anchors [A][4] = (cx, cy, w, h), 16-byte aligned (DataEncoder._get_anchor_boxes, bit for bit). */
+int32_t fd_anchor_boxes(const fd_anchor_params* p, float* anchors, int32_t A, fd_stream_t stream);
+
+/* DataEncoder.encode for B images in one launch.  gt [B][M][4] xyxy fp32 (16-byte aligned), labels [B][M] int64; a row
+ * with label < 0 is padding (the convention of fd_fcos_gen_targets); 0 <= M <= FD_ANCHOR_MAX_GT (FD_E_UNSUPPORTED above;
+ * gt / labels may be NULL when M == 0).  Outputs loc [B][A][4] fp32 (16-byte aligned), cls [B][A] int64.  Per anchor, fp32
+ * without FMA contraction: each box becomes (centre, b - a + 1), both sides go back to corners as c -/+ wh/2, IoU with the
+ * "+1" convention exactly as fd_pairwise_iou(plus_one = 1), first maximum over the image's boxes in row order;
+ * loc = ((gt_xy - a_xy) / a_wh, log(gt_wh / a_wh)); cls = 1 + label, 0 where max_iou < 0.5, then -1 where
+ * 0.4f < max_iou < 0.5.  An image without a valid box gets cls = 0, loc = 0 (the reference raises). */
+int32_t fd_anchor_encode(const fd_anchor_params* p, const float* gt, const int64_t* labels, int32_t B, int32_t M, int32_t A,
+                         float* loc, int64_t* cls, fd_stream_t stream);
+
+/* DataEncoder.decode for B images.  loc [B][A][4] fp32 (16-byte aligned), cls [B][A][C] fp32 logits, 1 <= C <=
+ * FD_ANCHOR_MAX_CLASSES (float4 loads when C % 4 == 0 and cls is 16-byte aligned, scalar loads otherwise).  Per anchor:
+ * xy = loc_xy * a_wh + a_xy, wh = exp(loc_wh) * a_wh, box = xy -/+ wh / 2; score, label = first maximum over the fp32
+ * SIGMOID values (not over the logits: saturated logits tie at 1.0f and the lowest class wins); candidate when
+ * score > cls_thresh.  The top K = min(max_candidates, A) candidates by score (ties: lower anchor row first;
+ * 1 <= max_candidates <= FD_ANCHOR_MAX_CAND) go through fd_box_nms_plus1(nms_thresh, 'union').  Outputs, all [B][K] and
+ * score-descending: boxes [B][K][4] xyxy (16-byte aligned), labels int64 (0-based; -1 in the padding), scores; counts [B]
+ * int32 = rows kept; n_candidates [B] int32 = anchors that passed cls_thresh (> K: the image was truncated to the K best).
+ * workspace: fd_anchor_decode_workspace_bytes(B, A, max_candidates) bytes (-1: bad arguments), 256-byte aligned.
+ * Five launches and one memset on `stream`, no host synchronisation. */
+int64_t fd_anchor_decode_workspace_bytes(int32_t B, int32_t A, int32_t max_candidates);
+int32_t fd_anchor_decode(const fd_anchor_params* p, const float* loc, const float* cls, int32_t B, int32_t A, int32_t C,
+                         float cls_thresh, float nms_thresh, int32_t max_candidates, float* boxes, int64_t* labels,
+                         float* scores, int32_t* counts, int32_t* n_candidates, void* workspace, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,14 @@ class WgradParams(C.Structure):
                 ("scale", C.c_void_p), ("segs", Segs), ("precision", C.c_int32), ("io_f16", C.c_int32)]
 
 
+class AnchorParams(C.Structure):
+    """fd_anchor_params (include/fcosdet.h): the anchor set of one input size, filled by the host (utill.utills.DataEncoder)."""
+    _fields_ = [("fm_w", C.c_int32 * 5), ("fm_h", C.c_int32 * 5), ("grid_w", C.c_float * 5), ("grid_h", C.c_float * 5),
+                ("wh", C.c_float * 2 * 9 * 5), ("num_anchors", C.c_int32)]
+
+
+ANCHOR_MAX_GT, ANCHOR_MAX_CLASSES, ANCHOR_MAX_CAND = 256, 128, 1024     # include/fcosdet.h FD_ANCHOR_MAX_*
+
 _lib = None
 
 _P, _I, _F, _D, _L = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_int64
@@ -204,6 +212,10 @@ _SIGS = {
     "fd_eval_coco": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, C.POINTER(_D), _I, C.POINTER(_D), _I, C.POINTER(_D), _I,
                           C.POINTER(_I), _I, _P, _P, _P, _P, _P]),
     "fd_fcos_gen_targets": (_I, [_P, _P, _I, C.POINTER(Segs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _F, _P, _P, _P, _P]),
+    "fd_anchor_boxes": (_I, [C.POINTER(AnchorParams), _P, _I, _P]),
+    "fd_anchor_encode": (_I, [C.POINTER(AnchorParams), _P, _P, _I, _I, _I, _P, _P, _P]),
+    "fd_anchor_decode_workspace_bytes": (_L, [_I, _I, _I]),
+    "fd_anchor_decode": (_I, [C.POINTER(AnchorParams), _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

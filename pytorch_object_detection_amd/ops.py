@@ -1711,6 +1711,99 @@ def fcos_gen_targets(gt_boxes: torch.Tensor, labels: torch.Tensor, level_hw, str
     return cls, cnt, reg
 
 
+# ---------------------------------------------------------------------------------------------------- anchors (DataEncoder)
+ANCHOR_LEVELS, ANCHOR_PER_CELL = 5, 9
+
+
+def anchor_params(input_size, anchor_wh) -> _lib.AnchorParams:
+    """fd_anchor_params of one input size: `input_size` an int or (w, h); `anchor_wh` [5, 9, 2] (w, h) pairs, rounded here to
+    fp32.  fm = ceil(input / 2^(level + 3)) and grid = input / fm in fp32, the reference's tensors (utills.py:121-130)."""
+    wh = np.asarray(anchor_wh.detach().cpu().numpy() if isinstance(anchor_wh, torch.Tensor) else anchor_wh, dtype=np.float64).astype(np.float32)
+    if wh.shape != (ANCHOR_LEVELS, ANCHOR_PER_CELL, 2) or not np.isfinite(wh).all() or not (wh > 0).all():
+        raise FdError(f"anchor_params: anchor_wh must be [5, 9, 2], finite and > 0 (got shape {wh.shape})")
+    if isinstance(input_size, torch.Tensor):
+        input_size = input_size.tolist()
+    size = np.array([input_size, input_size] if isinstance(input_size, (int, float)) else list(input_size), dtype=np.float32)
+    if size.shape != (2,) or not np.isfinite(size).all() or not (size >= 1).all():
+        raise FdError(f"anchor_params: input_size must be an int or (w, h) with sides >= 1 (got {input_size!r})")
+    p = _lib.AnchorParams()
+    total = 0
+    for i in range(ANCHOR_LEVELS):
+        fm = np.ceil(size / np.float32(2.0 ** (i + 3)))
+        grid = size / fm
+        p.fm_w[i], p.fm_h[i] = int(fm[0]), int(fm[1])
+        p.grid_w[i], p.grid_h[i] = float(grid[0]), float(grid[1])
+        for k in range(ANCHOR_PER_CELL):
+            p.wh[i][k][0], p.wh[i][k][1] = float(wh[i, k, 0]), float(wh[i, k, 1])
+        total += ANCHOR_PER_CELL * int(fm[0]) * int(fm[1])
+    if total >= 1 << 28:
+        raise FdError(f"anchor_params: {total} anchors (limit 2^28)")
+    p.num_anchors = total
+    return p
+
+
+def _need_f32(what: str, **ts) -> None:
+    for name, t in ts.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise FdError(f"{what}: {name} must be a contiguous fp32 tensor")
+
+
+def anchor_boxes(params: _lib.AnchorParams, device) -> torch.Tensor:
+    """-> anchors [A, 4] fp32 (cx, cy, w, h), DataEncoder._get_anchor_boxes bit for bit."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise FdError("anchor_boxes runs on the GPU only; there is no CPU fallback")
+    out = torch.empty(params.num_anchors, 4, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        check(_lib.lib().fd_anchor_boxes(C.byref(params), out.data_ptr(), params.num_anchors, _stream()), "fd_anchor_boxes")
+    return out
+
+
+def anchor_encode(params: _lib.AnchorParams, gt_boxes: torch.Tensor, labels: torch.Tensor):
+    """gt_boxes [B, M, 4] fp32 xyxy, labels [B, M] int64 (< 0 = padding) -> (loc [B, A, 4] fp32, cls [B, A] int64): fd_anchor_encode."""
+    _need_gpu(gt_boxes, labels)
+    _need_f32("anchor_encode", gt_boxes=gt_boxes)
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or not labels.is_contiguous():
+        raise FdError("anchor_encode: labels must be a contiguous int64 tensor")
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4 or tuple(labels.shape) != tuple(gt_boxes.shape[:2]) or gt_boxes.shape[0] < 1:
+        raise FdError(f"anchor_encode: gt_boxes {tuple(gt_boxes.shape)} / labels {tuple(labels.shape)} must be [B, M, 4] / [B, M] with B >= 1")
+    B, M = labels.shape
+    A = params.num_anchors
+    loc = torch.empty(B, A, 4, dtype=torch.float32, device=gt_boxes.device)
+    cls = torch.empty(B, A, dtype=torch.int64, device=gt_boxes.device)
+    check(_lib.lib().fd_anchor_encode(C.byref(params), gt_boxes.data_ptr() if M else None, labels.data_ptr() if M else None, B, M, A,
+                                      loc.data_ptr(), cls.data_ptr(), _stream()), "fd_anchor_encode")
+    return loc, cls
+
+
+def anchor_decode(params: _lib.AnchorParams, loc: torch.Tensor, cls: torch.Tensor, cls_thresh: float = 0.5, nms_thresh: float = 0.5,
+                  max_candidates: int = 1000):
+    """loc [B, A, 4] fp32, cls [B, A, C] fp32 logits -> (boxes [B, K, 4], labels [B, K] int64 (-1 = padding), scores [B, K], counts [B] int32,
+    n_candidates [B] int32), K = min(max_candidates, A): fd_anchor_decode.  n_candidates[b] > K: image b was cut to its K best candidates."""
+    _need_gpu(loc, cls)
+    _need_f32("anchor_decode", loc=loc, cls=cls)
+    A = params.num_anchors
+    if loc.dim() != 3 or cls.dim() != 3 or tuple(loc.shape[1:]) != (A, 4) or tuple(cls.shape[:2]) != tuple(loc.shape[:2]) or loc.shape[0] < 1:
+        raise FdError(f"anchor_decode: loc {tuple(loc.shape)} / cls {tuple(cls.shape)} must be [B, {A}, 4] / [B, {A}, C] with B >= 1")
+    B, _, Cn = cls.shape
+    need = _lib.lib().fd_anchor_decode_workspace_bytes(B, A, int(max_candidates))
+    if need < 0:
+        raise FdError(f"anchor_decode: unsupported B={B} A={A} max_candidates={max_candidates} (1 <= max_candidates <= {_lib.ANCHOR_MAX_CAND})",
+                      rc=_lib.E_UNSUPPORTED)
+    K = min(int(max_candidates), A)
+    dev = loc.device
+    ws = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    boxes = torch.empty(B, K, 4, dtype=torch.float32, device=dev)
+    labels = torch.empty(B, K, dtype=torch.int64, device=dev)
+    scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    n_cand = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_lib.lib().fd_anchor_decode(C.byref(params), loc.data_ptr(), cls.data_ptr(), B, A, Cn, float(cls_thresh), float(nms_thresh),
+                                      int(max_candidates), boxes.data_ptr(), labels.data_ptr(), scores.data_ptr(), counts.data_ptr(),
+                                      n_cand.data_ptr(), ws.data_ptr(), _stream()), "fd_anchor_decode")
+    return boxes, labels, scores, counts, n_cand
+
+
 EVAL_INPUT_ORDER = 1    # include/fcosdet.h FD_EVAL_INPUT_ORDER: match each image's detections in row order (eval_ap_2d) instead of score order
 
 
