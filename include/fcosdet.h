@@ -343,12 +343,19 @@ int32_t fd_preprocess_u8_nhwc4(const uint8_t* x, float* y, int32_t N, int32_t H,
                                const float* std3, fd_stream_t stream);
 /* Output pipeline tail (Test_coco.py:147-151): boxes /= scale, then xyxy -> xywh (COCO), in place on [n][4]. */
 int32_t fd_boxes_rescale_xywh(float* boxes, int64_t n_boxes, float scale, fd_stream_t stream);
-/* NHWC rows -> NCHW copy (only for callers that insist on contiguous NCHW) */
+/* NHWC rows -> NCHW copy (only for callers that insist on contiguous NCHW); any channel view with x_cs >= x_co + C (scalar loads) */
 int32_t fd_nhwc_to_nchw(const float* x, int32_t x_cs, int32_t x_co, float* y, int32_t N, int32_t HW,
                         int32_t C, fd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
 /* Bandwidth-bound layer ops                                                                     */
+/* Channel views (ptr, cs, co, C) of fd_maxpool[_bwd]_nhwc, fd_upsample2x_add_nhwc / fd_upsample2x_bwd_nhwc, fd_dwconv3x3[_gn]_nhwc,
+ * fd_dwconv_dilated_nhwc, fd_dwconv2d_nhwc, the two depthwise weight gradients, fd_groupnorm_act / _apply / _stats / _act_bwd_nhwc,
+ * fd_coef_apply_nhwc, fd_se_scale[_bwd]_nhwc, fd_act[_bwd]_nhwc[_h] and fd_batchnorm_sync_fwd / _bwd_nhwc are accessed four channels at a
+ * time: C, cs and co are multiples of 4, cs >= co + C, ptr is 16-byte aligned (8-byte for the f16 maps of fd_act_bwd_nhwc_h); a view
+ * that breaks this returns FD_E_INVAL before any launch (a width the kernel does not cover: FD_E_UNSUPPORTED).  In these entry points cs
+ * and co enter the address computation only: a result does not depend, bit for bit, on the view geometry, nothing outside an output
+ * view is written, and an output may be another channel slice of an input's buffer (tests/test_layer_views_gpu.py). */
 
 /* nn.MaxPool2d(k, s, pad) on NHWC; k=3,s=2,pad=1 is the ResNet stem pool, k=2,s=2,pad=0 the FPN
  * down_sample{1..6} (HISFcos.py:131-136); optional fused "+ add" of a tensor in output geometry

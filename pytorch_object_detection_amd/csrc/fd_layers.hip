@@ -97,6 +97,7 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const float* __restri
 extern "C" int32_t fd_nhwc_to_nchw(const float* x, int32_t x_cs, int32_t x_co, float* y, int32_t N, int32_t HW,
                                    int32_t C, fd_stream_t stream) {
     FD_REQUIRE(x && y && N >= 1 && HW >= 1 && C >= 1 && N <= 65535, FD_E_INVAL, "fd_nhwc_to_nchw: bad argument");
+    FD_REQUIRE(x_co >= 0 && x_cs >= x_co + C, FD_E_INVAL, "fd_nhwc_to_nchw: channel view [%d, %d) does not fit rows of %d channels", x_co, x_co + C, x_cs);
     dim3 grid((HW + 31) / 32, (C + 31) / 32, N);
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, x_cs, x_co, y, HW, C);
     FD_CHECK_LAUNCH("fd_nhwc_to_nchw");

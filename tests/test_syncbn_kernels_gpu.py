@@ -1,0 +1,209 @@
+"""fd_batchnorm_sync_fwd_nhwc / fd_batchnorm_sync_bwd_nhwc (two phases each, cut around an all-reduce the caller issues) and
+fd_batchnorm_update_running[_dev] at kernel level: R ranks are simulated on ONE device, without torch.distributed -- every rank is a shard of
+rows with its own sums buffer and workspace, the all-reduce is a sum of the ranks' buffers on the device.  The calls go through the C ABI with
+the argument order of train_ops.syncbn_begin / _SyncBatchNormApply; the reference is the float64 rank-set BatchNorm of tests/layer_ref.py:
+global mean / rstd, dgamma / dbeta from each rank's LOCAL sums, dx from the global means, running statistics with the unbiased variance.
+Tolerances: those of test_batchnorm_train_rows_matches_nn_batchnorm (the same arithmetic)."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import layer_ref as R
+from pytorch_object_detection_amd import _lib, ops
+from pytorch_object_detection_amd._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU, FdError, Segs
+
+pytestmark = pytest.mark.gpu
+DEV = R.DEV
+NAN = float("nan")
+EPS, MOM = 1e-5, 0.1
+SHARDS = (37, 5, 1)             # unequal row counts, a rank with a single row
+GEOMS = [(0, 4), (4, 4), (8, 4), (12, 4)]
+
+
+def close(a, b, tol):
+    s = float(b.abs().max()) + 1e-12
+    np.testing.assert_allclose(a.double().cpu().numpy() / s, b.numpy() / s, atol=tol)
+
+
+def st():
+    return ops._stream()
+
+
+def fwd(x, gm, bt, y, rows, C, act, phase, sums, total, ws):
+    ops.check(_lib.lib().fd_batchnorm_sync_fwd_nhwc(x.ptr, x.cs, x.co, gm.data_ptr() if gm is not None else None, bt.data_ptr() if bt is not None else None,
+                                                    y.ptr if y is not None else None, y.cs if y is not None else 0, y.co if y is not None else 0, rows, C, EPS, act,
+                                                    phase, sums.data_ptr(), ctypes.c_double(total), ws.data_ptr(), st()), "fd_batchnorm_sync_fwd_nhwc")
+
+
+def bwd(x, dy, gm, bt, dx, dgamma, dbeta, rows, C, act, phase, sums, total, ws, bws):
+    ops.check(_lib.lib().fd_batchnorm_sync_bwd_nhwc(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gm.data_ptr(), bt.data_ptr(), dx.ptr if dx is not None else None,
+                                                    dx.cs if dx is not None else 0, dx.co if dx is not None else 0, dgamma.data_ptr() if dgamma is not None else None,
+                                                    dbeta.data_ptr() if dbeta is not None else None, rows, C, EPS, act, phase, sums.data_ptr(), ctypes.c_double(total),
+                                                    ws.data_ptr(), bws.data_ptr() if bws is not None else None, st()), "fd_batchnorm_sync_bwd_nhwc")
+
+
+def bwd_workspace(rows, C):
+    segs = Segs.make(1, [(rows, 1)])
+    return torch.empty(_lib.lib().fd_groupnorm_bwd_workspace_bytes(ctypes.byref(segs), C) // 8, dtype=torch.float64, device=DEV)
+
+
+def data(shards, C, seed=0):
+    g = torch.Generator().manual_seed(1000 + C + len(shards) + seed)
+    xs = [torch.randn(r, C, generator=g) * 2 + 0.3 for r in shards]
+    dys = [torch.randn(r, C, generator=g) for r in shards]
+    gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.1
+    rmean, rvar = torch.randn(C, generator=g) * 0.1, torch.rand(C, generator=g) + 0.5
+    return xs, dys, gamma, beta, rmean, rvar
+
+
+def protocol(xs, dys, gamma, beta, rmean, rvar, act, host_total, geoms=None):
+    """The two-phase forward and backward over the ranks.  geoms: (co, tail) of x, y, dy, dx (None: contiguous).  Returns per-rank y, dx, dgamma, dbeta,
+    the running statistics after the update, and (buffers, their snapshots before the launches) for the view assertions."""
+    C, n = xs[0].shape[1], len(xs)
+    gx, gy, gdy, gdx = geoms or [(0, 0)] * 4
+    gm, bt = gamma.to(DEV), beta.to(DEV)
+    rm, rv = rmean.to(DEV).clone(), rvar.to(DEV).clone()
+    total = float(sum(x.shape[0] for x in xs)) if host_total else -1.0
+    xv, yv, dyv, dxv, bufs = [], [], [], [], []
+    for x, dy in zip(xs, dys):
+        for lst, t, geo in ((xv, x, gx), (yv, torch.full_like(x, NAN), gy), (dyv, dy, gdy), (dxv, torch.full_like(x, NAN), gdx)):
+            v, b = R.make_view(t, *geo)
+            lst.append(v)
+            bufs.append(b)
+    before = [b.clone() for b in bufs]
+    wss = [ops.groupnorm_workspace(Segs.make(1, [(x.shape[0], 1)]), C, DEV) for x in xs]
+    sums = [torch.empty(2 * C + 1, dtype=torch.float64, device=DEV) for _ in xs]
+    for r in range(n):                                                      # forward phase 1 + this rank's row count behind the sums
+        fwd(xv[r], None, None, None, xs[r].shape[0], C, act, 1, sums[r], 0.0, wss[r])
+        sums[r][2 * C] = float(xs[r].shape[0])
+    red = torch.stack(sums).sum(0)                                          # the all-reduce
+    for r in range(n):
+        sums[r].copy_(red)
+        fwd(xv[r], gm, bt, yv[r], xs[r].shape[0], C, act, 2, sums[r], total, wss[r])
+    ops.batchnorm_update_running_dev(wss[0], sums[0][2 * C:], C, MOM, EPS, rm, rv)
+    dgs = [torch.full((C,), NAN, device=DEV) for _ in xs]
+    dbs = [torch.full((C,), NAN, device=DEV) for _ in xs]
+    bsums = [torch.empty(2 * C + 1, dtype=torch.float64, device=DEV) for _ in xs]
+    for r in range(n):                                                      # backward phase 1; the row count is copied, not reduced again
+        bwd(xv[r], dyv[r], gm, bt, None, dgs[r], dbs[r], xs[r].shape[0], C, act, 1, bsums[r], 0.0, wss[r], bwd_workspace(xs[r].shape[0], C))
+        bsums[r][2 * C:].copy_(sums[r][2 * C:])
+    red = torch.stack([s[:2 * C] for s in bsums]).sum(0)                    # the all-reduce of sums[:2C] only
+    for r in range(n):
+        bsums[r][:2 * C].copy_(red)
+        bwd(xv[r], dyv[r], gm, bt, dxv[r], None, None, xs[r].shape[0], C, act, 2, bsums[r], total, wss[r], None)
+    torch.cuda.synchronize()
+    out = dict(y=[v.tensor().clone() for v in yv], dx=[v.tensor().clone() for v in dxv], dgamma=dgs, dbeta=dbs, rmean=rm, rvar=rv, ws=wss, count=sums[0][2 * C:])
+    return out, (bufs, before, [xv, yv, dyv, dxv])
+
+
+def assert_same(a, b):
+    for k in ("y", "dx", "dgamma", "dbeta"):
+        for r, (s, t) in enumerate(zip(a[k], b[k])):
+            assert torch.equal(s, t), f"{k} of rank {r} differs"
+    assert torch.equal(a["rmean"], b["rmean"]) and torch.equal(a["rvar"], b["rvar"])
+
+
+@pytest.mark.parametrize("act", [ACT_NONE, ACT_RELU, ACT_SILU])
+@pytest.mark.parametrize("C", [4, 64, 1024])
+@pytest.mark.parametrize("nranks", [1, 2, 3])
+def test_two_phase_protocol_over_simulated_ranks(nranks, C, act):
+    xs, dys, gamma, beta, rmean, rvar = data(SHARDS[:nranks], C)
+    dev_form, _ = protocol(xs, dys, gamma, beta, rmean, rvar, act, host_total=False)
+    host_form, _ = protocol(xs, dys, gamma, beta, rmean, rvar, act, host_total=True)
+    assert_same(dev_form, host_form)                     # total_rows as a host value and read on the device (-1): bit-identical
+    ys, mean, var, n = R.bn_sync_fwd(xs, gamma, beta, EPS, act)
+    ref = R.bn_sync_bwd(xs, dys, gamma, beta, EPS, act)
+    assert float(dev_form["count"].cpu()) == n
+    for r in range(nranks):
+        close(dev_form["y"][r], ys[r], 2e-5)
+        close(dev_form["dx"][r], ref[r][0], 1e-4)
+        close(dev_form["dgamma"][r], ref[r][1], 1e-4)    # from the rank's LOCAL sums
+        close(dev_form["dbeta"][r], ref[r][2], 1e-4)
+    rm, rv = R.bn_running(rmean, rvar, mean, var, n, MOM)
+    np.testing.assert_allclose(dev_form["rmean"].cpu().numpy(), rm.numpy(), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(dev_form["rvar"].cpu().numpy(), rv.numpy(), rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize("act", [ACT_NONE, ACT_RELU, ACT_SILU])
+@pytest.mark.parametrize("C", [4, 64, 1024])
+def test_one_rank_is_groupnorm_with_one_group_per_channel(C, act):
+    """The header's statement that these ARE the GroupNorm kernels: one rank gives bit for bit what groupnorm_act / groupnorm_act_bwd give on one
+    image of rows x 1 pixels with G = C."""
+    rows = SHARDS[0]
+    xs, dys, gamma, beta, rmean, rvar = data(SHARDS[:1], C)
+    got, _ = protocol(xs, dys, gamma, beta, rmean, rvar, act, host_total=False)
+    segs = Segs.make(1, [(rows, 1)])
+    gm, bt = gamma.to(DEV), beta.to(DEV)
+    x, dy = ops.Rows(xs[0].to(DEV)), ops.Rows(dys[0].to(DEV))
+    y, dx = ops.new_rows(rows, C, DEV), ops.new_rows(rows, C, DEV)
+    ws = ops.groupnorm_workspace(segs, C, DEV)
+    ops.groupnorm_act(x, gm, bt, y, segs, C, act, ws, EPS)
+    dgamma, dbeta = ops.groupnorm_act_bwd(x, dy, gm, bt, dx, segs, C, act, ws, EPS)
+    assert torch.equal(got["y"][0], y.tensor()) and torch.equal(got["dx"][0], dx.tensor())
+    assert torch.equal(got["dgamma"][0], dgamma) and torch.equal(got["dbeta"][0], dbeta)
+    # the running statistics with the row count as a host value and in device memory: bit-identical
+    rm, rv = rmean.to(DEV).clone(), rvar.to(DEV).clone()
+    ops.batchnorm_update_running(ws, rows, C, MOM, EPS, rm, rv)
+    assert torch.equal(rm, got["rmean"]) and torch.equal(rv, got["rvar"])
+
+
+@pytest.mark.parametrize("host_total", [False, True])
+def test_protocol_on_channel_views(host_total):
+    """x, y, dy and dx each on its own channel view with NaN neighbours: bit-identical to the contiguous run, nothing outside y / dx written,
+    x and dy unchanged."""
+    C, act = 64, ACT_SILU
+    xs, dys, gamma, beta, rmean, rvar = data(SHARDS[:2], C, seed=1)
+    base, _ = protocol(xs, dys, gamma, beta, rmean, rvar, act, host_total)
+    for rot in (0, 1):
+        geoms = [GEOMS[(i + rot) % 4] for i in range(4)]
+        got, (bufs, before, views) = protocol(xs, dys, gamma, beta, rmean, rvar, act, host_total, geoms)
+        assert_same(got, base)
+        for r in range(2):
+            bx, by, bdy, bdx = bufs[4 * r:4 * r + 4]
+            ax, ay, ady, adx = before[4 * r:4 * r + 4]
+            assert R.unchanged(bx, ax) and R.unchanged(bdy, ady)
+            assert R.outside_untouched(by, views[1][r].co, C, ay) and R.outside_untouched(bdx, views[3][r].co, C, adx)
+
+
+def test_update_running_host_count_matches_device_count():
+    C = 64
+    xs, dys, gamma, beta, rmean, rvar = data(SHARDS, C, seed=2)
+    got, _ = protocol(xs, dys, gamma, beta, rmean, rvar, ACT_NONE, host_total=False)
+    rm, rv = rmean.to(DEV).clone(), rvar.to(DEV).clone()
+    ops.batchnorm_update_running(got["ws"][0], sum(SHARDS), C, MOM, EPS, rm, rv)
+    assert torch.equal(rm, got["rmean"]) and torch.equal(rv, got["rvar"])
+
+
+def test_rejections_leave_the_outputs_untouched():
+    """Argument checks that return before any launch."""
+    rows = 37
+    for what in ("C48", "total_rows", "phase", "sigmoid"):
+        C = 48 if what == "C48" else 64
+        g = torch.Generator().manual_seed(7)
+        x, bx = R.make_view(torch.randn(rows, C, generator=g), 4, 4)
+        dy, _ = R.make_view(torch.randn(rows, C, generator=g), 8, 4)
+        y, by = R.make_view(torch.full((rows, C), NAN), 0, 4)
+        dx, bdx = R.make_view(torch.full((rows, C), NAN), 12, 4)
+        gm, bt = torch.ones(C, device=DEV), torch.zeros(C, device=DEV)
+        sums = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device=DEV)
+        dg, db = torch.full((C,), NAN, device=DEV), torch.full((C,), NAN, device=DEV)
+        ws = ops.groupnorm_workspace(Segs.make(1, [(rows, 1)]), C, DEV)
+        bws = bwd_workspace(rows, C)
+        calls = {
+            "C48": [lambda: fwd(x, None, None, None, rows, C, ACT_NONE, 1, sums, 0.0, ws), lambda: fwd(x, gm, bt, y, rows, C, ACT_NONE, 2, sums, -1.0, ws),
+                    lambda: bwd(x, dy, gm, bt, None, dg, db, rows, C, ACT_NONE, 1, sums, 0.0, ws, bws),
+                    lambda: bwd(x, dy, gm, bt, dx, None, None, rows, C, ACT_NONE, 2, sums, -1.0, ws, None)],
+            "total_rows": [lambda: fwd(x, gm, bt, y, rows, C, ACT_NONE, 2, sums, 5.0, ws),              # 0 < total_rows < this shard's rows
+                           lambda: bwd(x, dy, gm, bt, dx, None, None, rows, C, ACT_NONE, 2, sums, 36.0, ws, None)],
+            "phase": [lambda: fwd(x, gm, bt, y, rows, C, ACT_NONE, 3, sums, -1.0, ws), lambda: bwd(x, dy, gm, bt, dx, dg, db, rows, C, ACT_NONE, 3, sums, -1.0, ws, bws)],
+            "sigmoid": [lambda: bwd(x, dy, gm, bt, None, dg, db, rows, C, ACT_SIGMOID, 1, sums, 0.0, ws, bws),
+                        lambda: bwd(x, dy, gm, bt, dx, None, None, rows, C, ACT_SIGMOID, 2, sums, -1.0, ws, None)],
+        }[what]
+        for call in calls:
+            with pytest.raises(FdError):
+                call()
+        torch.cuda.synchronize()
+        for t in (by, bdx, sums, dg, db):
+            assert bool(torch.isnan(t).all()), f"{what}: a rejected call wrote an output"
