@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's train.py:97-181 loop on the MI355X path, with synthetic VOC-shaped batches.
 
-    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS]
+    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_like_train_py.py   # DDP / RCCL
 
 Same objects and call order as the reference: HalfInvertedStageFCOS([512, 1024, 2048], 20, 256), FCOSGenTargets,
@@ -10,7 +10,9 @@ In model.train() the forward is an autograd graph of HIP kernels (train_ops.py);
 kernels; under autocast the dense convolutions run on the f16 MFMA with fp32 accumulation (forward, data and weight gradients:
 the reference's AMP arithmetic), normalisation and losses in fp32; under DDP the FPN's BatchNorms are SyncBatchNorm on the HIP statistics path.
 --model MNFCOS (what the reference's config/main.yaml selects) builds MNFCOS([2048, 1024, 512], 20, 256) and opts in to its HIP training nodes
-with model.enable_training() (which also freezes the Cin = 3 stem: the optimizer is built after it).
+with model.enable_training() (which also freezes the Cin = 3 stem: the optimizer is built after it).  --hip-stem trains the 7x7 stem on its HIP node
+(fd_stem7x7_bwd_weight_nhwc4) instead: MNFCOS keeps the stem trainable (enable_training(train_stem=True)), HISFCOS un-freezes conv1 and sets
+enable_stem_training() -- without the option a trainable stem runs on stock ops.
 """
 import argparse
 import os
@@ -32,6 +34,7 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--amp", action="store_true")
     ap.add_argument("--model", choices=["HISFCOS", "MNFCOS"], default="HISFCOS")
+    ap.add_argument("--hip-stem", action="store_true", help="train the 7x7 stem (conv1) on its HIP forward / weight-gradient node")
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
     torch.cuda.set_device(local)
@@ -42,9 +45,12 @@ def main():
 
     torch.manual_seed(0)
     if args.model == "MNFCOS":
-        model = MNFCOS([2048, 1024, 512], 20, 256).enable_training().to(dev)                        # config/main.yaml:2, mnfcos.yaml
+        model = MNFCOS([2048, 1024, 512], 20, 256).enable_training(train_stem=args.hip_stem).to(dev)   # config/main.yaml:2, mnfcos.yaml
     else:
         model = HalfInvertedStageFCOS([512, 1024, 2048], 20, 256).to(dev)                           # train.py:97
+        if args.hip_stem:
+            model.backbone.conv1.weight.requires_grad_(True)      # (the constructor's freeze_stages(1) froze it; bn1 stays frozen and folds into the launch)
+            model.enable_stem_training()
     gen_target = FCOSGenTargets(strides=[8, 16, 32, 64, 128],
                                 limit_range=[[-1, 64], [64, 128], [128, 256], [256, 512], [512, 999999]])   # train.py:98
     if world > 1:

@@ -333,6 +333,21 @@ int32_t fd_stem7x7_pool_nhwc4(const float* x4, const float* w, const float* scal
 int32_t fd_stem7x7_nchw3(const float* x, const float* w, const float* scale, const float* shift, float* y, int32_t y_cs, int32_t y_co,
                          int32_t N, int32_t H, int32_t W, int32_t act, int32_t pool, fd_stream_t stream);
 
+/* Weight gradient of the stem above (the image needs no gradient: there is no data-gradient kernel):
+ *   dw[co][ci][ky][kx] = scale[co] * sum over (n, oy, ox) of g[n][oy][ox][co] * x4[n][2 oy - 3 + ky][2 ox - 3 + kx][ci],  taps outside the image contribute zero,
+ * g = dy when y is NULL, else dy where y > 0 and 0 elsewhere (y = the forward output after ReLU: the mask is applied in the dy loader, no separate pass).
+ * x4: the [N][H][W][4] image (channel 3 ignored).  dy and y: [N][H/2][W/2] rows, each a 64-CHANNEL VIEW of a rows buffer -- channel stride cs, first channel co,
+ * cs % 4 == 0, co % 4 == 0, cs >= co + 64, base pointer 16-byte aligned; only those 64 channels of a row are read.  scale: optional [64] (a frozen BatchNorm folded
+ * into the forward).  dw: [64][3][7][7], torch's OIHW layout.  H and W even and >= 2.  An fp32-MFMA GEMM (M = 64, N = 154 padded to 160, K = the output pixels);
+ * the pixels are partitioned by (N, H, W) alone, every part's fp32 partial slab goes to `workspace`, and a second launch adds the slabs in index order in fp64:
+ * two runs are bit-identical.  Two launches on `stream`, no host synchronisation, no allocation (safe under graph capture); nothing outside dw and the first
+ * fd_stem7x7_wgrad_workspace_bytes(N, H, W) bytes of the 16-byte aligned workspace is written (-1: N < 1, or H / W odd or < 2).  A violated contract returns
+ * FD_E_INVAL before any launch. */
+int64_t fd_stem7x7_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int32_t fd_stem7x7_bwd_weight_nhwc4(const float* x4, const float* dy, int32_t dy_cs, int32_t dy_co, const float* y, int32_t y_cs, int32_t y_co,
+                                    const float* scale, float* dw, void* workspace, int64_t workspace_bytes, int32_t N, int32_t H, int32_t W,
+                                    fd_stream_t stream);
+
 /* [N][3][H][W] fp32 (NCHW, the reference's input layout, dataset/voc.py:141-173) -> [N][H][W][4] (c=3 zero) */
 int32_t fd_nchw3_to_nhwc4(const float* x, float* y, int32_t N, int32_t H, int32_t W, fd_stream_t stream);
 /* Input pipeline tail on the device: uint8 [N][H][W][3] images, already resized and zero padded

@@ -144,6 +144,8 @@ _SIGS = {
     "fd_stem7x7_nhwc4": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "fd_stem7x7_pool_nhwc4": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "fd_stem7x7_nchw3": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "fd_stem7x7_wgrad_workspace_bytes": (_L, [_I, _I, _I]),
+    "fd_stem7x7_bwd_weight_nhwc4": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _L, _I, _I, _I, _P]),
     "fd_nchw3_to_nhwc4": (_I, [_P, _P, _I, _I, _I, _P]),
     "fd_nhwc_to_nchw": (_I, [_P, _I, _I, _P, _I, _I, _I, _P]),
     "fd_preprocess_u8_nhwc4": (_I, [_P, _P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),

@@ -38,6 +38,8 @@ def _make_layer(inplanes: int, planes: int, blocks: int, stride: int) -> nn.Sequ
 class _Trunk(nn.Module):
     """conv1, bn1, layer1..layer4 (no avgpool/fc: the fx feature extractor of the reference prunes them)."""
 
+    hip_stem_train = False       # opt-in: a trainable stem on the HIP node (train_ops.stem_rows) instead of stock ops
+
     def __init__(self):
         super().__init__()
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
@@ -58,12 +60,15 @@ def _no_torch_forward(self, *a, **k):
 def trunk_train_forward(trunk: nn.Module, x: torch.Tensor):
     """Autograd-capable trunk forward (training only; inference runs the HIP plan).  Every bottleneck conv is one fused
     HIP launch (conv + frozen BN + residual + ReLU, train_ops.conv_bn_act) differentiated by the HIP data- / weight-
-    gradient kernels; a frozen stem (freeze_stages(1)) runs on the inference kernels.  Returns (C3, C4, C5)."""
+    gradient kernels; a frozen stem (freeze_stages(1)) runs on the inference kernels; a trainable one runs on train_ops.stem_rows (the stem kernel +
+    fd_stem7x7_bwd_weight_nhwc4) when `trunk.hip_stem_train` is set, else on stock ops.  Returns (C3, C4, C5)."""
     import torch.nn.functional as F
 
-    from ...train_ops import bottleneck, stem_frozen, stem_is_frozen
+    from ...train_ops import bottleneck, stem_frozen, stem_is_frozen, stem_rows, stem_rows_ok
     if stem_is_frozen(trunk, x):
         x = stem_frozen(trunk, x)
+    elif getattr(trunk, "hip_stem_train", False) and stem_rows_ok(trunk, x):      # opt-in: the stem's HIP forward + weight gradient
+        x = stem_rows(trunk, x)
     else:                                                     # trainable 7x7 stem (Cin = 3): stock ops
         from ...train_ops import stock_fallback
         stock_fallback("a trainable / un-frozen 7x7 stem (Cin = 3)")
@@ -93,6 +98,15 @@ class ResNet50v2(nn.Module):
     def trunk(self) -> nn.Module:
         return self.extract_feature
 
+    @property
+    def hip_stem_train(self) -> bool:
+        """Opt-in (default False): a trainable stem runs on the HIP node instead of stock ops.  Lives on the trunk that trunk_train_forward sees."""
+        return self.extract_feature.hip_stem_train
+
+    @hip_stem_train.setter
+    def hip_stem_train(self, on: bool) -> None:
+        self.extract_feature.hip_stem_train = bool(on)
+
     forward = _no_torch_forward
 
     def freeze_bn(self):
@@ -115,6 +129,8 @@ class ResNet50v2(nn.Module):
 
 class ResNet50(nn.Module):
     """Reference model/backbone/resnet50.py:9-57 (FCOS baseline backbone): keys conv1, bn1, layer1..layer4."""
+
+    hip_stem_train = False       # opt-in: a trainable stem on the HIP node (train_ops.stem_rows) instead of stock ops
 
     def __init__(self, re_layer: int = 1):
         super().__init__()

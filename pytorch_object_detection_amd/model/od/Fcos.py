@@ -191,6 +191,14 @@ class FCOS(PlannedModule):
         plan.outs, plan.segs = outs, segs
         return plan
 
+    def enable_stem_training(self):
+        """Opt in to the HIP node for the trainable 7x7 stem (backbone.hip_stem_train: the stem kernel forward, fd_stem7x7_bwd_weight_nhwc4 backward)
+        instead of the stock-op fallback.  Off by default.  Returns self."""
+        if self.efficientnet:
+            raise FdError("FCOS(efficientnet=True) has no ResNet stem to train")
+        self.backbone.hip_stem_train = True
+        return self
+
     def forward(self, x: torch.Tensor, events=None):
         if self.training:
             self._check_train_input(x)

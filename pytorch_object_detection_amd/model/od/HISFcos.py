@@ -297,6 +297,12 @@ class HalfInvertedStageFCOS(PlannedModule):
         plan.outs, plan.segs = outs, segs
         return plan
 
+    def enable_stem_training(self):
+        """Opt in to the HIP node for a trainable 7x7 stem (backbone.hip_stem_train) instead of the stock-op fallback.  It only matters once the user
+        un-freezes backbone.conv1, which the constructor freezes (freeze_stages(1)).  Off by default.  Returns self."""
+        self.backbone.hip_stem_train = True
+        return self
+
     def forward(self, x: torch.Tensor, events=None):
         """[B,3,H,W] fp32 CUDA -> (cls_logits, cnt_logits, reg_preds), each a list of 5 NCHW-shaped tensors
         (strides 8..128; reference HISFcos.py:70-74).  The tensors are views of plan-owned buffers and are

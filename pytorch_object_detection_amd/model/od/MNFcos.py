@@ -12,8 +12,8 @@ Training is opt-in.  As constructed the model is inference-only (`train()` + for
 HalfInvertedStageFCOS does: the trunk's fused bottlenecks, the 1x1 laterals, the MNBlocks (train_ops.mn_block_rows: dilated depthwise conv with its data
 and weight gradient kernels), upsample / max-pool nodes, the head over the whole pyramid per launch.  BatchNorm follows PlannedModule.train(): the
 backbone's stays frozen, the FPN's and the head's run on batch statistics (per level in the shared head blocks, as the reference calls them once per
-level) unless `freeze_all_bn` pins them.  The 7x7 stem (Cin = 3) has no HIP backward: enable_training() freezes it (backbone.freeze_stages(0)), the one
-departure from the reference's trainable set."""
+level) unless `freeze_all_bn` pins them.  enable_training() freezes the 7x7 stem (backbone.freeze_stages(0)) by default, the one departure from the
+reference's trainable set; enable_training(train_stem=True) keeps it trainable on the HIP stem node (train_ops.stem_rows)."""
 from __future__ import annotations
 
 from typing import List
@@ -203,14 +203,18 @@ class MNFCOS(PlannedModule):
         plan.outs, plan.segs = outs, segs
         return plan
 
-    def enable_training(self):
-        """Opt in to training on the HIP autograd nodes: hip_train on the model, its FPN, its head and every MNBlock.  The 7x7 stem (Cin = 3) has no
-        HIP backward, so it is frozen here (backbone.freeze_stages(0): conv1 + bn1), as HalfInvertedStageFCOS freezes it at construction -- build the
-        optimizer after this call.  Returns self."""
+    def enable_training(self, train_stem: bool = False):
+        """Opt in to training on the HIP autograd nodes: hip_train on the model, its FPN, its head and every MNBlock.  By default the 7x7 stem (Cin = 3)
+        is frozen here (backbone.freeze_stages(0): conv1 + bn1), as HalfInvertedStageFCOS freezes it at construction -- build the optimizer after this
+        call.  `train_stem=True` keeps the reference's trainable set instead: the stem stays trainable and runs on the HIP node (backbone.hip_stem_train:
+        the stem kernel forward, fd_stem7x7_bwd_weight_nhwc4 backward); nothing is frozen and nothing is warned about.  Returns self."""
         _enable_blocks(self)
+        if train_stem:
+            self.backbone.hip_stem_train = True
+            return self
         if self.backbone.conv1.weight.requires_grad:
             import warnings
-            warnings.warn("MNFCOS.enable_training() freezes the 7x7 stem (backbone.conv1 / bn1: no HIP backward for Cin = 3); "
+            warnings.warn("MNFCOS.enable_training() freezes the 7x7 stem (backbone.conv1 / bn1); pass train_stem=True to train it on the HIP node; "
                           "an optimizer built before this call holds a parameter that no longer receives a gradient", stacklevel=2)
         self.backbone.freeze_stages(0)
         return self

@@ -180,6 +180,33 @@ def pack_dwk_weight(w: torch.Tensor) -> torch.Tensor:
     return w.detach().reshape(w.shape[0], -1).t().contiguous().float()
 
 
+def stem7x7_wgrad_workspace(N: int, H: int, W: int, device) -> torch.Tensor:
+    """The workspace of stem7x7_wgrad for an [N, 3, H, W] batch (fd_stem7x7_wgrad_workspace_bytes: the fp32 partial slabs of the fixed pixel partition)."""
+    nb = _lib.lib().fd_stem7x7_wgrad_workspace_bytes(N, H, W)
+    if nb < 0:
+        raise FdError(f"fd_stem7x7_wgrad_workspace_bytes: N >= 1 and even H, W >= 2 (got N={N}, H={H}, W={W})")
+    return torch.empty(nb // 4, dtype=torch.float32, device=device)
+
+
+def stem7x7_wgrad(x4: Rows, dy: Rows, N: int, H: int, W: int, y: Optional[Rows] = None, scale: Optional[torch.Tensor] = None,
+                  ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Weight gradient [64, 3, 7, 7] of the ResNet stem 7x7 s2 p3 given dy on the [N][H/2][W/2] rows (fd_stem7x7_bwd_weight_nhwc4).  `y`: the forward output
+    after ReLU -- the mask dy * [y > 0] is applied in the kernel's loader; `scale` multiplies the result per output channel (a frozen BatchNorm folded into
+    the forward).  dy / y may be 64-channel views.  Deterministic; two launches, no host sync."""
+    _need_gpu(x4.buf, dy.buf, y.buf if y is not None else None, scale, ws)
+    if x4.cs != 4 or x4.co != 0 or dy.C != 64 or (y is not None and y.C != 64) or dy.f16 or x4.f16 or (y is not None and y.f16):
+        raise FdError("stem7x7_wgrad: input must be the fp32 [rows][4] image buffer, dy (and y) fp32 64-channel views")
+    if x4.rows != N * H * W or dy.rows * 4 != N * H * W or (y is not None and y.rows != dy.rows):
+        raise FdError(f"stem7x7_wgrad: {x4.rows} image rows / {dy.rows} gradient rows do not match N={N}, H={H}, W={W}")
+    if ws is None:
+        ws = stem7x7_wgrad_workspace(N, H, W, dy.buf.device)
+    dw = torch.empty(64, 3, 7, 7, dtype=torch.float32, device=dy.buf.device)
+    check(_lib.lib().fd_stem7x7_bwd_weight_nhwc4(x4.ptr, dy.ptr, dy.cs, dy.co, y.ptr if y is not None else None, y.cs if y is not None else 0,
+                                                 y.co if y is not None else 0, scale.data_ptr() if scale is not None else None, dw.data_ptr(),
+                                                 ws.data_ptr(), ws.numel() * ws.element_size(), N, H, W, _stream()), "fd_stem7x7_bwd_weight_nhwc4")
+    return dw
+
+
 def pack_stem3_weight(w: torch.Tensor) -> torch.Tensor:
     """[Cout,3,K,K] -> [K*K][4][Cout] (fd_stem_conv_nhwc4); input channel 3 is zero."""
     co, ci, kh, kw = w.shape

@@ -13,9 +13,10 @@ over the whole pyramid exactly as at inference.
   dw_dilated_rows           dilated depthwise k x k (MNBlock): fd_dwconv_dilated_nhwc forward and data gradient, fd_dwconv_dilated_bwd_weight_nhwc;
                             mn_block_rows = the whole MNBlock (depthwise, BatchNorm frozen or on batch statistics, PW1 + SiLU, PW2 + residual).
   groupnorm_rows            GroupNorm + ReLU / SiLU: fd_groupnorm_act_nhwc / fd_groupnorm_act_bwd_nhwc.
+  stem_rows                 the trainable 7x7 stem (Cin = 3), opt-in (trunk.hip_stem_train): fd_stem7x7_nhwc4 forward, fd_stem7x7_bwd_weight_nhwc4 backward.
 
 What the kernels do not cover falls back to stock PyTorch-ROCm ops on the GPU: the data gradient of strided layers,
-dense layers with Cin % 32 != 0 (the 7x7 stem when it is trainable), BatchNorm in training mode or with trainable
+dense layers with Cin % 32 != 0 (the 7x7 stem when it is trainable and its node is not switched on), BatchNorm in training mode or with trainable
 affine parameters, and SiLU after a BatchNorm (its derivative needs the pre-activation, which the fused epilogue does
 not keep).  Narrow outputs (class / centre-ness / box logits) are padded to 32 channels by `conv_rows(pad_out=True)`.
 """
@@ -1152,3 +1153,64 @@ def stem_frozen(trunk: nn.Module, x: torch.Tensor) -> torch.Tensor:
 def stem_is_frozen(trunk: nn.Module, x: torch.Tensor) -> bool:
     return (not _STOCK and bn_is_frozen(trunk.bn1) and not trunk.conv1.weight.requires_grad and not x.requires_grad
             and _f32(x) and tuple(trunk.conv1.weight.shape) == (64, 3, 7, 7))
+
+
+# ------------------------------------------------------------------------------- the trainable 7x7 stem (Cin = 3)
+class _StemRows(torch.autograd.Function):
+    """conv1 (7x7 stride 2 pad 3, 3 -> 64, no bias) of the ResNet stem on an NCHW fp32 image batch that needs no gradient, as rows [B * H/2 * W/2, 64]:
+    y = act(conv(x, w) * scale + shift) with scale / shift the constants of a frozen bn1 (act = ReLU), or the raw conv (scale = shift = None, ACT_NONE) in
+    front of a BatchNorm on batch statistics.  Forward: fd_nchw3_to_nhwc4 + the unfused fd_stem7x7_nhwc4 (the map is needed for the ReLU mask and by the
+    max-pool's backward).  Backward: fd_stem7x7_bwd_weight_nhwc4, the ReLU mask applied in its dy loader; there is no data gradient.
+    Under torch.autocast the node computes in fp32 (_fwd32), like the depthwise and normalisation nodes: the reference's fp16 stem convolution is computed
+    wider here."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, weight, scale, shift, act):
+        B, _, H, W = x.shape
+        x4 = torch.empty(B * H * W, 4, dtype=torch.float32, device=x.device)
+        ops.nchw3_to_nhwc4(x.contiguous(), x4)
+        y = torch.empty(B * (H // 2) * (W // 2), 64, dtype=torch.float32, device=x.device)
+        ops.stem7x7(Rows(x4), ops.pack_stem7_weight(weight.detach()), Rows(y), B, H, W, scale, shift, act)
+        ctx.save_for_backward(x4, scale, y if act == ACT_RELU else None)
+        ctx.geom = (B, H, W)
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        x4, scale, y = ctx.saved_tensors
+        B, H, W = ctx.geom
+        gw = None
+        if ctx.needs_input_grad[1]:
+            g = resolve_pending(gy)
+            gr = _rv(g)
+            if gr is None:
+                g = g.contiguous()
+                gr = _r(g)
+            gw = ops.stem7x7_wgrad(Rows(x4), gr, B, H, W, _r(y) if y is not None else None, scale)
+        return None, gw, None, None, None
+
+
+def stem_rows_ok(trunk: nn.Module, x: torch.Tensor) -> bool:
+    """What stem_rows covers: the [64, 3, 7, 7] fp32 filter bank without bias, an fp32 image batch of even size that needs no gradient, and bn1 either
+    frozen or a BatchNorm in training mode that batchnorm_train_rows takes (not a SyncBatchNorm spanning ranks: that keeps the stock path)."""
+    m, bn = trunk.conv1, trunk.bn1
+    return (not _STOCK and tuple(m.weight.shape) == (64, 3, 7, 7) and m.bias is None and m.weight.dtype == torch.float32 and x.dtype == torch.float32
+            and not x.requires_grad and x.dim() == 4 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.shape[2] >= 2 and x.shape[3] >= 2
+            and (bn_is_frozen(bn) or (_bn_train_ok(bn, x) and not _is_sync(bn))))
+
+
+def stem_rows(trunk: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """maxpool(relu(bn1(conv1(x)))) of a TRAINABLE ResNet stem with every op a HIP node (check with stem_rows_ok): _StemRows (frozen bn1 folded into the
+    launch, or the raw conv + batchnorm_train_rows on batch statistics) and the max-pool node at (3, 2, 1).  NCHW-shaped channels-last view out."""
+    B, _, H, W = x.shape
+    bn = trunk.bn1
+    if bn_is_frozen(bn):
+        sc, sf = _bn_fold(bn)
+        t = _StemRows.apply(x, trunk.conv1.weight, sc, sf, ACT_RELU)
+    else:
+        t = batchnorm_train_rows(bn, _StemRows.apply(x, trunk.conv1.weight, None, None, ACT_NONE), ACT_RELU)
+    H1, W1 = H // 2, W // 2
+    y2 = _PoolAddRows.apply(t, None, (B, H1, W1, 3, 2, 1))
+    return from_rows(y2, B, (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1)
