@@ -57,6 +57,25 @@ def _no_torch_forward(self, *a, **k):
     raise RuntimeError("the backbone runs inside the model's HIP plan; call the detector (model(x)) instead")
 
 
+def _freeze_bn(self):
+    for layer in self.modules():
+        if isinstance(layer, (nn.BatchNorm2d, nn.SyncBatchNorm)):
+            layer.eval()
+
+
+def _freeze_stages(self, stage: int):
+    if stage >= 0:
+        self.bn1.eval()
+        for m in [self.conv1, self.bn1]:
+            for param in m.parameters():
+                param.requires_grad = False
+    for i in range(1, stage + 1):
+        layer = getattr(self, f'layer{i}')
+        layer.eval()
+        for param in layer.parameters():
+            param.requires_grad = False
+
+
 def trunk_train_forward(trunk: nn.Module, x: torch.Tensor):
     """Autograd-capable trunk forward (training only; inference runs the HIP plan).  Every bottleneck conv is one fused
     HIP launch (conv + frozen BN + residual + ReLU, train_ops.conv_bn_act) differentiated by the HIP data- / weight-
@@ -108,23 +127,7 @@ class ResNet50v2(nn.Module):
         self.extract_feature.hip_stem_train = bool(on)
 
     forward = _no_torch_forward
-
-    def freeze_bn(self):
-        for layer in self.modules():
-            if isinstance(layer, (nn.BatchNorm2d, nn.SyncBatchNorm)):
-                layer.eval()
-
-    def freeze_stages(self, stage: int):
-        if stage >= 0:
-            self.bn1.eval()
-            for m in [self.conv1, self.bn1]:
-                for param in m.parameters():
-                    param.requires_grad = False
-        for i in range(1, stage + 1):
-            layer = getattr(self, f'layer{i}')
-            layer.eval()
-            for param in layer.parameters():
-                param.requires_grad = False
+    freeze_bn, freeze_stages = _freeze_bn, _freeze_stages
 
 
 class ResNet50(nn.Module):
@@ -146,20 +149,4 @@ class ResNet50(nn.Module):
         return self
 
     forward = _no_torch_forward
-
-    def freeze_bn(self):
-        for layer in self.modules():
-            if isinstance(layer, (nn.BatchNorm2d, nn.SyncBatchNorm)):
-                layer.eval()
-
-    def freeze_stages(self, stage: int):
-        if stage >= 0:
-            self.bn1.eval()
-            for m in [self.conv1, self.bn1]:
-                for param in m.parameters():
-                    param.requires_grad = False
-        for i in range(1, stage + 1):
-            layer = getattr(self, 'layer{}'.format(i))
-            layer.eval()
-            for param in layer.parameters():
-                param.requires_grad = False
+    freeze_bn, freeze_stages = _freeze_bn, _freeze_stages

@@ -9,15 +9,15 @@ import torch
 import torch.nn as nn
 
 from ... import engine
-from ..._lib import FdError, Segs
+from ..._lib import FdError
 import torch.nn.functional as F
 
 from ...ops import ACT_RELU
 from ... import train_ops as T
 from ...train_ops import conv2d as tconv, conv_bn_act as cba
-from ..backbone.resnet50 import ResNet50, trunk_train_forward
+from ..backbone.resnet50 import ResNet50
 from ..modules.modules import ScaleExp, init_conv_kaiming, init_conv_random_normal
-from ._planned import PlannedModule, copy_in_nchw, pyramid_out
+from ._planned import PlannedModule
 
 
 class FeaturePyramidNetwork(PlannedModule):
@@ -44,26 +44,7 @@ class FeaturePyramidNetwork(PlannedModule):
         return p3, p4, p5, p6, tconv(self.P7_c1, p6)
 
     def forward(self, x):
-        if self.training:
-            return self.train_forward(x)
-        c3, c4, c5 = x
-        key = ("FPN",) + tuple(tuple(t.shape) for t in x) + (str(c3.device),)
-
-        def build():
-            plan = engine.Plan(c3.device, self.conv_precision)
-            ins = []
-            for t in (c3, c4, c5):
-                B, C, H, W = t.shape
-                full, view = engine.padded_input(plan, B * H * W, C)
-                ins.append((full, Segs.make(B, [(H, W)]), view))
-            pyr, segs = engine.build_fcos_fpn(plan, self, [(r, s) for r, s, _ in ins])
-            return plan, ins, pyr, segs
-
-        plan, ins, pyr, segs = self._get_plan(key, build)
-        for (_, s, view), t in zip(ins, (c3, c4, c5)):
-            copy_in_nchw(view, s, 0, t)
-        plan.run()
-        return pyramid_out(pyr, segs)
+        return self.train_forward(x) if self.training else self._run_fpn(engine.build_fcos_fpn, x)
 
 
 class HeadFCOS(PlannedModule):
@@ -97,12 +78,7 @@ class HeadFCOS(PlannedModule):
                                  self.cls_branch[3 * k + 2])
             r = T.groupnorm_rows(self.reg_branch[3 * k + 1], T.conv_rows(self.reg_branch[3 * k], r, segs), segs,
                                  self.reg_branch[3 * k + 2])
-        cls = T.conv_rows(self.cls_logits, c, segs, pad_out=True)
-        rc = T.conv_rows(T.MergedConv(self.reg_pred, self.cnt_logits), r, segs, pad_out=True)  # [:, :4] boxes, [:, 4] centre-ness
-        cls_l = T.pyramid_split(cls, segs)
-        cnt_l = T.pyramid_split(rc[:, 4:5], segs)
-        reg_l = [torch.exp(t * self.scale_exp[i].scale) for i, t in enumerate(T.pyramid_split(rc[:, :4], segs))]
-        return cls_l, cnt_l, reg_l
+        return T.predictor_rows(self.cls_logits, self.reg_pred, self.cnt_logits, c, r, segs, self.scale_exp)
 
     def _train_forward_stock(self, inputs):
         T.stock_fallback("the HeadFCOS GroupNorm layers (widths outside the rows kernels)")
@@ -118,24 +94,7 @@ class HeadFCOS(PlannedModule):
         return cls_l, cnt_l, reg_l
 
     def forward(self, inputs):
-        if self.training:
-            return self.train_forward(inputs)
-        shapes = tuple(tuple(t.shape) for t in inputs)
-        key = ("head",) + shapes + (str(inputs[0].device),)
-
-        def build():
-            plan = engine.Plan(inputs[0].device, self.conv_precision)
-            B, C = shapes[0][0], shapes[0][1]
-            segs = Segs.make(B, [(s[2], s[3]) for s in shapes])
-            pyr = plan.pool.get(segs.rows, C)
-            outs = engine.build_fcos_head(plan, self, pyr, segs)
-            return plan, pyr, segs, outs
-
-        plan, pyr, segs, outs = self._get_plan(key, build)
-        for i, t in enumerate(inputs):
-            copy_in_nchw(pyr, segs, i, t)
-        plan.run()
-        return tuple(pyramid_out(o, segs) for o in outs)
+        return self.train_forward(inputs) if self.training else self._run_head(engine.build_fcos_head, inputs)
 
 
 class FCOS(PlannedModule):
@@ -169,27 +128,15 @@ class FCOS(PlannedModule):
         self.head = HeadFCOS(feature, num_class, 0.01)
         self.backbone_freeze = freeze_bn
         if self.backbone_freeze:
-            for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.eval()
-                    for p in m.parameters():
-                        p.requires_grad = False
+            self.freeze_batchnorm()
 
-    def build_plan(self, B: int, H: int, W: int, device, input_mode=None):
-        plan = engine.Plan(device, self.conv_precision, pair_tuned=getattr(self, "_plan_pair_tuned", False))
-        plan.image_ref = [None]
-        plan.input_mode, plan.canvas_hw = input_mode, (H, W)
-        plan.input_u8 = (self.pixel_mean, self.pixel_std) if input_mode else None
+    def _parts(self):
+        return self.FPN, engine.build_fcos_fpn, engine.build_fcos_head
+
+    def _build_trunk(self, plan, B: int, H: int, W: int):
         if self.efficientnet:
-            feats = engine.build_efficientnet(plan, self.backbone.model, B, H, W, plan.image_ref, keep=(2, 3, 4))[2:]
-        else:
-            feats = engine.build_resnet50(plan, self.backbone.trunk, B, H, W, plan.image_ref)
-        pyr, segs = engine.build_fcos_fpn(plan, self.FPN, feats)
-        for r, _ in feats:
-            plan.pool.put(r)
-        outs = engine.build_fcos_head(plan, self.head, pyr, segs)
-        plan.outs, plan.segs = outs, segs
-        return plan
+            return engine.build_efficientnet(plan, self.backbone.model, B, H, W, plan.image_ref, keep=(2, 3, 4))[2:]
+        return super()._build_trunk(plan, B, H, W)
 
     def enable_stem_training(self):
         """Opt in to the HIP node for the trainable 7x7 stem (backbone.hip_stem_train: the stem kernel forward, fd_stem7x7_bwd_weight_nhwc4 backward)
@@ -200,19 +147,10 @@ class FCOS(PlannedModule):
         return self
 
     def forward(self, x: torch.Tensor, events=None):
-        if self.training:
+        if not self.training:
+            return self._eval_forward(x, events)
+        if self.efficientnet:
             self._check_train_input(x)
-            if self.efficientnet:
-                raise FdError("FCOS(efficientnet=True) is inference-only on the HIP path: the MBConv trunk has no backward "
-                              "kernels (the reference's train.py:92-97 never builds it); call model.eval()")
-            T.PACKS.refresh()        # every parameter's packed conv weights for this step, one launch
-            return self.head.train_forward(self.FPN.train_forward(trunk_train_forward(self.backbone.trunk, x)))
-        chunk = self.plan_batch_limit(x)
-        if x.shape[0] > chunk:
-            return self._forward_chunked(x, chunk)
-        plan = self.plan_for(x)
-        plan.image_ref[0] = x.contiguous()
-        if self.use_graph and plan.graph is None and not events:
-            plan.capture_graph()
-        plan.run(events)
-        return self.outputs_of(plan)
+            raise FdError("FCOS(efficientnet=True) is inference-only on the HIP path: the MBConv trunk has no backward "
+                          "kernels (the reference's train.py:92-97 never builds it); call model.eval()")
+        return self._train_forward(x)

@@ -17,9 +17,9 @@ import torch.nn.functional as F
 from ...ops import ACT_NONE, ACT_RELU, ACT_SILU
 from ... import train_ops as T
 from ...train_ops import conv2d as tconv, conv_bn_act as cba
-from ..backbone.resnet50 import ResNet50v2, trunk_train_forward
+from ..backbone.resnet50 import ResNet50v2
 from ..modules.modules import DepthWiseConv2d, PointWiseConv, ScaleExp, SEBlock
-from ._planned import PlannedModule, copy_in_nchw, pyramid_out
+from ._planned import PlannedModule
 
 
 class HisBlock(nn.Module):
@@ -35,6 +35,15 @@ class HisBlock(nn.Module):
         self.bn1, self.bn2, self.bn3 = nn.BatchNorm2d(half), nn.BatchNorm2d(half), nn.BatchNorm2d(half)
         self.bn4 = nn.BatchNorm2d(feature)
 
+    def _conv12_rows(self, x: torch.Tensor, segs: Segs):
+        """conv1 (+ frozen bn1) and conv2 read the same map: one 2*half-wide launch forward, one data gradient (no gradient add for x) and one weight
+        gradient backward.  Returns (bn1(conv1(x)) before its SiLU, conv2(x)): the halves are channel views of the node's output rows."""
+        sc, sf = T._bn_fold(self.bn1)
+        half = self.conv1.out_channels
+        both = T._ConvRows.apply(x, torch.cat((self.conv1.weight, self.conv2.weight), 0), torch.cat((sc, torch.ones_like(sc))),
+                                 torch.cat((self.conv1.bias * sc + sf, self.conv2.bias)), None, segs, 1, 0, 1, ACT_NONE, T.amp_prec())
+        return both[:, :half], both[:, half:]
+
     def train_forward_rows(self, x: torch.Tensor, segs: Segs):
         """HisBlock on single-level NHWC rows with EVERY op on the HIP kernels, forward and backward: the 1x1 / 3x3 / dilated
         convs (MFMA), the depthwise conv, SE (pool, gate, scale), SiLU / ReLU, and each BatchNorm in whichever mode it is in
@@ -44,12 +53,8 @@ class HisBlock(nn.Module):
             return None
         if (T.bn_is_frozen(self.bn1) and T._dense_ok(self.conv1, x) and T._dense_ok(self.conv2, x) and self.conv1.bias is not None
                 and self.conv2.bias is not None and not T._STOCK):
-            # conv1 (+ frozen bn1) and conv2 read the same map: one 2*half-wide launch forward, one data / weight gradient backward
-            sc, sf = T._bn_fold(self.bn1)
-            half = self.conv1.out_channels
-            both = T._ConvRows.apply(x, torch.cat((self.conv1.weight, self.conv2.weight), 0), torch.cat((sc, torch.ones_like(sc))),
-                                     torch.cat((self.conv1.bias * sc + sf, self.conv2.bias)), None, segs, 1, 0, 1, ACT_NONE, T.amp_prec())
-            x1, x2 = T.act_rows(both[:, :half], ACT_SILU), both[:, half:]
+            x1, x2 = self._conv12_rows(x, segs)
+            x1 = T.act_rows(x1, ACT_SILU)
         else:
             # a SyncBatchNorm's statistics all-reduce is issued by ..._begin and waited for by ..._finish: conv2(x) does not depend on bn1 and is
             # enqueued under it (and, mirrored, its backward under bn1's backward collective) -- train.py:101-103, VERDICT r3 item 7
@@ -78,17 +83,10 @@ class HisBlock(nn.Module):
                 return T.from_rows(out, B, H, W)
         T.stock_fallback("a HisBlock (SE / depthwise / BatchNorm configuration outside the rows kernels)")
         if T.covered(self.conv1, self.bn1, x) and T.covered(self.conv2, None, x) and self.conv1.bias is not None:
-            # conv1 (+ frozen bn1) and conv2 read the same map: one 2*half-wide launch forward, one data gradient (no gradient
-            # add for x) and one weight gradient backward; the halves are channel views of its output
             B, _, H, W = x.shape
-            sc, sf = T._bn_fold(self.bn1)
-            half = self.conv1.out_channels
-            both = T._ConvRows.apply(T.to_rows(x), torch.cat((self.conv1.weight, self.conv2.weight), 0),
-                                     torch.cat((sc, torch.ones_like(sc))),
-                                     torch.cat((self.conv1.bias * sc + sf, self.conv2.bias)), None, Segs.make(B, [(H, W)]), 1, 0, 1,
-                                     ACT_NONE, T.amp_prec())
-            x1 = F.silu(T.from_rows(both[:, :half], B, H, W))    # SiLU stock (its derivative needs the pre-activation)
-            x2 = T.from_rows(both[:, half:], B, H, W)
+            x1, x2 = self._conv12_rows(T.to_rows(x), Segs.make(B, [(H, W)]))
+            x1 = F.silu(T.from_rows(x1, B, H, W))    # SiLU stock (its derivative needs the pre-activation)
+            x2 = T.from_rows(x2, B, H, W)
         else:
             x1 = F.silu(cba(self.conv1, self.bn1, x))
             x2 = tconv(self.conv2, x)
@@ -169,26 +167,7 @@ class HalfInvertedStageFPN(PlannedModule):
 
     def forward(self, x):
         """(C3, C4, C5) NCHW CUDA tensors -> PyramidOut of 5 NCHW-shaped maps (strides 8..128)."""
-        if self.training:
-            return self.train_forward(x)
-        c3, c4, c5 = x
-        key = ("fpn",) + tuple(tuple(t.shape) for t in x) + (str(c3.device),)
-
-        def build():
-            plan = engine.Plan(c3.device, self.conv_precision)
-            ins = []
-            for t in (c3, c4, c5):
-                B, C, H, W = t.shape
-                full, view = engine.padded_input(plan, B * H * W, C)
-                ins.append((full, Segs.make(B, [(H, W)]), view))
-            pyr, segs = engine.build_his_fpn(plan, self, [(r, s) for r, s, _ in ins])
-            return plan, ins, pyr, segs
-
-        plan, ins, pyr, segs = self._get_plan(key, build)
-        for (_, s, view), t in zip(ins, (c3, c4, c5)):
-            copy_in_nchw(view, s, 0, t)
-        plan.run()
-        return pyramid_out(pyr, segs)
+        return self.train_forward(x) if self.training else self._run_fpn(engine.build_his_fpn, x)
 
 
 class HISFCOSHead(PlannedModule):
@@ -225,12 +204,7 @@ class HISFCOSHead(PlannedModule):
         z = T.conv_rows(self.pw2, h, segs, residual=f, out_f16=True)      # (AMP: z feeds the two tower convs only -- stored as f16, read by them as it is)
         c = T.groupnorm_rows(self.cls_conv[1], T.conv_rows(self.cls_conv[0], z, segs), segs, self.cls_conv[2])
         r = T.groupnorm_rows(self.reg_conv[1], T.conv_rows(self.reg_conv[0], z, segs), segs, self.reg_conv[2])
-        cls = T.conv_rows(self.cls_logits, c, segs, pad_out=True)
-        rc = T.conv_rows(T.MergedConv(self.reg_pred, self.cnt_logits), r, segs, pad_out=True)     # [:, :4] boxes, [:, 4] centre-ness
-        cls_l = T.pyramid_split(cls, segs)
-        cnt_l = T.pyramid_split(rc[:, 4:5], segs)
-        reg_l = [torch.exp(t * self.scale_exp[i].scale) for i, t in enumerate(T.pyramid_split(rc[:, :4], segs))]
-        return cls_l, cnt_l, reg_l
+        return T.predictor_rows(self.cls_logits, self.reg_pred, self.cnt_logits, c, r, segs, self.scale_exp)
 
     def _train_forward_stock(self, inputs):
         T.stock_fallback("the HISFCOSHead GroupNorm / depthwise layers (widths outside the rows kernels)")
@@ -247,24 +221,7 @@ class HISFCOSHead(PlannedModule):
 
     def forward(self, inputs):
         """5 pyramid maps (PyramidOut or a list of NCHW CUDA tensors) -> (cls_logits, cnt_logits, reg_preds)."""
-        if self.training:
-            return self.train_forward(inputs)
-        shapes = tuple(tuple(t.shape) for t in inputs)
-        key = ("head",) + shapes + (str(inputs[0].device),)
-
-        def build():
-            plan = engine.Plan(inputs[0].device, self.conv_precision)
-            B, C = shapes[0][0], shapes[0][1]
-            segs = Segs.make(B, [(s[2], s[3]) for s in shapes])
-            pyr = plan.pool.get(segs.rows, C)
-            outs = engine.build_his_head(plan, self, pyr, segs)
-            return plan, pyr, segs, outs
-
-        plan, pyr, segs, outs = self._get_plan(key, build)
-        for i, t in enumerate(inputs):
-            copy_in_nchw(pyr, segs, i, t)
-        plan.run()
-        return tuple(pyramid_out(o, segs) for o in outs)
+        return self.train_forward(inputs) if self.training else self._run_head(engine.build_his_head, inputs)
 
 
 class HalfInvertedStageFCOS(PlannedModule):
@@ -275,27 +232,11 @@ class HalfInvertedStageFCOS(PlannedModule):
         self.fpn = HalfInvertedStageFPN(feature_map, feature)
         self.head = HISFCOSHead(feature, num_classes, 0.01)
         if self.backbone_freeze:
-            for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.eval()
-                    for p in m.parameters():
-                        p.requires_grad = False
+            self.freeze_batchnorm()
             self.backbone.freeze_stages(1)
 
-    def build_plan(self, B: int, H: int, W: int, device, input_mode=None):
-        plan = engine.Plan(device, self.conv_precision, pair_tuned=getattr(self, "_plan_pair_tuned", False))
-        plan.image_ref = [None]
-        plan.input_mode, plan.canvas_hw = input_mode, (H, W)
-        plan.input_u8 = (self.pixel_mean, self.pixel_std) if input_mode else None
-        feats = engine.build_resnet50(plan, self.backbone.trunk, B, H, W, plan.image_ref)
-        plan.marks["backbone_end"] = (0, len(plan.steps))
-        pyr, segs = engine.build_his_fpn(plan, self.fpn, feats)
-        for r, _ in feats:
-            plan.pool.put(r)
-        plan.marks["fpn_end"] = (0, len(plan.steps))
-        outs = engine.build_his_head(plan, self.head, pyr, segs)
-        plan.outs, plan.segs = outs, segs
-        return plan
+    def _parts(self):
+        return self.fpn, engine.build_his_fpn, engine.build_his_head
 
     def enable_stem_training(self):
         """Opt in to the HIP node for a trainable 7x7 stem (backbone.hip_stem_train) instead of the stock-op fallback.  It only matters once the user
@@ -307,18 +248,4 @@ class HalfInvertedStageFCOS(PlannedModule):
         """[B,3,H,W] fp32 CUDA -> (cls_logits, cnt_logits, reg_preds), each a list of 5 NCHW-shaped tensors
         (strides 8..128; reference HISFcos.py:70-74).  The tensors are views of plan-owned buffers and are
         overwritten by the next forward of the same shape."""
-        if self.training:
-            # training: an autograd graph whose nodes are the HIP kernels (train_ops.py: fused conv + frozen BN + ReLU, data /
-            # weight gradients, depthwise, GroupNorm); the losses and the target assignment are HIP kernels too
-            self._check_train_input(x)
-            T.PACKS.refresh()        # every parameter's packed conv weights for this step, one launch
-            return self.head.train_forward(self.fpn.train_forward(trunk_train_forward(self.backbone.trunk, x)))
-        chunk = self.plan_batch_limit(x)
-        if x.shape[0] > chunk:
-            return self._forward_chunked(x, chunk)
-        plan = self.plan_for(x)
-        plan.image_ref[0] = x.contiguous()
-        if self.use_graph and plan.graph is None and not events:
-            plan.capture_graph()
-        plan.run(events)
-        return self.outputs_of(plan)
+        return self._train_forward(x) if self.training else self._eval_forward(x, events)

@@ -25,9 +25,9 @@ import torch.nn as nn
 from ... import engine
 from ... import train_ops as T
 from ..._lib import FdError, Segs
-from ..backbone.resnet50 import ResNet50v2, trunk_train_forward
+from ..backbone.resnet50 import ResNet50v2
 from ..modules.modules import MNBlock, ScaleExp
-from ._planned import PlannedModule, copy_in_nchw, pyramid_out
+from ._planned import PlannedModule
 
 
 def _enable_blocks(root: nn.Module) -> None:
@@ -88,24 +88,7 @@ class LieghtWeightFeaturePyramid_old(PlannedModule):
         if self.training and self.hip_train:
             return self.train_forward(x)
         self._check_eval()
-        c3, c4, c5 = x
-        key = ("FPN",) + tuple(tuple(t.shape) for t in x) + (str(c3.device),)
-
-        def build():
-            plan = engine.Plan(c3.device, self.conv_precision)
-            ins = []
-            for t in (c3, c4, c5):
-                B, C, H, W = t.shape
-                full, view = engine.padded_input(plan, B * H * W, C)
-                ins.append((full, Segs.make(B, [(H, W)]), view))
-            pyr, segs = engine.build_mn_fpn(plan, self, [(r, s) for r, s, _ in ins])
-            return plan, ins, pyr, segs
-
-        plan, ins, pyr, segs = self._get_plan(key, build)
-        for (_, s, view), t in zip(ins, (c3, c4, c5)):
-            copy_in_nchw(view, s, 0, t)
-        plan.run()
-        return pyramid_out(pyr, segs)
+        return self._run_fpn(engine.build_mn_fpn, x)
 
 
 class MNHeadFCOS(PlannedModule):
@@ -143,33 +126,13 @@ class MNHeadFCOS(PlannedModule):
         f = T.mn_block_rows(self.block2, T.mn_block_rows(self.block1, f, segs), segs)
         c = T.groupnorm_rows(self.cls_conv[1], T.conv_rows(self.cls_conv[0], f, segs), segs, self.cls_conv[2])
         r = T.groupnorm_rows(self.reg_conv[1], T.conv_rows(self.reg_conv[0], f, segs), segs, self.reg_conv[2])
-        cls = T.conv_rows(self.cls_logits, c, segs, pad_out=True)
-        rc = T.conv_rows(T.MergedConv(self.reg_pred, self.cnt_logits), r, segs, pad_out=True)     # [:, :4] boxes, [:, 4] centre-ness
-        cls_l = T.pyramid_split(cls, segs)
-        cnt_l = T.pyramid_split(rc[:, 4:5], segs)
-        reg_l = [torch.exp(t * self.scale_exp[i].scale) for i, t in enumerate(T.pyramid_split(rc[:, :4], segs))]
-        return cls_l, cnt_l, reg_l
+        return T.predictor_rows(self.cls_logits, self.reg_pred, self.cnt_logits, c, r, segs, self.scale_exp)
 
     def forward(self, inputs):
         if self.training and self.hip_train:
             return self.train_forward(inputs)
         self._check_eval()
-        shapes = tuple(tuple(t.shape) for t in inputs)
-        key = ("head",) + shapes + (str(inputs[0].device),)
-
-        def build():
-            plan = engine.Plan(inputs[0].device, self.conv_precision)
-            B, C = shapes[0][0], shapes[0][1]
-            segs = Segs.make(B, [(s[2], s[3]) for s in shapes])
-            pyr = plan.pool.get(segs.rows, C)
-            outs = engine.build_mn_head(plan, self, pyr, segs)
-            return plan, pyr, segs, outs
-
-        plan, pyr, segs, outs = self._get_plan(key, build)
-        for i, t in enumerate(inputs):
-            copy_in_nchw(pyr, segs, i, t)
-        plan.run()
-        return tuple(pyramid_out(o, segs) for o in outs)
+        return self._run_head(engine.build_mn_head, inputs)
 
 
 class MNFCOS(PlannedModule):
@@ -184,24 +147,10 @@ class MNFCOS(PlannedModule):
         self.head = MNHeadFCOS(feature, num_class, 0.01)
         self.backbone_freeze = freeze_bn
         if self.backbone_freeze:
-            for m in self.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.eval()
-                    for p in m.parameters():
-                        p.requires_grad = False
+            self.freeze_batchnorm()
 
-    def build_plan(self, B: int, H: int, W: int, device, input_mode=None):
-        plan = engine.Plan(device, self.conv_precision, pair_tuned=getattr(self, "_plan_pair_tuned", False))
-        plan.image_ref = [None]
-        plan.input_mode, plan.canvas_hw = input_mode, (H, W)
-        plan.input_u8 = (self.pixel_mean, self.pixel_std) if input_mode else None
-        feats = engine.build_resnet50(plan, self.backbone.trunk, B, H, W, plan.image_ref)
-        pyr, segs = engine.build_mn_fpn(plan, self.FeaturePyramidNetwork, feats)
-        for r, _ in feats:
-            plan.pool.put(r)
-        outs = engine.build_mn_head(plan, self.head, pyr, segs)
-        plan.outs, plan.segs = outs, segs
-        return plan
+    def _parts(self):
+        return self.FeaturePyramidNetwork, engine.build_mn_fpn, engine.build_mn_head
 
     def enable_training(self, train_stem: bool = False):
         """Opt in to training on the HIP autograd nodes: hip_train on the model, its FPN, its head and every MNBlock.  By default the 7x7 stem (Cin = 3)
@@ -220,21 +169,10 @@ class MNFCOS(PlannedModule):
         return self
 
     def forward(self, x: torch.Tensor, events=None):
-        if self.training:
-            if not self.hip_train:
-                raise FdError("MNFCOS is inference-only on the HIP path as constructed (as shipped the reference's own forward raises, "
-                              "MNFcos.py:233-235 / modules.py:203,215); call model.eval(), or opt in to training on the HIP autograd nodes "
-                              "with model.enable_training()")
-            # training: an autograd graph whose nodes are the HIP kernels, like HalfInvertedStageFCOS.forward
-            self._check_train_input(x)
-            T.PACKS.refresh()        # every parameter's packed conv weights for this step, one launch
-            return self.head.train_forward(self.FeaturePyramidNetwork.train_forward(trunk_train_forward(self.backbone.trunk, x)))
-        chunk = self.plan_batch_limit(x)
-        if x.shape[0] > chunk:
-            return self._forward_chunked(x, chunk)
-        plan = self.plan_for(x)
-        plan.image_ref[0] = x.contiguous()
-        if self.use_graph and plan.graph is None and not events:
-            plan.capture_graph()
-        plan.run(events)
-        return self.outputs_of(plan)
+        if not self.training:
+            return self._eval_forward(x, events)
+        if not self.hip_train:
+            raise FdError("MNFCOS is inference-only on the HIP path as constructed (as shipped the reference's own forward raises, "
+                          "MNFcos.py:233-235 / modules.py:203,215); call model.eval(), or opt in to training on the HIP autograd nodes "
+                          "with model.enable_training()")
+        return self._train_forward(x)      # an autograd graph whose nodes are the HIP kernels, like HalfInvertedStageFCOS.forward

@@ -7,8 +7,10 @@ import torch
 import torch.nn as nn
 
 from ... import engine
+from ... import train_ops as T
 from ..._lib import FdError, Segs
 from ...ops import Rows
+from ..backbone.resnet50 import trunk_train_forward
 
 
 class PyramidOut(list):
@@ -76,6 +78,97 @@ class PlannedModule(nn.Module):
             parts.append([[t.clone() for t in grp] for grp in out])
         return tuple([torch.cat([p[g][lv] for p in parts], 0) for lv in range(5)] for g in range(3))
 
+    def freeze_batchnorm(self) -> None:
+        """Every BatchNorm2d below this module in eval mode with its affine parameters frozen (the detectors' constructors)."""
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.eval()
+                for p in m.parameters():
+                    p.requires_grad = False
+
+    # ---- what a detector (backbone + FPN + head) supplies, and what it gets for it ----
+    def _parts(self):
+        """(the FPN module, its engine.build_*_fpn, the head's engine.build_*_head) of a detector; the head is `self.head`."""
+        raise NotImplementedError
+
+    def _build_trunk(self, plan, B: int, H: int, W: int):
+        """The trunk's plan steps; returns the (rows, segs) of C3, C4, C5."""
+        return engine.build_resnet50(plan, self.backbone.trunk, B, H, W, plan.image_ref)
+
+    def build_plan(self, B: int, H: int, W: int, device, input_mode=None):
+        fpn, build_fpn, build_head = self._parts()
+        plan = engine.Plan(device, self.conv_precision, pair_tuned=getattr(self, "_plan_pair_tuned", False))
+        plan.image_ref = [None]
+        plan.input_mode, plan.canvas_hw = input_mode, (H, W)
+        plan.input_u8 = (self.pixel_mean, self.pixel_std) if input_mode else None
+        feats = self._build_trunk(plan, B, H, W)
+        plan.marks["backbone_end"] = (0, len(plan.steps))
+        pyr, segs = build_fpn(plan, fpn, feats)
+        for r, _ in feats:
+            plan.pool.put(r)
+        plan.marks["fpn_end"] = (0, len(plan.steps))
+        plan.outs, plan.segs = build_head(plan, self.head, pyr, segs), segs
+        return plan
+
+    def _eval_forward(self, x: torch.Tensor, events=None):
+        """The detector's forward in eval mode: the cached plan of this input shape (sub-batches beyond plan_batch_limit), run, its outputs."""
+        chunk = self.plan_batch_limit(x)
+        if x.shape[0] > chunk:
+            return self._forward_chunked(x, chunk)
+        plan = self.plan_for(x)
+        plan.image_ref[0] = x.contiguous()
+        if self.use_graph and plan.graph is None and not events:
+            plan.capture_graph()
+        plan.run(events)
+        return self.outputs_of(plan)
+
+    def _train_forward(self, x: torch.Tensor):
+        """The detector's forward in train mode: an autograd graph whose nodes are the HIP kernels (train_ops.py: fused conv + frozen BN + ReLU, data /
+        weight gradients, depthwise, GroupNorm); the losses and the target assignment are HIP kernels too."""
+        self._check_train_input(x)
+        T.PACKS.refresh()        # every parameter's packed conv weights for this step, one launch
+        return self.head.train_forward(self._parts()[0].train_forward(trunk_train_forward(self.backbone.trunk, x)))
+
+    # ---- stand-alone sub-module calls in eval mode (an FPN or a head called on caller-owned NCHW tensors) ----
+    def _run_fpn(self, build_fpn, x):
+        """(C3, C4, C5) NCHW CUDA tensors -> PyramidOut of 5 NCHW-shaped maps (strides 8..128) through this FPN's own plan."""
+        c3, c4, c5 = x
+        key = ("fpn",) + tuple(tuple(t.shape) for t in x) + (str(c3.device),)     # (the cache is per module: the tag only has to differ from the model plans')
+
+        def build():
+            plan = engine.Plan(c3.device, self.conv_precision)
+            ins = []
+            for t in (c3, c4, c5):
+                B, C, H, W = t.shape
+                full, view = engine.padded_input(plan, B * H * W, C)
+                ins.append((full, Segs.make(B, [(H, W)]), view))
+            pyr, segs = build_fpn(plan, self, [(r, s) for r, s, _ in ins])
+            return plan, ins, pyr, segs
+
+        plan, ins, pyr, segs = self._get_plan(key, build)
+        for (_, s, view), t in zip(ins, (c3, c4, c5)):
+            copy_in_nchw(view, s, 0, t)
+        plan.run()
+        return pyramid_out(pyr, segs)
+
+    def _run_head(self, build_head, inputs):
+        """5 pyramid maps (PyramidOut or a list of NCHW CUDA tensors) -> (cls_logits, cnt_logits, reg_preds) through this head's own plan."""
+        shapes = tuple(tuple(t.shape) for t in inputs)
+        key = ("head",) + shapes + (str(inputs[0].device),)
+
+        def build():
+            plan = engine.Plan(inputs[0].device, self.conv_precision)
+            B, C = shapes[0][0], shapes[0][1]
+            segs = Segs.make(B, [(s[2], s[3]) for s in shapes])
+            pyr = plan.pool.get(segs.rows, C)
+            outs = build_head(plan, self, pyr, segs)
+            return plan, pyr, segs, outs
+
+        plan, pyr, segs, outs = self._get_plan(key, build)
+        for i, t in enumerate(inputs):
+            copy_in_nchw(pyr, segs, i, t)
+        plan.run()
+        return tuple(pyramid_out(o, segs) for o in outs)
 
     @staticmethod
     def _check_image(x: torch.Tensor) -> None:

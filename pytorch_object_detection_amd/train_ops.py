@@ -22,7 +22,10 @@ not keep).  Narrow outputs (class / centre-ness / box logits) are padded to 32 c
 """
 from __future__ import annotations
 
+import collections
+import functools
 import os
+import weakref
 from typing import List, NamedTuple, Optional, Sequence
 
 import torch
@@ -35,15 +38,12 @@ from .ops import ACT_NONE, ACT_RELU, ACT_SILU, Rows
 
 # Under torch.autocast (the reference trains with AMP when cfg['model']['amp'] is set, train.py:175) the HIP nodes keep
 # computing in fp32: inputs are cast up on entry, autocast is off inside, gradients come back in fp32.
-import functools as _functools
-
-
 def _fwd32(fwd):
     """torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32) without its recursive argument walk: under autocast the top-level floating-point CUDA
     tensors are cast to fp32 and the forward runs with autocast off (custom_bwd then runs the backward the same way); otherwise the forward runs as it is.  The nodes'
     arguments are flat (tensors, Segs tables, ints, tuples of fp32 constants), and torch's generic walk over them -- ~1 100 _cast calls per training step -- was 2 ms of
     the 20 ms of host work that bound the AMP step (tools/train_host_time.py)."""
-    @_functools.wraps(fwd)
+    @functools.wraps(fwd)
     def wrapper(ctx, *args):
         ctx._dtype = torch.get_autocast_dtype("cuda")
         ctx._fwd_used_autocast = False
@@ -238,7 +238,6 @@ class _PackCache:
 
     def get(self, w: torch.Tensor, scale: Optional[torch.Tensor] = None, dgrad: bool = False, fmt: ops.WFormat = ops.WFormat.DIRECT) -> Packed:
         """Weights packed in `fmt` (conv_format's choice); dgrad=True = the flipped / transposed / BN-scaled weights of the data gradient."""
-        import weakref
         if isinstance(w, nn.Parameter) and w.is_contiguous():
             self.params[w.data_ptr()] = weakref.ref(w)
         ref = self.params.get(w.data_ptr())
@@ -260,7 +259,6 @@ class _PackCache:
         return e[3]
 
     def refresh(self) -> None:
-        import ctypes as C
         live = {}
         newest: dict = {}        # (param address, shape, format) -> newest data-gradient entry: a re-folded frozen BN (load_state_dict) makes
         for key, e in self.entries.items():      # a new scale tensor and a new entry; the superseded one is dropped here
@@ -367,6 +365,46 @@ def _strided_dgrad(g: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.
     return gx
 
 
+def _dense_launch(x: torch.Tensor, segs: Segs, w: torch.Tensor, y: torch.Tensor, k: int, stride: int, pad: int, dil: int, prec: int, scale=None, shift=None,
+                  res: Optional[torch.Tensor] = None, act=ACT_NONE) -> None:
+    """The forward launch of a dense conv layer from its OIHW weight `w` and its geometry (k, stride, pad, dil), stated once: the weight format, the packed
+    weights (PACKS) and the launch.  y = act(conv(x, w) * scale + shift + res); `segs` is the table of x.  (Its data gradient: _dense_dgrad.)"""
+    _conv_launch(x, segs, PACKS.get(w, fmt=conv_format(w.shape[1], w.shape[0], k, stride, pad, dil, segs, prec)), y, k=k, stride=stride, pad=pad, dil=dil,
+                 scale=scale, shift=shift, res=res, act=act)
+
+
+def _dense_dgrad(g: torch.Tensor, x: torch.Tensor, w: torch.Tensor, scale: Optional[torch.Tensor], segs: Segs, so: Segs, k: int, stride: int, pad: int,
+                 dil: int, prec: int, res: Optional[torch.Tensor] = None, res_mask: bool = False) -> torch.Tensor:
+    """dX rows of a dense conv layer from dY rows `g`, given the layer as its forward saw it: input map x on `segs`, output on `so` (both tables were made by
+    the forward: none is built here), OIHW weight `w`, folded-BN `scale`, geometry k / stride / pad / dil.  `res` is a gradient added to dX, or with res_mask
+    the ReLU output of the layer dX flows into (dX is masked by it).  The rungs:
+      stride 1 and Cout % 32 == 0   the conv kernel on dY over `so` with the channel roles swapped, the flipped / transposed / scaled weights and
+                                    pad' = dil * (k - 1) - pad; `res` rides in its epilogue
+      strided, one level, dil 1     one exact-FLOP launch per parity class (ops.conv_dgrad_strided), `res` in their epilogues
+      what is left on one level     (narrow Cout, dilated + strided) the stock op, then one relu_mask launch or the add; counted by stock_fallback
+      what is left over a pyramid   an error
+    _BottleneckRows never reaches the last two: bottleneck() admits only widths with Cout % 32 == 0 and dilation 1 to the node."""
+    Cout = w.shape[0]
+    if stride == 1 and Cout % 32 == 0:
+        gx = torch.empty_like(x)
+        pad = dil * (k - 1) - pad
+        _conv_launch(g, so, PACKS.get(w, scale, dgrad=True, fmt=conv_format(Cout, w.shape[1], k, 1, pad, dil, so, prec)), gx, k=k, stride=1, pad=pad, dil=dil,
+                     res=res, res_mask=res_mask)
+        return gx
+    if segs.nseg != 1:
+        raise FdError("data gradient of a strided / narrow conv over a pyramid is not supported (pad Cout to 32)")
+    if stride > 1 and dil == 1 and (gx := _strided_dgrad(g, w, scale, segs, k, stride, pad, res=res, res_mask=res_mask, prec=prec)) is not None:
+        return gx
+    stock_fallback(f"the data gradient of a {k}x{k} stride-{stride} conv with Cout={Cout}")
+    weff = w.detach() if scale is None else w.detach() * scale.view(-1, 1, 1, 1)
+    B, (H, W), (Ho, Wo) = segs.batch, segs.level_hw()[0], so.level_hw()[0]
+    gx = to_rows(torch.ops.aten.convolution_backward(from_rows(g, B, Ho, Wo), from_rows(x, B, H, W), weff, None, [stride, stride], [pad, pad], [dil, dil],
+                                                     False, [0, 0], 1, [True, False, False])[0])
+    if res_mask:
+        return relu_mask(gx.contiguous(), res)
+    return gx if res is None else gx + res
+
+
 class _ConvRows(torch.autograd.Function):
     """y = act(conv(x, w) * scale + shift + residual) on rows; scale is a constant (frozen BN), shift may need a gradient."""
 
@@ -385,9 +423,8 @@ class _ConvRows(torch.autograd.Function):
         Cout, _, k, _ = weight.shape
         so = ops.conv_out_segs(segs, k, stride, pad, dil)
         y = torch.empty(so.rows, Cout, dtype=torch.float16 if (f16_io and out_f16) else torch.float32, device=x.device)
-        _conv_launch(x, segs, PACKS.get(weight, fmt=conv_format(x.shape[1], Cout, k, stride, pad, dil, segs, prec)), y, k=k, stride=stride,
-                     pad=pad, dil=dil, scale=scale.float() if scale is not None else None, shift=shift.detach().float().contiguous() if shift is not None else None,
-                     res=residual.contiguous() if residual is not None else None, act=act)
+        _dense_launch(x, segs, weight, y, k, stride, pad, dil, prec, scale=scale.float() if scale is not None else None,
+                      shift=shift.detach().float().contiguous() if shift is not None else None, res=residual.contiguous() if residual is not None else None, act=act)
         ctx.res_dtype = residual.dtype if residual is not None else None
         ctx.save_for_backward(x, weight, scale, y if act == ACT_RELU else None)
         ctx.geom = (segs, so, stride, pad, dil, act, prec)
@@ -407,22 +444,7 @@ class _ConvRows(torch.autograd.Function):
         if ctx.needs_input_grad[4]:
             gres = g if g.dtype == ctx.res_dtype else g.to(ctx.res_dtype)
         if ctx.needs_input_grad[0]:
-            if stride == 1 and Cout % 32 == 0:
-                gx = torch.empty_like(x)
-                _conv_launch(g, so, PACKS.get(weight, scale, dgrad=True, fmt=conv_format(Cout, Cin, k, stride, dil * (k - 1) - pad, dil, so, prec)),
-                             gx, k=k, stride=1, pad=dil * (k - 1) - pad, dil=dil)
-            elif segs.nseg == 1 and stride > 1 and dil == 1 and (gx := _strided_dgrad(g, weight, scale, segs, k, stride, pad, prec=prec)) is not None:
-                pass                                   # strided layer: one exact-FLOP launch per parity class (ops.conv_dgrad_strided)
-            elif segs.nseg == 1:  # what is left (narrow Cout, dilated + strided): stock op for the data gradient
-                stock_fallback(f"the data gradient of a {k}x{k} stride-{stride} conv with Cout={Cout}")
-                weff = weight.detach() if scale is None else weight.detach() * scale.view(-1, 1, 1, 1)
-                B, (H, W), (Ho, Wo) = segs.batch, segs.level_hw()[0], so.level_hw()[0]
-                gx4 = torch.ops.aten.convolution_backward(from_rows(g, B, Ho, Wo), from_rows(x, B, H, W), weff, None,
-                                                          [stride, stride], [pad, pad], [dil, dil], False, [0, 0], 1,
-                                                          [True, False, False])[0]
-                gx = to_rows(gx4)
-            else:
-                raise FdError("data gradient of a strided / narrow conv over a pyramid is not supported (pad Cout to 32)")
+            gx = _dense_dgrad(g, x, weight, scale, segs, so, k, stride, pad, dil, prec)
         if ctx.needs_input_grad[1]:
             gw = ops.conv_wgrad(_r(x), _r(g), segs, Cin=Cin, Cout=Cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale,
                                 oihw=True, precision=prec)
@@ -462,6 +484,17 @@ class MergedConv:
         self.stride, self.padding, self.dilation, self.kernel_size = a.stride, a.padding, a.dilation, a.kernel_size
 
 
+def predictor_rows(cls_logits: nn.Conv2d, reg_pred: nn.Conv2d, cnt_logits: nn.Conv2d, c: torch.Tensor, r: torch.Tensor, segs: Segs, scale_exp):
+    """The predictor tail of an FCOS head over the whole pyramid: class logits from the class tower `c`; box regression and centre-ness from the
+    regression tower `r` in one launch; exp(reg * scale_i) per level.  Returns (cls_l, cnt_l, reg_l), each a list of per-level NCHW-shaped views."""
+    cls = conv_rows(cls_logits, c, segs, pad_out=True)
+    rc = conv_rows(MergedConv(reg_pred, cnt_logits), r, segs, pad_out=True)     # [:, :4] boxes, [:, 4] centre-ness
+    cls_l = pyramid_split(cls, segs)
+    cnt_l = pyramid_split(rc[:, 4:5], segs)
+    reg_l = [torch.exp(t * scale_exp[i].scale) for i, t in enumerate(pyramid_split(rc[:, :4], segs))]
+    return cls_l, cnt_l, reg_l
+
+
 class _BottleneckRows(torch.autograd.Function):
     """A whole ResNet bottleneck with frozen BatchNorm as one autograd node (torchvision Bottleneck.forward):
          y1 = relu(bn1(conv1 x));  y2 = relu(bn2(conv2 y1));  out = relu(bn3(conv3 y2) + (downsample(x) | x))
@@ -483,16 +516,14 @@ class _BottleneckRows(torch.autograd.Function):
         y1 = torch.empty(segs.rows, P, dtype=st, device=dev)
         y2 = torch.empty(so.rows, P, dtype=st, device=dev)
         out = torch.empty(so.rows, C4, dtype=st, device=dev)
-        _conv_launch(x, segs, PACKS.get(w1, fmt=conv_format(w1.shape[1], P, 1, 1, 0, 1, segs, prec)), y1, k=1, stride=1, pad=0, dil=1, scale=c1[0], shift=c1[1], act=ACT_RELU)
-        _conv_launch(y1, segs, PACKS.get(w2, fmt=conv_format(P, P, 3, stride, 1, 1, segs, prec)), y2, k=3, stride=stride, pad=1, dil=1, scale=c2[0],
-                     shift=c2[1], act=ACT_RELU)
+        _dense_launch(x, segs, w1, y1, 1, 1, 0, 1, prec, scale=c1[0], shift=c1[1], act=ACT_RELU)
+        _dense_launch(y1, segs, w2, y2, 3, stride, 1, 1, prec, scale=c2[0], shift=c2[1], act=ACT_RELU)
         if wd is not None:
             idt = torch.empty(so.rows, C4, dtype=st, device=dev)
-            _conv_launch(x, segs, PACKS.get(wd, fmt=conv_format(wd.shape[1], wd.shape[0], 1, stride, 0, 1, segs, prec)), idt, k=1, stride=stride, pad=0, dil=1, scale=cd[0], shift=cd[1])
+            _dense_launch(x, segs, wd, idt, 1, stride, 0, 1, prec, scale=cd[0], shift=cd[1])
         else:
             idt = x
-        _conv_launch(y2, so, PACKS.get(w3, fmt=conv_format(P, C4, 1, 1, 0, 1, so, prec)), out, k=1, stride=1, pad=0, dil=1, scale=c3[0], shift=c3[1], res=idt,
-                     act=ACT_RELU)
+        _dense_launch(y2, so, w3, out, 1, 1, 0, 1, prec, scale=c3[0], shift=c3[1], res=idt, act=ACT_RELU)
         ctx.save_for_backward(x, y1, y2, out, w1, w2, w3, wd, c1[0], c2[0], c3[0], cd[0] if wd is not None else None)
         ctx.geom = (segs, so, stride, prec)
         return out
@@ -511,42 +542,19 @@ class _BottleneckRows(torch.autograd.Function):
                                                                      pad=pad, dil=1, scale=sc, oihw=True, precision=prec)
         if ctx.needs_input_grad[3]:
             gw3 = wg(y2, g, so, P, C4, 1, 1, 0, s3)
-        g2 = torch.empty_like(y2)                                                    # d/d(conv2 output), ReLU-masked in the epilogue
-        _conv_launch(g, so, PACKS.get(w3, s3, dgrad=True, fmt=conv_format(C4, P, 1, 1, 0, 1, so, prec)), g2, k=1, stride=1, pad=0, dil=1, res=y2, res_mask=True)
+        g2 = _dense_dgrad(g, y2, w3, s3, so, so, 1, 1, 0, 1, prec, res=y2, res_mask=True)     # d/d(conv2 output), ReLU-masked in the epilogue
         if ctx.needs_input_grad[2]:
             gw2 = wg(y1, g2, segs, P, P, 3, stride, 1, s2)
-        if stride == 1:
-            g1 = torch.empty_like(y1)
-            _conv_launch(g2, so, PACKS.get(w2, s2, dgrad=True, fmt=conv_format(P, P, 3, 1, 1, 1, so, prec)), g1, k=3, stride=1, pad=1,
-                         dil=1, res=y1, res_mask=True)
-        elif (g1 := _strided_dgrad(g2, w2, s2, segs, 3, stride, 1, res=y1, res_mask=True, prec=prec)) is not None:
-            pass    # strided 3x3: four parity-class launches on the conv kernel, ReLU mask of y1 applied in their epilogues
-        else:   # strided 3x3: stock data gradient, masked separately
-            stock_fallback("the data gradient of a bottleneck's strided 3x3 conv")
-            B, (H, W), (Ho, Wo) = segs.batch, segs.level_hw()[0], so.level_hw()[0]
-            g1 = torch.ops.aten.convolution_backward(from_rows(g2, B, Ho, Wo), from_rows(y1, B, H, W), w2.detach() * s2.view(-1, 1, 1, 1),
-                                                     None, [stride, stride], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
-            g1 = relu_mask(to_rows(g1).contiguous(), y1)
+        # conv2's data gradient, the ReLU mask of y1 in the epilogue (strided: four parity-class launches on the conv kernel)
+        g1 = _dense_dgrad(g2, y1, w2, s2, segs, so, 3, stride, 1, 1, prec, res=y1, res_mask=True)
         if ctx.needs_input_grad[1]:
             gw1 = wg(x, g1, segs, Cin, P, 1, 1, 0, s1)
         if wd is not None and ctx.needs_input_grad[4]:
             gwd = wg(x, g, segs, Cin, C4, 1, stride, 0, sd)
         if need_x:
-            if wd is None:
-                gid = g                                                             # identity path
-            elif stride == 1:
-                gid = torch.empty_like(x)
-                _conv_launch(g, so, PACKS.get(wd, sd, dgrad=True, fmt=conv_format(wd.shape[0], wd.shape[1], 1, 1, 0, 1, so, prec)), gid, k=1, stride=1, pad=0, dil=1)
-            elif (gid := _strided_dgrad(g, wd, sd, segs, 1, stride, 0, prec=prec)) is not None:
-                pass    # 1x1 stride-2 downsample: the (0, 0) parity class is a plain GEMM scattered into a zeroed dX
-            else:
-                stock_fallback("the data gradient of a bottleneck's strided downsample conv")
-                B, (H, W), (Ho, Wo) = segs.batch, segs.level_hw()[0], so.level_hw()[0]
-                gid = to_rows(torch.ops.aten.convolution_backward(from_rows(g, B, Ho, Wo), from_rows(x, B, H, W),
-                                                                   wd.detach() * sd.view(-1, 1, 1, 1), None, [stride, stride], [0, 0],
-                                                                   [1, 1], False, [0, 0], 1, [True, False, False])[0])
-            gx = torch.empty_like(x)                                                # conv1's data gradient + the identity gradient
-            _conv_launch(g1, segs, PACKS.get(w1, s1, dgrad=True, fmt=conv_format(P, Cin, 1, 1, 0, 1, segs, prec)), gx, k=1, stride=1, pad=0, dil=1, res=gid)
+            # identity path, or the downsample's data gradient (1x1 stride 2: the (0, 0) parity class is a plain GEMM scattered into a zeroed dX)
+            gid = g if wd is None else _dense_dgrad(g, x, wd, sd, segs, so, 1, stride, 0, 1, prec)
+            gx = _dense_dgrad(g1, x, w1, s1, segs, segs, 1, 1, 0, 1, prec, res=gid)       # conv1's data gradient + the identity gradient
         return gx, gw1, gw2, gw3, gwd, None, None, None, None, None, None, None
 
 
@@ -890,8 +898,7 @@ class _BatchNormTrainRows(torch.autograd.Function):
 #             all-reduce flies under conv2's data / weight gradient kernels, bn2's under the SE backward).
 # With RCCL the collective runs on its own stream and wait() is a stream dependency; with gloo (tests) wait() blocks the host after the independent
 # launches were enqueued.  SYNC_TRACE records, per collective, how many HIP launches were enqueued between issue and wait (tests assert on it).
-import collections as _collections
-SYNC_TRACE = _collections.deque(maxlen=4096)      # (bounded: a long multi-rank run appends ~200 entries per step; only tests read it)
+SYNC_TRACE = collections.deque(maxlen=4096)      # (bounded: a long multi-rank run appends ~200 entries per step; only tests read it)
 # Unfinished input gradients of deferred SyncBatchNorm backward nodes: data_ptr -> (autograd graph-task id of the backward pass that deferred it, closure that
 # finishes it).  The task id ties an entry to ITS pass: what a pass that raised before its flush left behind is never applied to a later pass's gradient that
 # happens to reuse the address, and is dropped when the next pass defers its first gradient.
