@@ -12,6 +12,7 @@
 //
 // Replaces nn.Conv2d(+BatchNorm2d eval)+ReLU/SiLU(+add) of the reference models (see include/fcosdet.h).
 #include "fd_conv_common.h"
+#include <string>
 
 // GATE: the A operand is multiplied by a per-(image, input channel) gate on its way to LDS (1x1 GEMM layers, single level): the
 // squeeze-excitation gate of an MBConv block folded into its project conv.
@@ -410,6 +411,97 @@ static int launch_conv(const ConvArgs& a, hipStream_t stream) {
     return FD_OK;
 }
 
+// ---- which instantiation a call launches -------------------------------------------------------------------------------------------------------------------------
+// The kernel variant flags (SB belongs to the tile) ...
+enum : unsigned { V_STEM = 1, V_TAG = 2, V_SPLIT = 4, V_GATE = 8, V_GNS = 16, V_H1 = 32, V_GEMM = 64, V_DUAL = 128, V_RUP = 256 };
+
+// ... and the one table of tile shapes: BM x BN = (WGM * TM * 32) x (WGN * TN * 32) on WGM x WGN waves; SB: single LDS buffer.
+template <int ID> struct TileShape;
+#define FD_TILE_SHAPE(id, wgm, wgn, tm, tn, sb) \
+    template <> struct TileShape<id> { static constexpr int WGM = wgm, WGN = wgn, TM = tm, TN = tn; static constexpr bool SB = sb; static constexpr const char* name = &#id[8]; }
+FD_TILE_SHAPE(FD_TILE_128x128, 2, 2, 2, 2, false);
+FD_TILE_SHAPE(FD_TILE_128x64, 2, 2, 2, 1, false);
+FD_TILE_SHAPE(FD_TILE_64x128, 2, 2, 1, 2, false);
+FD_TILE_SHAPE(FD_TILE_64x64, 2, 2, 1, 1, false);
+FD_TILE_SHAPE(FD_TILE_128x32, 4, 1, 1, 1, false);
+FD_TILE_SHAPE(FD_TILE_128x96, 4, 1, 1, 3, false);
+FD_TILE_SHAPE(FD_TILE_128x128_SB, 2, 2, 2, 2, true);
+FD_TILE_SHAPE(FD_TILE_128x64_SB, 2, 2, 2, 1, true);
+FD_TILE_SHAPE(FD_TILE_64x128_SB, 2, 2, 1, 2, true);
+FD_TILE_SHAPE(FD_TILE_256x128, 4, 2, 2, 2, false);
+FD_TILE_SHAPE(FD_TILE_256x128_SB, 4, 2, 2, 2, true);
+FD_TILE_SHAPE(FD_TILE_128x96_SB, 4, 1, 1, 3, true);
+#undef FD_TILE_SHAPE
+
+template <unsigned V, int ID>
+static int launch_tile(const ConvArgs& a, hipStream_t stream) {
+    using T = TileShape<ID>;
+    return launch_conv<T::WGM, T::WGN, T::TM, T::TN, (V & V_STEM) != 0, T::SB, (V & V_TAG) ? 1 : 0, (V & V_SPLIT) != 0, (V & V_GATE) != 0, (V & V_GNS) != 0, (V & V_H1) != 0,
+                       (V & V_GEMM) != 0, (V & V_DUAL) != 0, (V & V_RUP) != 0>(a, stream);
+}
+
+// A kernel variant and the tiles it is built for: exactly these (V, ID) pairs are instantiated, never the cross product (compile time and library size follow the count).
+template <unsigned V, int... IDS>
+struct Variant {
+    static bool has(int tile) { return ((tile == IDS) || ...); }
+    static int launch(int tile, const ConvArgs& a, hipStream_t stream) {     // callers test has(tile) first, or pass the result of an *_auto_tile() below
+        int rc = FD_E_UNSUPPORTED;
+        (void)((tile == IDS && ((rc = launch_tile<V, IDS>(a, stream)), true)) || ...);
+        return rc;
+    }
+    static std::string names() {     // "64x64, 128x64_SB, ..." for the error message of a rejected tile
+        std::string s;
+        ((s += s.empty() ? "" : ", ", s += TileShape<IDS>::name), ...);
+        return s;
+    }
+};
+using Stem = Variant<V_STEM, FD_TILE_128x64>;
+using X2 = Variant<V_GEMM | V_DUAL, FD_TILE_64x64, FD_TILE_128x64_SB, FD_TILE_64x128_SB, FD_TILE_128x128_SB>;
+using Gate = Variant<V_GATE, FD_TILE_128x32, FD_TILE_64x64, FD_TILE_128x64, FD_TILE_128x96, FD_TILE_64x128, FD_TILE_128x128, FD_TILE_64x128_SB>;
+using GateGemm = Variant<V_GATE | V_GEMM, FD_TILE_64x128_SB>;
+using F16x3 = Variant<V_SPLIT, FD_TILE_128x128, FD_TILE_128x64, FD_TILE_64x128, FD_TILE_64x64, FD_TILE_128x32, FD_TILE_128x96, FD_TILE_128x128_SB, FD_TILE_128x64_SB,
+                      FD_TILE_64x128_SB, FD_TILE_256x128, FD_TILE_256x128_SB, FD_TILE_128x96_SB>;
+using F16x3Tag = Variant<V_SPLIT | V_TAG, FD_TILE_128x128, FD_TILE_128x128_SB, FD_TILE_256x128, FD_TILE_256x128_SB>;
+using F16 = Variant<V_SPLIT | V_H1, FD_TILE_128x128, FD_TILE_128x64, FD_TILE_64x128, FD_TILE_64x64, FD_TILE_128x32, FD_TILE_128x96, FD_TILE_128x128_SB>;
+using Fp32Tag = Variant<V_TAG, FD_TILE_128x128, FD_TILE_128x128_SB, FD_TILE_64x128_SB, FD_TILE_128x64_SB>;
+using GnStats = Variant<V_GNS, FD_TILE_64x64, FD_TILE_128x64, FD_TILE_64x128, FD_TILE_64x128_SB, FD_TILE_128x64_SB>;
+using GnStatsGemm = Variant<V_GNS | V_GEMM, FD_TILE_64x128_SB, FD_TILE_128x64_SB>;
+using ResUp = Variant<V_GEMM | V_RUP, FD_TILE_64x64, FD_TILE_128x64_SB, FD_TILE_64x128_SB>;
+using Fp32Gemm = Variant<V_GEMM, FD_TILE_128x128, FD_TILE_128x64, FD_TILE_64x128, FD_TILE_64x64, FD_TILE_128x128_SB, FD_TILE_128x64_SB, FD_TILE_64x128_SB>;      // the 2 x 2-wave tiles
+using Fp32 = Variant<0, FD_TILE_128x128, FD_TILE_128x64, FD_TILE_64x128, FD_TILE_64x64, FD_TILE_128x32, FD_TILE_128x96, FD_TILE_128x128_SB, FD_TILE_128x64_SB,
+                     FD_TILE_64x128_SB, FD_TILE_256x128, FD_TILE_256x128_SB, FD_TILE_128x96_SB>;
+
+// FD_TILE_AUTO resolved per variant (x2, gn_stats and res_mode 2 resolve to one fixed tile at their launch).  Workgroups of a bm x bn tiling:
+static long tile_blocks(const ConvArgs& a, int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn); }
+
+static int fp32_auto_tile(const ConvArgs& a) {      // largest tile that still yields `want` workgroups (1.5 per CU, 256 CUs); tiny maps fall through to 64 x 64
+    if (a.Cout <= 32) return FD_TILE_128x32;
+    const long want = 384;
+    if (a.Cout > 64 && a.Cout <= 96 && tile_blocks(a, 128, 96) >= want) return FD_TILE_128x96;
+    if (a.Cout > 64 && tile_blocks(a, 128, 128) >= want) return FD_TILE_128x128;
+    return tile_blocks(a, 128, 64) >= want ? FD_TILE_128x64 : FD_TILE_64x64;
+}
+
+static int f16_auto_tile(const ConvArgs& a) {
+    if (a.Cout <= 32) return FD_TILE_128x32;
+    if (a.Cout <= 64) return tile_blocks(a, 128, 64) >= 512 ? FD_TILE_128x64 : FD_TILE_64x64;
+    if (a.Cout <= 96) return FD_TILE_128x96;
+    if (tile_blocks(a, 128, 128) >= 512) return FD_TILE_128x128;
+    return tile_blocks(a, 64, 128) >= 256 ? FD_TILE_64x128 : FD_TILE_64x64;
+}
+
+static int f16x3_auto_tile(const ConvArgs& a) { return a.Cout <= 32 ? FD_TILE_128x32 : a.Cout <= 64 ? FD_TILE_64x64 : a.Cout <= 96 ? FD_TILE_128x96 : FD_TILE_64x128; }
+
+static int gate_auto_tile(const ConvArgs& a) {
+    // the GroupNorm-fused form (HISFCOSHead pw2): single-LDS-buffer tiles at three workgroups per CU, as the tuned table picks for the plain layer
+    if (a.gate_b && a.Cout > 64 && tile_blocks(a, 64, 128) >= 512) return FD_TILE_64x128_SB;
+    if (a.Cout <= 32) return FD_TILE_128x32;
+    const long m128 = (a.M + 127) / 128;
+    if (a.Cout <= 64) return m128 < 512 ? FD_TILE_64x64 : FD_TILE_128x64;      // small maps need more workgroups
+    if (a.Cout <= 96 && m128 >= 512) return FD_TILE_128x96;
+    return m128 * ((a.Cout + 127) / 128) < 640 ? FD_TILE_64x128 : FD_TILE_128x128;
+}
+
 static int dispatch_conv(const fd_conv_params* p, ConvArgs& a, bool stem, hipStream_t stream);
 
 extern "C" int32_t fd_conv_workgroups(const fd_conv_params* p) {
@@ -458,8 +550,7 @@ extern "C" int32_t fd_conv2d_nhwc_f32(const fd_conv_params* p, fd_stream_t strea
     if (p->res && p->res_mode == 2) {
         // The half-resolution addend has M / 4 rows: every kernel that is NOT an RUP instantiation would read `res` at all M output rows (out of bounds).  The whole
         // precondition therefore sits HERE, in front of every early return below (gate, x2, split-K, f16 / f16x3, gn_stats, tag 1 and the stem never reach an RUP kernel).
-        FD_REQUIRE(p->tile == FD_TILE_AUTO || p->tile == FD_TILE_64x64 || p->tile == FD_TILE_128x64_SB || p->tile == FD_TILE_64x128_SB, FD_E_UNSUPPORTED,
-                   "fd_conv2d: res_mode 2 is built for tiles 64x64, 128x64_SB, 64x128_SB (got %d)", p->tile);
+        FD_REQUIRE(p->tile == FD_TILE_AUTO || ResUp::has(p->tile), FD_E_UNSUPPORTED, "fd_conv2d: res_mode 2 is built for tiles %s (got %d)", ResUp::names().c_str(), p->tile);
         FD_REQUIRE(!stem && p->KH == 1 && p->KW == 1 && p->stride == 1 && p->pad == 0 && p->in.nseg == 1 && p->Cin % 32 == 0 && p->precision == FD_PREC_F32 &&
                        p->ksplit <= 1 && p->sc_H <= 0 && p->out_H <= 0 && p->out_W <= 0 && !p->gate && !p->gn_stats && !p->x2 && p->tag != 1 &&
                        p->in.H[0] % 2 == 0 && p->in.W[0] % 2 == 0 && p->Cout % 4 == 0 && p->y_cs % 4 == 0 && p->y_co % 4 == 0 && ((uintptr_t)p->y & 15) == 0 &&
@@ -549,13 +640,9 @@ extern "C" int32_t fd_conv2d_nhwc_f32(const fd_conv_params* p, fd_stream_t strea
         a.kt2 = p->Cin / 32; a.x2_bytes = (unsigned)x2b;
         a.KT = (p->Cin + p->x2_Cin) / 32; a.Kpacked = a.KT * 32; a.kt_per = a.KT;
         a.w_bytes = (unsigned)((long)p->Cout * a.Kpacked * 4);
-        switch (p->tile) {      // (the single-buffer GEMM-addressed tiles the bottleneck expansions use)
-            case FD_TILE_64x128_SB: return launch_conv<2, 2, 1, 2, false, true, 0, false, false, false, false, true, true>(a, stream);
-            case FD_TILE_64x64: return launch_conv<2, 2, 1, 1, false, false, 0, false, false, false, false, true, true>(a, stream);
-            case FD_TILE_128x128_SB: return launch_conv<2, 2, 2, 2, false, true, 0, false, false, false, false, true, true>(a, stream);
-            case FD_TILE_AUTO: case FD_TILE_128x64_SB: return launch_conv<2, 2, 2, 1, false, true, 0, false, false, false, false, true, true>(a, stream);
-            default: fd_set_error("fd_conv2d: `x2` is built for tiles 64x64, 128x64_SB, 64x128_SB, 128x128_SB (got %d)", p->tile); return FD_E_UNSUPPORTED;
-        }
+        const int tile = p->tile == FD_TILE_AUTO ? FD_TILE_128x64_SB : p->tile;      // (the single-buffer GEMM-addressed tiles the bottleneck expansions use)
+        FD_REQUIRE(X2::has(tile), FD_E_UNSUPPORTED, "fd_conv2d: `x2` is built for tiles %s (got %d)", X2::names().c_str(), p->tile);
+        return X2::launch(tile, a, stream);
     }
     if (p->io_f16) {     // AMP activations stored as f16 (train.py:175-181 autocast): the single-plane f16 kernels read / write them directly
         FD_REQUIRE(p->precision == FD_PREC_F16 && !stem && !p->gate && !p->gn_stats && !p->x2 && (p->io_f16 & ~7) == 0 && p->tile != FD_TILE_WAVE64 && p->tile != FD_TILE_128x128_PATCH,
@@ -582,20 +669,9 @@ extern "C" int32_t fd_conv2d_nhwc_f32(const fd_conv_params* p, fd_stream_t strea
                    FD_E_INVAL, "fd_conv2d: gate_b must be 16-byte aligned, gate_act in {NONE, RELU, SILU}");
         a.gate = p->gate; a.gate_cs = p->gate_cs; a.gate_hw = p->in.H[0] * p->in.W[0];
         a.gate_b = p->gate_b; a.gate_act = p->gate_b ? p->gate_act : FD_ACT_NONE;
-        // the GroupNorm-fused form (HISFCOSHead pw2): single-LDS-buffer tiles at three workgroups per CU, as the tuned table picks for the plain layer
-        if (p->gate_b && a.Cout > 64 && (long)((a.M + 63) / 64) * ((a.Cout + 127) / 128) >= 512) {   // 64 x 128 SB
-            if (p->Cin % 32 == 0 && !a.sc_on) return launch_conv<2, 2, 1, 2, false, true, 0, false, true, false, false, true>(a, stream);      // (GEMM-addressed loader)
-            return launch_conv<2, 2, 1, 2, false, true, 0, false, true>(a, stream);
-        }
-        if (a.Cout <= 32) return launch_conv<4, 1, 1, 1, false, false, 0, false, true>(a, stream);      // 128 x 32
-        const long m128 = (a.M + 127) / 128;
-        if (a.Cout <= 64) {
-            if (m128 < 512) return launch_conv<2, 2, 1, 1, false, false, 0, false, true>(a, stream);    // 64 x 64: small maps need more workgroups
-            return launch_conv<2, 2, 2, 1, false, false, 0, false, true>(a, stream);                    // 128 x 64
-        }
-        if (a.Cout <= 96 && m128 >= 512) return launch_conv<4, 1, 1, 3, false, false, 0, false, true>(a, stream);      // 128 x 96
-        if (m128 * ((a.Cout + 127) / 128) < 640) return launch_conv<2, 2, 1, 2, false, false, 0, false, true>(a, stream);   // 64 x 128
-        return launch_conv<2, 2, 2, 2, false, false, 0, false, true>(a, stream);                        // 128 x 128
+        const int tile = gate_auto_tile(a);      // (p->tile is not consulted)
+        if (tile == FD_TILE_64x128_SB && p->Cin % 32 == 0 && !a.sc_on) return GateGemm::launch(tile, a, stream);       // (GEMM-addressed loader)
+        return Gate::launch(tile, a, stream);
     }
     if (p->tile == FD_TILE_WAVE64) {     // GEMM-addressed layers as wave-autonomous 64 x 64 tiles (fd_conv_wave.hip)
         FD_REQUIRE(a.is_gemm && p->Cin % 32 == 0 && p->Cout % 32 == 0 && p->precision == FD_PREC_F32 && p->ksplit <= 1 && !a.sc_on && p->out_H <= 0 &&
@@ -636,139 +712,37 @@ extern "C" int32_t fd_conv2d_nhwc_f32(const fd_conv_params* p, fd_stream_t strea
 }
 
 static int dispatch_conv(const fd_conv_params* p, ConvArgs& a, bool stem, hipStream_t stream) {
-
-    if (stem) { FD_REQUIRE(!a.gn_stats, FD_E_UNSUPPORTED, "fd_conv2d: gn_stats on the stem"); return launch_conv<2, 2, 2, 1, true>(a, stream); }       // 128 x 64
+    const bool autot = p->tile == FD_TILE_AUTO;
+    if (stem) { FD_REQUIRE(!a.gn_stats, FD_E_UNSUPPORTED, "fd_conv2d: gn_stats on the stem"); return Stem::launch(FD_TILE_128x64, a, stream); }
     if (p->precision == FD_PREC_F16X3) {   // split-f16: 3 f16 MFMAs per fp32 product (weights pre-split by the caller)
-        FD_REQUIRE(!stem, FD_E_UNSUPPORTED, "fd_conv2d: the stem runs in exact fp32 only");
-        const bool tg = p->tag == 1;
-        switch (p->tile) {
-            case FD_TILE_AUTO:
-                if (a.Cout <= 32) return launch_conv<4, 1, 1, 1, false, false, 0, true>(a, stream);
-                if (a.Cout <= 64) return launch_conv<2, 2, 1, 1, false, false, 0, true>(a, stream);
-                if (a.Cout <= 96) return launch_conv<4, 1, 1, 3, false, false, 0, true>(a, stream);
-                return launch_conv<2, 2, 1, 2, false, false, 0, true>(a, stream);
-            case FD_TILE_128x128:
-                return tg ? launch_conv<2, 2, 2, 2, false, false, 1, true>(a, stream) : launch_conv<2, 2, 2, 2, false, false, 0, true>(a, stream);
-            case FD_TILE_128x128_SB:
-                return tg ? launch_conv<2, 2, 2, 2, false, true, 1, true>(a, stream) : launch_conv<2, 2, 2, 2, false, true, 0, true>(a, stream);
-            case FD_TILE_128x64: return launch_conv<2, 2, 2, 1, false, false, 0, true>(a, stream);
-            case FD_TILE_64x128: return launch_conv<2, 2, 1, 2, false, false, 0, true>(a, stream);
-            case FD_TILE_64x64: return launch_conv<2, 2, 1, 1, false, false, 0, true>(a, stream);
-            case FD_TILE_128x64_SB: return launch_conv<2, 2, 2, 1, false, true, 0, true>(a, stream);
-            case FD_TILE_64x128_SB: return launch_conv<2, 2, 1, 2, false, true, 0, true>(a, stream);
-            case FD_TILE_128x32: return launch_conv<4, 1, 1, 1, false, false, 0, true>(a, stream);
-            case FD_TILE_128x96: return launch_conv<4, 1, 1, 3, false, false, 0, true>(a, stream);
-            case FD_TILE_128x96_SB: return launch_conv<4, 1, 1, 3, false, true, 0, true>(a, stream);
-            case FD_TILE_256x128:
-                return tg ? launch_conv<4, 2, 2, 2, false, false, 1, true>(a, stream) : launch_conv<4, 2, 2, 2, false, false, 0, true>(a, stream);
-            case FD_TILE_256x128_SB:
-                return tg ? launch_conv<4, 2, 2, 2, false, true, 1, true>(a, stream) : launch_conv<4, 2, 2, 2, false, true, 0, true>(a, stream);
-            default: fd_set_error("fd_conv2d: tile id %d has no split-f16 kernel", p->tile); return FD_E_UNSUPPORTED;
-        }
+        const int tile = autot ? f16x3_auto_tile(a) : p->tile;
+        if (p->tag == 1 && F16x3Tag::has(tile)) return F16x3Tag::launch(tile, a, stream);     // other tiles keep the shared symbol
+        FD_REQUIRE(F16x3::has(tile), FD_E_UNSUPPORTED, "fd_conv2d: tile id %d has no split-f16 kernel", p->tile);
+        return F16x3::launch(tile, a, stream);
     }
     if (p->precision == FD_PREC_F16) {   // single-plane f16 products, fp32 accumulation (torch.autocast arithmetic); weights in the FD_PREC_F16X3 packing (hi plane used)
         FD_REQUIRE(!a.gn_stats && !a.gate, FD_E_UNSUPPORTED, "fd_conv2d: FD_PREC_F16 has no gn_stats / gate form");
-        auto blocks = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn); };
-        switch (p->tile) {
-            case FD_TILE_AUTO:
-                if (a.Cout <= 32) return launch_conv<4, 1, 1, 1, false, false, 0, true, false, false, true>(a, stream);
-                if (a.Cout <= 64) return blocks(128, 64) >= 512 ? launch_conv<2, 2, 2, 1, false, false, 0, true, false, false, true>(a, stream)
-                                                                : launch_conv<2, 2, 1, 1, false, false, 0, true, false, false, true>(a, stream);
-                if (a.Cout <= 96) return launch_conv<4, 1, 1, 3, false, false, 0, true, false, false, true>(a, stream);
-                if (blocks(128, 128) >= 512) return launch_conv<2, 2, 2, 2, false, false, 0, true, false, false, true>(a, stream);
-                if (blocks(64, 128) >= 256) return launch_conv<2, 2, 1, 2, false, false, 0, true, false, false, true>(a, stream);
-                return launch_conv<2, 2, 1, 1, false, false, 0, true, false, false, true>(a, stream);
-            case FD_TILE_128x128: return launch_conv<2, 2, 2, 2, false, false, 0, true, false, false, true>(a, stream);
-            case FD_TILE_128x128_SB: return launch_conv<2, 2, 2, 2, false, true, 0, true, false, false, true>(a, stream);
-            case FD_TILE_128x64: return launch_conv<2, 2, 2, 1, false, false, 0, true, false, false, true>(a, stream);
-            case FD_TILE_64x128: return launch_conv<2, 2, 1, 2, false, false, 0, true, false, false, true>(a, stream);
-            case FD_TILE_64x64: return launch_conv<2, 2, 1, 1, false, false, 0, true, false, false, true>(a, stream);
-            case FD_TILE_128x32: return launch_conv<4, 1, 1, 1, false, false, 0, true, false, false, true>(a, stream);
-            case FD_TILE_128x96: return launch_conv<4, 1, 1, 3, false, false, 0, true, false, false, true>(a, stream);
-            default: fd_set_error("fd_conv2d: tile id %d has no f16 kernel", p->tile); return FD_E_UNSUPPORTED;
-        }
+        const int tile = autot ? f16_auto_tile(a) : p->tile;
+        FD_REQUIRE(F16::has(tile), FD_E_UNSUPPORTED, "fd_conv2d: tile id %d has no f16 kernel", p->tile);
+        return F16::launch(tile, a, stream);
     }
     FD_REQUIRE(p->precision == FD_PREC_F32, FD_E_INVAL, "fd_conv2d: unknown precision %d", p->precision);
-    if (p->tag == 1) {  // profiling tag: same code under its own kernel symbol (TAG = 1) so rocprofv3 --stats isolates it
-        switch (p->tile) {
-            case FD_TILE_128x128: return launch_conv<2, 2, 2, 2, false, false, 1>(a, stream);
-            case FD_TILE_128x128_SB: return launch_conv<2, 2, 2, 2, false, true, 1>(a, stream);
-            case FD_TILE_64x128_SB: return launch_conv<2, 2, 1, 2, false, true, 1>(a, stream);
-            case FD_TILE_128x64_SB: return launch_conv<2, 2, 2, 1, false, true, 1>(a, stream);
-            default: break;  // other tiles keep the shared symbol
-        }
-    }
+    // profiling tag: same code under its own kernel symbol (TAG = 1) so rocprofv3 --stats isolates it; other tiles keep the shared symbol
+    if (p->tag == 1 && Fp32Tag::has(p->tile)) return Fp32Tag::launch(p->tile, a, stream);
     if (a.gn_stats) {   // row-group statistics in the epilogue: dedicated instantiations of the one- / two-sub-tile tiles
-        if (a.is_gemm && p->Cin % 32 == 0 && !a.sc_on) {     // (GEMM-addressed loader for the tiles the fused head uses)
-            switch (p->tile) {
-                case FD_TILE_64x128_SB: return launch_conv<2, 2, 1, 2, false, true, 0, false, false, true, false, true>(a, stream);
-                case FD_TILE_AUTO: case FD_TILE_128x64_SB: return launch_conv<2, 2, 2, 1, false, true, 0, false, false, true, false, true>(a, stream);
-                default: break;
-            }
-        }
-        switch (p->tile) {
-            case FD_TILE_64x64: return launch_conv<2, 2, 1, 1, false, false, 0, false, false, true>(a, stream);
-            case FD_TILE_128x64: return launch_conv<2, 2, 2, 1, false, false, 0, false, false, true>(a, stream);
-            case FD_TILE_64x128: return launch_conv<2, 2, 1, 2, false, false, 0, false, false, true>(a, stream);
-            case FD_TILE_64x128_SB: return launch_conv<2, 2, 1, 2, false, true, 0, false, false, true>(a, stream);
-            case FD_TILE_AUTO: case FD_TILE_128x64_SB: return launch_conv<2, 2, 2, 1, false, true, 0, false, false, true>(a, stream);
-            default: fd_set_error("fd_conv2d: gn_stats is built for tiles 64x64, 128x64(_SB), 64x128(_SB), WAVE64 and WINOGRAD (got %d)", p->tile); return FD_E_UNSUPPORTED;
-        }
+        const int tile = autot ? FD_TILE_128x64_SB : p->tile;
+        if (a.is_gemm && p->Cin % 32 == 0 && !a.sc_on && GnStatsGemm::has(tile)) return GnStatsGemm::launch(tile, a, stream);    // (the tiles the fused head uses)
+        FD_REQUIRE(GnStats::has(tile), FD_E_UNSUPPORTED, "fd_conv2d: gn_stats is built for tiles 64x64, 128x64(_SB), 64x128(_SB), WAVE64 and WINOGRAD (got %d)", p->tile);
+        return GnStats::launch(tile, a, stream);
     }
-    if (p->res && p->res_mode == 2) {
-        // the upsampled addend of an FPN lateral: 1x1 stride-1 unpadded fp32 layers on one level with even H, W, vector epilogue, no split-K
-        FD_REQUIRE(a.is_gemm && p->in.nseg == 1 && p->Cin % 32 == 0 && p->precision == FD_PREC_F32 && p->ksplit <= 1 && !a.sc_on && p->out_H <= 0 && !p->gate &&
-                       !p->gn_stats && !p->x2 && a.vec_epi && p->tag != 1 && p->in.H[0] % 2 == 0 && p->in.W[0] % 2 == 0,
-                   FD_E_UNSUPPORTED, "fd_conv2d: res_mode 2 (half-resolution addend) needs an fp32 1x1 stride-1 unpadded single-level conv with even H, W, Cin %% 32 == 0, "
-                                     "16-byte views, no split-K / scatter / gate / gn_stats / x2");
+    if (p->res && p->res_mode == 2) {   // the upsampled addend of an FPN lateral (preconditions: fd_conv2d_nhwc_f32, in front of its early returns)
         FD_REQUIRE((long)p->in.batch * (p->in.H[0] / 2) * (p->in.W[0] / 2) * p->res_cs < (1L << 31), FD_E_UNSUPPORTED, "fd_conv2d: residual exceeds 2^31 elements");
         a.res_up = 1;
-        switch (p->tile) {
-            case FD_TILE_64x64: return launch_conv<2, 2, 1, 1, false, false, 0, false, false, false, false, true, false, true>(a, stream);
-            case FD_TILE_128x64_SB: return launch_conv<2, 2, 2, 1, false, true, 0, false, false, false, false, true, false, true>(a, stream);
-            case FD_TILE_AUTO: case FD_TILE_64x128_SB: return launch_conv<2, 2, 1, 2, false, true, 0, false, false, false, false, true, false, true>(a, stream);
-            default: fd_set_error("fd_conv2d: res_mode 2 is built for tiles 64x64, 128x64_SB, 64x128_SB (got %d)", p->tile); return FD_E_UNSUPPORTED;
-        }
+        return ResUp::launch(autot ? FD_TILE_64x128_SB : p->tile, a, stream);
     }
-    // GEMM-addressed fp32 layers (1x1, stride 1, no padding, Cin % 32 == 0, no gate): the loader compiled without the tap / bounds arithmetic
+    // GEMM-addressed fp32 layers (1x1, no padding, Cin % 32 == 0, no gate): the loader compiled without the tap / bounds arithmetic
     const bool pointwise = !stem && p->KH == 1 && p->KW == 1 && p->pad == 0;     // any stride: one input address per output row
-    if (pointwise && p->Cin % 32 == 0 && !a.gate && !a.sc_on) {
-        switch (p->tile) {
-            case FD_TILE_128x128: return launch_conv<2, 2, 2, 2, false, false, 0, false, false, false, false, true>(a, stream);
-            case FD_TILE_128x64: return launch_conv<2, 2, 2, 1, false, false, 0, false, false, false, false, true>(a, stream);
-            case FD_TILE_64x128: return launch_conv<2, 2, 1, 2, false, false, 0, false, false, false, false, true>(a, stream);
-            case FD_TILE_64x64: return launch_conv<2, 2, 1, 1, false, false, 0, false, false, false, false, true>(a, stream);
-            case FD_TILE_128x128_SB: return launch_conv<2, 2, 2, 2, false, true, 0, false, false, false, false, true>(a, stream);
-            case FD_TILE_128x64_SB: return launch_conv<2, 2, 2, 1, false, true, 0, false, false, false, false, true>(a, stream);
-            case FD_TILE_64x128_SB: return launch_conv<2, 2, 1, 2, false, true, 0, false, false, false, false, true>(a, stream);
-            default: break;
-        }
-    }
-    switch (p->tile) {
-        case FD_TILE_AUTO: break;
-        case FD_TILE_128x128: return launch_conv<2, 2, 2, 2, false>(a, stream);
-        case FD_TILE_128x64: return launch_conv<2, 2, 2, 1, false>(a, stream);
-        case FD_TILE_64x128: return launch_conv<2, 2, 1, 2, false>(a, stream);
-        case FD_TILE_64x64: return launch_conv<2, 2, 1, 1, false>(a, stream);
-        case FD_TILE_128x32: return launch_conv<4, 1, 1, 1, false>(a, stream);
-        case FD_TILE_128x96: return launch_conv<4, 1, 1, 3, false>(a, stream);
-        case FD_TILE_128x96_SB: return launch_conv<4, 1, 1, 3, false, true>(a, stream);
-        case FD_TILE_128x128_SB: return launch_conv<2, 2, 2, 2, false, true>(a, stream);
-        case FD_TILE_128x64_SB: return launch_conv<2, 2, 2, 1, false, true>(a, stream);
-        case FD_TILE_64x128_SB: return launch_conv<2, 2, 1, 2, false, true>(a, stream);
-        case FD_TILE_256x128: return launch_conv<4, 2, 2, 2, false, false>(a, stream);
-        case FD_TILE_256x128_SB: return launch_conv<4, 2, 2, 2, false, true>(a, stream);
-        default: fd_set_error("fd_conv2d: unknown tile id %d", p->tile); return FD_E_INVAL;
-    }
-    if (a.Cout <= 32) return launch_conv<4, 1, 1, 1, false>(a, stream);   // 128 x 32
-    // Largest tile that still yields >= 2 workgroups per CU (256 CUs); tiny maps fall through to 64 x 64.
-    auto blocks = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.Cout + bn - 1) / bn); };
-    const long want = 384;
-    if (a.Cout > 64 && a.Cout <= 96 && blocks(128, 96) >= want) return launch_conv<4, 1, 1, 3, false>(a, stream);  // 128 x 96
-    if (a.Cout > 64 && blocks(128, 128) >= want) return launch_conv<2, 2, 2, 2, false>(a, stream);
-    if (blocks(128, 64) >= want || a.Cout <= 64) {
-        if (a.Cout <= 64 && blocks(128, 64) < want) return launch_conv<2, 2, 1, 1, false>(a, stream);
-        return launch_conv<2, 2, 2, 1, false>(a, stream);             // 128 x 64
-    }
-    return launch_conv<2, 2, 1, 1, false>(a, stream);                 // 64 x 64
+    if (pointwise && p->Cin % 32 == 0 && !a.gate && !a.sc_on && Fp32Gemm::has(p->tile)) return Fp32Gemm::launch(p->tile, a, stream);
+    FD_REQUIRE(autot || Fp32::has(p->tile), FD_E_INVAL, "fd_conv2d: unknown tile id %d", p->tile);
+    return Fp32::launch(autot ? fp32_auto_tile(a) : p->tile, a, stream);
 }

@@ -43,19 +43,22 @@ def test_conv_f16_operands_fp32_accumulate(case):
     rs = [torch.randn(B, Cout, a, b, generator=gen) for a, b in so.level_hw()]
     xr = ops.Rows(torch.cat([t.permute(0, 2, 3, 1).reshape(-1, Cin) for t in xs]).to(DEV))
     rr = ops.Rows(torch.cat([t.permute(0, 2, 3, 1).reshape(-1, Cout) for t in rs]).to(DEV)) if use_res else None
-    y = ops.new_rows(so.rows, Cout, DEV)
     wp = ops.pack_conv_weight_hip(w.to(DEV), f16=True)
-    ops.conv_call(xr, segs, wp, y, Cin=Cin, Cout=Cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale.to(DEV), shift=shift.to(DEV), res=rr, act=act,
-                  precision=_lib.PREC_F16)()
-    got = y.tensor().cpu()
-    for lv, ((a, b), x, r) in enumerate(zip(so.level_hw(), xs, rs)):
+    refs = []
+    for x, r in zip(xs, rs):
         ref = F.conv2d(h(x), h(w), None, stride, pad, dil) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
         if use_res:
             ref = ref + r
-        if act == ACT_RELU:
-            ref = F.relu(ref)
-        g = got[so.m_start[lv]:so.m_start[lv + 1]].reshape(B, a, b, Cout).permute(0, 3, 1, 2)
-        np.testing.assert_allclose(g.numpy(), ref.numpy(), atol=2e-5, rtol=2e-5, err_msg=f"level {lv}")
+        refs.append(F.relu(ref) if act == ACT_RELU else ref)
+    # the two smallest cases run every tile id FD_PREC_F16 is built for (Cout = 80 leaves a partial N tile at every width), the others the built-in choice (0)
+    for tile in (range(8) if case in (CASES[1], CASES[5]) else (0,)):
+        y = ops.Rows(torch.full((so.rows, Cout), float("nan"), device=DEV))       # (not the previous tile's result in a recycled buffer)
+        ops.conv_call(xr, segs, wp, y, Cin=Cin, Cout=Cout, k=k, stride=stride, pad=pad, dil=dil, scale=scale.to(DEV), shift=shift.to(DEV), res=rr, act=act,
+                      precision=_lib.PREC_F16, tile=tile)()
+        got = y.tensor().cpu()
+        for lv, ((a, b), ref) in enumerate(zip(so.level_hw(), refs)):
+            g = got[so.m_start[lv]:so.m_start[lv + 1]].reshape(B, a, b, Cout).permute(0, 3, 1, 2)
+            np.testing.assert_allclose(g.numpy(), ref.numpy(), atol=2e-5, rtol=2e-5, err_msg=f"tile {tile} level {lv}")
     # and it is NOT the fp32 result (the operands really were rounded)
     ref32 = F.conv2d(xs[0], w, None, stride, pad, dil)
     assert float((F.conv2d(h(xs[0]), h(w), None, stride, pad, dil) - ref32).abs().max()) > 1e-4

@@ -532,6 +532,39 @@ def test_round5_entry_points_validate_on_the_host():
     assert ops.f16k64_ok(128, 80) and not ops.f16k64_ok(96, 64)
 
 
+def test_conv_variants_reject_the_tiles_they_are_not_built_for():
+    """fd_conv.hip instantiates each kernel variant for its own list of tiles: a forced tile outside that list is refused on the host, before any
+    launch, with FD_E_UNSUPPORTED (an id that names no tile at all: FD_E_INVAL).  ONLY refused pairs may be listed here -- the pointers are fake."""
+    lib = _lib.lib()
+
+    def layer(k, tile, **fields):
+        p = _lib.ConvParams()
+        p.x, p.w, p.y = 4096, 8192, 12288
+        p.segs = _lib.Segs.make(2, [(16, 16)])
+        p.Cin, p.Cout, p.KH, p.KW, p.stride, p.pad, p.dil = 64, 64, k, k, 1, k // 2, 1
+        p.x_cs, p.y_cs, p.tile = 64, 64, tile
+        for name, value in fields.items():
+            setattr(p, name, value)
+        return lib.fd_conv2d_nhwc_f32(ctypes.byref(p), None), lib.fd_last_error()
+
+    for k in (1, 3):
+        for tile in (1, 5, 6, 7, 10, 11, 12):
+            rc, msg = layer(k, tile, gn_stats=16384, gn_groups=8)
+            assert rc == _lib.E_UNSUPPORTED and b"gn_stats is built for" in msg, (k, tile, rc, msg)
+        for tile in (8, 9, 10, 11, 12):
+            rc, msg = layer(k, tile, precision=_lib.PREC_F16)
+            assert rc == _lib.E_UNSUPPORTED and b"no f16 kernel" in msg, (k, tile, rc, msg)
+        for tile in (-1, 19, 20):
+            rc, msg = layer(k, tile)
+            assert rc == _lib.E_INVAL and b"unknown tile id" in msg, (k, tile, rc, msg)
+    for tile in (1, 2, 3, 5, 6, 10, 11, 12):
+        rc, msg = layer(1, tile, x2=16384, x2_cs=64, x2_Cin=64, x2_stride=1, x2_H=16, x2_W=16)
+        assert rc == _lib.E_UNSUPPORTED and b"`x2` is built for tiles 64x64, 128x64_SB, 64x128_SB, 128x128_SB" in msg, (tile, rc, msg)
+    for tile in (1, 2, 3, 5, 6, 7, 10, 11, 12):
+        rc, msg = layer(1, tile, res=16384, res_cs=64, res_mode=2)
+        assert rc == _lib.E_UNSUPPORTED and b"res_mode 2 is built for tiles 64x64, 128x64_SB, 64x128_SB" in msg, (tile, rc, msg)
+
+
 def test_graphed_step_refuses_host_tensors():
     """train_graph.GraphedStep records a training step as a HIP graph: without CUDA tensors there is nothing to record -- it must say so before touching a stream."""
     import torch

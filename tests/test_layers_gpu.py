@@ -965,7 +965,7 @@ def test_conv1x1_wave_tile_is_bit_identical_to_the_workgroup_kernel(case):
 
 
 # ------------------------------------------------------------------------------------------------ GroupNorm fused into its neighbours
-@pytest.mark.parametrize("kind", ["tile4", "tile8", "tile9", "wave", "winograd", "winograd_d2"])
+@pytest.mark.parametrize("kind", ["tile4", "tile8", "tile9", "wave", "winograd", "winograd_d2", "tile2", "tile3", "auto"])
 @pytest.mark.parametrize("G", [32, 64])
 def test_conv_epilogue_row_group_statistics(kind, G):
     """fd_conv_params.gn_stats: per output row and channel group the (sum, sum of squares) of the stored values, from the epilogue of every
@@ -983,7 +983,7 @@ def test_conv_epilogue_row_group_statistics(kind, G):
     w = (torch.randn(Cout, Cin, k, k, generator=gen) / np.sqrt(Cin * k * k)).to(DEV)
     res = ops.Rows(torch.randn(segs.rows, Cout, generator=gen).to(DEV))
     shift = torch.randn(Cout, generator=gen).to(DEV)
-    tile = {"tile4": 4, "tile8": 8, "tile9": 9, "wave": _lib.WAVE_TILE}.get(kind, _lib.WINO_TILE)
+    tile = {"tile2": 2, "tile3": 3, "tile4": 4, "tile8": 8, "tile9": 9, "auto": 0, "wave": _lib.WAVE_TILE}.get(kind, _lib.WINO_TILE)
     wp = ops.pack_conv_weight_wino(w) if wino else ops.pack_conv_weight(w)
     wf = ops.pack_conv_weight_wave(w) if kind == "wave" else None
     outs = []
