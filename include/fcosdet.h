@@ -420,6 +420,35 @@ int32_t fd_dwconv_dilated_bwd_weight_nhwc(const float* x, int32_t x_cs, int32_t 
                                           float* dw, int32_t C, int32_t K, int32_t dil, const float* scale, int32_t layout,
                                           const fd_segs* segs, void* workspace, fd_stream_t stream);
 
+/* Modulated deformable convolution ("DCNv2"): the sampler of the reference's DeformableConv2d (model/modules/modules.py:219-277, which calls
+ * torchvision.ops.deform_conv2d) in front of the dense-conv GEMM.  groups = offset_groups = 1, square kernel, single level, fp32 maps.
+ *   Ho = (H + 2*pad - dil*(K-1) - 1) / stride + 1, Wo likewise; tap t = i*K + j; offset rows [B*Ho*Wo][2*K*K]: channel 2t = dy, 2t+1 = dx;
+ *   y = ho*stride - pad + i*dil + dy,  x = wo*stride - pad + j*dil + dx
+ *   s_c(y, x) = 0 unless -1 < y < H and -1 < x < W (a NaN or infinite offset counts as outside); else with y0 = floor(y), x0 = floor(x), ly = y - y0, lx = x - x0:
+ *               (1-ly)(1-lx) x[y0][x0] + (1-ly) lx x[y0][x0+1] + ly (1-lx) x[y0+1][x0] + ly lx x[y0+1][x0+1], a corner outside the map contributing 0
+ *   cols[m][t*C + c] = mask[m][t] * s_c(y, x)      (mask = NULL: 1; mask_act = 1: `mask` holds logits v and the factor is 2 * sigmoid(v))
+ * so that the layer is the 1x1 conv of `cols` (K*K*C channels, tap major then channel) with weight.permute(0, 2, 3, 1), and fd_conv2d_bwd_weight_f32 on
+ * `cols` gives the weight gradient as [Cout][K][K][C].  This rule is the project's own statement of torchvision's published algorithm; it is not pinned
+ * against torchvision (absent from this stack) but against the float64 reference tests/deform_ref.py.
+ * x, cols (and dcols, d_x below) are channel views read four channels at a time (C % 4 == 0, cs and co multiples of 4, 16-byte aligned); offset and
+ * mask (d_offset, d_mask) are channel views read one float at a time: any co >= 0 with cs >= co + 2*K*K (K*K) -- two slices of one side-conv output.
+ * 1 <= K <= 7, 1 <= stride <= 4, 0 <= pad <= 7, 1 <= dil <= 4.  A bad argument returns FD_E_INVAL before any launch. */
+int32_t fd_deform_im2col_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* offset, int32_t off_cs, int32_t off_co,
+                              const float* mask, int32_t mask_cs, int32_t mask_co, int32_t mask_act, float* cols, int32_t cols_cs,
+                              int32_t cols_co, int32_t B, int32_t H, int32_t W, int32_t C, int32_t K, int32_t stride, int32_t pad,
+                              int32_t dil, fd_stream_t stream);
+/* Backward of the sampler above from dcols (the gradient of `cols`): the exact derivatives of the piecewise-bilinear rule with floor() held constant
+ * (at an integer coordinate: the ly = 0 / lx = 0 side); a fully outside sample gives zero to offset, mask and input.
+ *   d_offset rows [B*Ho*Wo][2*K*K], d_mask rows [B*Ho*Wo][K*K] (with mask_act = 1: the gradient of the logits); mask and d_mask are both given or both NULL.
+ *   Sums over the channels in a fixed order: deterministic, bit-identical from run to run.
+ *   d_x (optional, NULL skips it) rows [B*H*W][C]: the caller zeroes it, the kernel ADDS each sample's four corner shares with fp32 atomic adds
+ *   (one hardware add each).  They arrive in no fixed order: d_x is the one result of this layer that is not bit-reproducible. */
+int32_t fd_deform_bwd_nhwc(const float* dcols, int32_t dcols_cs, int32_t dcols_co, const float* x, int32_t x_cs, int32_t x_co,
+                           const float* offset, int32_t off_cs, int32_t off_co, const float* mask, int32_t mask_cs, int32_t mask_co,
+                           int32_t mask_act, float* d_offset, int32_t doff_cs, int32_t doff_co, float* d_mask, int32_t dmask_cs,
+                           int32_t dmask_co, float* d_x, int32_t dx_cs, int32_t dx_co, int32_t B, int32_t H, int32_t W, int32_t C,
+                           int32_t K, int32_t stride, int32_t pad, int32_t dil, fd_stream_t stream);
+
 /* Depthwise k x k convolution with stride and asymmetric zero padding, y = act(dw(x)*scale + shift): the depthwise
  * stage of an EfficientNet MBConv block (efficientnet_pytorch 0.7.1 MBConvBlock._depthwise_conv + _bn1 + swish, wrapped by
  * the reference's model/backbone/efficientnetv1.py:11-26; Conv2dStaticSamePadding pads (pad//2, pad - pad//2), i.e. more at

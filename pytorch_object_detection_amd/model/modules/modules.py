@@ -135,6 +135,97 @@ class MNBlock(nn.Module):
         return out.tensor().view(B, H, W, C).permute(0, 3, 1, 2).clone()
 
 
+def _nhwc_rows(t: torch.Tensor) -> torch.Tensor:
+    B, Cc, H, W = t.shape
+    return t.permute(0, 2, 3, 1).reshape(B * H * W, Cc)
+
+
+def deform_conv2d(input: torch.Tensor, offset: torch.Tensor, weight: torch.Tensor, bias=None, stride=1, padding=0, dilation=1, mask=None) -> torch.Tensor:
+    """Modulated deformable convolution (DCNv2) on the HIP kernels, with the argument order of torchvision.ops.deform_conv2d, which it stands in for
+    (torchvision is not part of this stack).  NCHW in and out: input [B, Cin, H, W], offset [B, 2*K*K, Ho, Wo] (channel 2t = row offset, 2t + 1 = column
+    offset of tap t = i*K + j), mask [B, K*K, Ho, Wo] (already activated) or None, weight [Cout, Cin, K, K], bias [Cout] or None.  The sampling rule is
+    stated in include/fcosdet.h (fd_deform_im2col_nhwc) and DESIGN 4.3f.  Differentiable in input, offset, mask, weight and bias; the input gradient is
+    summed with fp32 atomics and is not bit-reproducible, everything else is.  Coverage: Cin % 32 == 0, square kernel, groups = offset_groups = 1,
+    1 <= K <= 7, 1 <= stride, dilation <= 4, 0 <= padding <= 7, fp32 CUDA tensors; anything else raises FdError."""
+    from ... import ops, train_ops as T
+    for t in (input, offset, weight, bias, mask):
+        if t is not None:
+            T._need_cuda(t)
+
+    def one(v, what):
+        if isinstance(v, (tuple, list)):
+            if len(v) != 2 or v[0] != v[1]:
+                raise FdError(f"deform_conv2d: {what} must be the same in both directions (got {tuple(v)})")
+            v = v[0]
+        return int(v)
+
+    s, p, d = one(stride, "stride"), one(padding, "padding"), one(dilation, "dilation")
+    if input.dim() != 4 or offset.dim() != 4 or weight.dim() != 4 or (mask is not None and mask.dim() != 4):
+        raise FdError("deform_conv2d: NCHW tensors expected")
+    B, C, H, W = input.shape
+    Cout, Cw, K, K2 = weight.shape
+    if K != K2 or Cw != C:
+        raise FdError(f"deform_conv2d: square kernel and groups = 1 expected (input has {C} channels, weight is {tuple(weight.shape)})")
+    if not (1 <= K <= 7 and 1 <= s <= 4 and 0 <= p <= 7 and 1 <= d <= 4):
+        raise FdError(f"deform_conv2d: 1 <= K <= 7, 1 <= stride <= 4, 0 <= padding <= 7, 1 <= dilation <= 4 expected (K={K} stride={s} padding={p} dilation={d})")
+    Ho, Wo = ops.deform_out_hw(H, W, K, s, p, d)
+    if tuple(offset.shape) != (B, 2 * K * K, Ho, Wo):
+        raise FdError(f"deform_conv2d: offset must be {(B, 2 * K * K, Ho, Wo)} (offset_groups = 1), got {tuple(offset.shape)}")
+    if mask is not None and tuple(mask.shape) != (B, K * K, Ho, Wo):
+        raise FdError(f"deform_conv2d: mask must be {(B, K * K, Ho, Wo)}, got {tuple(mask.shape)}")
+    if bias is not None and tuple(bias.shape) != (Cout,):
+        raise FdError(f"deform_conv2d: bias must be [{Cout}]")
+    y = T.deform_conv_rows(_nhwc_rows(input), _nhwc_rows(offset), _nhwc_rows(mask) if mask is not None else None, weight, bias, B, H, W, s, p, d)
+    return T.from_rows(y, B, Ho, Wo)
+
+
+class DeformableConv2d(nn.Module):
+    """Modulated deformable convolution layer of the reference (model/modules/modules.py:219-277; imported by model/od/MNFcos.py:6): offset_conv predicts
+    2*K*K offsets per output pixel, modulator_conv K*K logits m, and regular_conv's weights are applied to the input sampled bilinearly at the offset tap
+    positions, each tap weighted by 2 * sigmoid(m) (deform_conv2d above).  Same constructor, attributes and state-dict keys as the reference; both side
+    convs start at zero, so a fresh layer computes the plain convolution.  forward runs on the HIP kernels with autograd (train_ops.deformable_conv2d:
+    three launches forward), also under torch.autocast and inside a captured training step.  Coverage: in_channels % 32 == 0, square kernel, fp32
+    parameters, a CUDA input; anything else raises FdError.  FD_TRAIN_STOCK_CONV=1 raises too: the stock-op form of this layer is torchvision's op, and
+    torchvision is not part of this stack."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False):
+        super().__init__()
+        if isinstance(kernel_size, int):
+            kernel_size = (kernel_size, kernel_size)
+        if not isinstance(kernel_size, tuple):
+            raise TypeError(f"kernel_size: an int or a tuple expected, got {type(kernel_size).__name__}")
+        kk = kernel_size[0] * kernel_size[1]
+        self.stride = stride if isinstance(stride, tuple) else (stride, stride)
+        self.padding = padding
+        self.offset_conv = nn.Conv2d(in_channels, 2 * kk, kernel_size=kernel_size, stride=stride, padding=self.padding, bias=True)
+        self.modulator_conv = nn.Conv2d(in_channels, kk, kernel_size=kernel_size, stride=stride, padding=self.padding, bias=True)
+        for side in (self.offset_conv, self.modulator_conv):
+            nn.init.constant_(side.weight, 0.)
+            nn.init.constant_(side.bias, 0.)
+        self.regular_conv = nn.Conv2d(in_channels, out_channels, kernel_size=kernel_size, stride=stride, padding=self.padding, bias=bias)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from ... import train_ops as T
+        T._need_cuda(x)
+        if T._STOCK:
+            raise FdError("DeformableConv2d: FD_TRAIN_STOCK_CONV=1 has no stock op to route this layer to (torchvision.ops.deform_conv2d is not part of this stack)")
+        m = self.regular_conv
+        k = m.kernel_size
+        if m.groups != 1 or self.offset_conv.groups != 1 or self.modulator_conv.groups != 1:
+            raise FdError("DeformableConv2d: groups = 1 expected")
+        if k[0] != k[1] or not (T._square(m) and T._square(self.offset_conv) and T._square(self.modulator_conv)):
+            raise FdError(f"DeformableConv2d: square kernel, stride and padding expected (kernel {tuple(k)}, stride {tuple(m.stride)}, padding {m.padding})")
+        if m.in_channels % 32 or x.dim() != 4 or x.shape[1] != m.in_channels:
+            raise FdError(f"DeformableConv2d: in_channels % 32 == 0 and an NCHW input of that width expected (in_channels={m.in_channels}, input {tuple(x.shape)})")
+        if self.offset_conv.out_channels != 2 * k[0] * k[0] or self.modulator_conv.out_channels != k[0] * k[0]:
+            raise FdError(f"DeformableConv2d: offset_conv must have 2*K*K = {2 * k[0] * k[0]} output channels, modulator_conv K*K = {k[0] * k[0]}")
+        if any(c.weight.dtype != torch.float32 for c in (m, self.offset_conv, self.modulator_conv)) or not T._f32(x):
+            raise FdError("DeformableConv2d: fp32 parameters and an fp32 input (any float type under torch.autocast) expected")
+        if not (1 <= k[0] <= 7 and 1 <= m.stride[0] <= 4 and 0 <= m.padding[0] <= 7) or m.dilation != (1, 1):
+            raise FdError(f"DeformableConv2d: 1 <= K <= 7, 1 <= stride <= 4, 0 <= padding <= 7, dilation 1 expected (K={k[0]} stride={m.stride[0]} padding={m.padding[0]})")
+        return T.deformable_conv2d(self, x)
+
+
 def init_conv_random_normal(module: nn.Module, std: float = 0.01):
     if isinstance(module, nn.Conv2d):
         nn.init.normal_(module.weight, std=std)

@@ -1375,6 +1375,66 @@ def dwconv_dilated_wgrad(x: Rows, dy: Rows, segs: Segs, K: int, dil: int, scale:
     return dw
 
 
+def deform_out_hw(H: int, W: int, K: int, stride: int, pad: int, dil: int) -> Tuple[int, int]:
+    return (H + 2 * pad - dil * (K - 1) - 1) // stride + 1, (W + 2 * pad - dil * (K - 1) - 1) // stride + 1
+
+
+def _deform_check(what: str, x: Rows, offset: Rows, mask: Optional[Rows], B: int, H: int, W: int, K: int, stride: int, pad: int, dil: int) -> int:
+    """The argument checks the two deformable-conv launches share (the library repeats the geometry ones); returns the output row count."""
+    _need_gpu(x.buf, offset.buf, mask.buf if mask is not None else None)
+    if not (1 <= K <= 7 and 1 <= stride <= 4 and 0 <= pad <= 7 and 1 <= dil <= 4):
+        raise FdError(f"{what}: 1 <= K <= 7, 1 <= stride <= 4, 0 <= pad <= 7, 1 <= dil <= 4 expected (K={K} stride={stride} pad={pad} dil={dil})")
+    Ho, Wo = deform_out_hw(H, W, K, stride, pad, dil)
+    if B < 1 or H < 1 or W < 1 or Ho < 1 or Wo < 1:
+        raise FdError(f"{what}: empty map (B={B} H={H} W={W} -> {Ho} x {Wo})")
+    if x.C % 4:
+        raise FdError(f"{what}: C % 4 == 0 expected (C={x.C})")
+    if x.f16 or offset.f16 or (mask is not None and mask.f16):
+        raise FdError(f"{what}: fp32 maps expected")
+    if x.rows != B * H * W:
+        raise FdError(f"{what}: x has {x.rows} rows, B*H*W = {B * H * W}")
+    if offset.C != 2 * K * K or offset.rows != B * Ho * Wo:
+        raise FdError(f"{what}: offset must be [B*Ho*Wo = {B * Ho * Wo}, 2*K*K = {2 * K * K}] (got [{offset.rows}, {offset.C}])")
+    if mask is not None and (mask.C != K * K or mask.rows != B * Ho * Wo):
+        raise FdError(f"{what}: mask must be [B*Ho*Wo = {B * Ho * Wo}, K*K = {K * K}] (got [{mask.rows}, {mask.C}])")
+    return B * Ho * Wo
+
+
+def _view3(r: Optional[Rows]):
+    return (r.ptr, r.cs, r.co) if r is not None else (None, 0, 0)
+
+
+def deform_im2col(x: Rows, offset: Rows, mask: Optional[Rows], cols: Rows, B: int, H: int, W: int, K: int, stride: int = 1, pad: int = 0, dil: int = 1,
+                  mask_act: bool = False) -> None:
+    """The sampler of modulated deformable convolution (include/fcosdet.h fd_deform_im2col_nhwc): cols[m, t*C + c] = mask[m, t] * bilinear(x_c at the
+    offset position of tap t), [B*Ho*Wo, K*K*C].  mask=None: no modulation; mask_act: `mask` holds logits and the kernel applies 2 * sigmoid."""
+    M = _deform_check("deform_im2col", x, offset, mask, B, H, W, K, stride, pad, dil)
+    _need_gpu(cols.buf)
+    if cols.f16 or cols.C != K * K * x.C or cols.rows != M:
+        raise FdError(f"deform_im2col: cols must be fp32 [{M}, K*K*C = {K * K * x.C}] (got [{cols.rows}, {cols.C}])")
+    check(_lib.lib().fd_deform_im2col_nhwc(x.ptr, x.cs, x.co, offset.ptr, offset.cs, offset.co, *_view3(mask), 1 if mask_act else 0, cols.ptr, cols.cs, cols.co,
+                                           B, H, W, x.C, K, stride, pad, dil, _stream()), "fd_deform_im2col_nhwc")
+
+
+def deform_bwd(dcols: Rows, x: Rows, offset: Rows, mask: Optional[Rows], d_offset: Rows, d_mask: Optional[Rows], d_x: Optional[Rows], B: int, H: int, W: int,
+               K: int, stride: int = 1, pad: int = 0, dil: int = 1, mask_act: bool = False) -> None:
+    """Backward of deform_im2col from the gradient of the columns (fd_deform_bwd_nhwc): writes d_offset and d_mask (with mask_act: of the logits) --
+    deterministic -- and, when d_x is given, ADDS the input gradient into it with fp32 atomics (the caller zeroes it; not bit-reproducible)."""
+    M = _deform_check("deform_bwd", x, offset, mask, B, H, W, K, stride, pad, dil)
+    _need_gpu(dcols.buf, d_offset.buf, d_mask.buf if d_mask is not None else None, d_x.buf if d_x is not None else None)
+    if dcols.f16 or dcols.C != K * K * x.C or dcols.rows != M:
+        raise FdError(f"deform_bwd: dcols must be fp32 [{M}, K*K*C = {K * K * x.C}] (got [{dcols.rows}, {dcols.C}])")
+    if d_offset.f16 or d_offset.C != offset.C or d_offset.rows != M:
+        raise FdError(f"deform_bwd: d_offset must be fp32 [{M}, {offset.C}]")
+    if (mask is None) != (d_mask is None) or (d_mask is not None and (d_mask.f16 or d_mask.C != K * K or d_mask.rows != M)):
+        raise FdError(f"deform_bwd: d_mask (fp32 [{M}, {K * K}]) comes with mask, and only with it")
+    if d_x is not None and (d_x.f16 or d_x.C != x.C or d_x.rows != x.rows):
+        raise FdError(f"deform_bwd: d_x must be fp32 [{x.rows}, {x.C}]")
+    check(_lib.lib().fd_deform_bwd_nhwc(dcols.ptr, dcols.cs, dcols.co, x.ptr, x.cs, x.co, offset.ptr, offset.cs, offset.co, *_view3(mask), 1 if mask_act else 0,
+                                        d_offset.ptr, d_offset.cs, d_offset.co, *_view3(d_mask), *_view3(d_x), B, H, W, x.C, K, stride, pad, dil, _stream()),
+          "fd_deform_bwd_nhwc")
+
+
 def groupnorm_workspace(segs: Segs, G: int, device) -> torch.Tensor:
     n = _lib.lib().fd_groupnorm_workspace_bytes(C.byref(segs), G)
     if n < 0:

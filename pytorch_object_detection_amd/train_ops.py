@@ -12,6 +12,8 @@ over the whole pyramid exactly as at inference.
   dw_rows                   depthwise 3x3: fd_dwconv3x3_nhwc forward and data gradient, fd_dwconv3x3_bwd_weight_nhwc.
   dw_dilated_rows           dilated depthwise k x k (MNBlock): fd_dwconv_dilated_nhwc forward and data gradient, fd_dwconv_dilated_bwd_weight_nhwc;
                             mn_block_rows = the whole MNBlock (depthwise, BatchNorm frozen or on batch statistics, PW1 + SiLU, PW2 + residual).
+  deform_conv_rows          modulated deformable conv (DeformableConv2d): the sampler node fd_deform_im2col_nhwc / fd_deform_bwd_nhwc writes the columns,
+                            conv_rows' node is the GEMM over them; deformable_conv2d = the layer with its two side convs as one launch.
   groupnorm_rows            GroupNorm + ReLU / SiLU: fd_groupnorm_act_nhwc / fd_groupnorm_act_bwd_nhwc.
   stem_rows                 the trainable 7x7 stem (Cin = 3), opt-in (trunk.hip_stem_train): fd_stem7x7_nhwc4 forward, fd_stem7x7_bwd_weight_nhwc4 backward.
 
@@ -671,6 +673,77 @@ def dw_dilated_rows(m: nn.Conv2d, x: torch.Tensor, segs: Segs, bn: Optional[nn.M
     if bn is not None:
         scale, shift = _bn_fold(bn)
     return _DwDilatedRows.apply(x, m.weight, scale, shift, segs, m.kernel_size[0], m.dilation[0])
+
+
+# ------------------------------------------------------------------- modulated deformable conv (DeformableConv2d)
+def _rv_or_copy(t: torch.Tensor) -> Rows:
+    r = _rv(t)
+    return r if r is not None else Rows(t.contiguous())
+
+
+class _DeformCols(torch.autograd.Function):
+    """The sampler of modulated deformable convolution: (x rows [B*H*W, C], offset rows [M, 2*K*K], mask rows [M, K*K] or None) -> columns
+    [M, K*K*C] (fd_deform_im2col_nhwc; M = B*Ho*Wo).  offset / mask may be channel slices of one buffer (the merged side conv's output): they are read
+    in place.  mask_act: `mask` holds the modulator's logits and 2 * sigmoid is applied inside, forward and backward.  Backward: fd_deform_bwd_nhwc --
+    d_offset / d_mask deterministic, d_x scattered with fp32 atomics into a zeroed buffer.  fp32 under autocast, like the depthwise nodes."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, offset, mask, geom, mask_act):
+        B, H, W, K, stride, pad, dil = geom
+        x = x.contiguous()
+        Ho, Wo = ops.deform_out_hw(H, W, K, stride, pad, dil)
+        cols = torch.empty(B * Ho * Wo, K * K * x.shape[1], dtype=torch.float32, device=x.device)
+        ops.deform_im2col(_r(x), _rv_or_copy(offset), _rv_or_copy(mask) if mask is not None else None, _r(cols), B, H, W, K, stride, pad, dil, mask_act)
+        ctx.save_for_backward(x, offset, mask)
+        ctx.geom, ctx.mask_act = geom, mask_act
+        return cols
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gcols):
+        x, offset, mask = ctx.saved_tensors
+        B, H, W, K, stride, pad, dil = ctx.geom
+        g = resolve_pending(gcols).contiguous()
+        M = g.shape[0]
+        d_off = torch.empty(M, 2 * K * K, dtype=torch.float32, device=g.device)
+        d_mask = torch.empty(M, K * K, dtype=torch.float32, device=g.device) if mask is not None else None
+        d_x = torch.zeros_like(x) if ctx.needs_input_grad[0] else None
+        ops.deform_bwd(_r(g), _r(x), _rv_or_copy(offset), _rv_or_copy(mask) if mask is not None else None, _r(d_off), _r(d_mask) if mask is not None else None,
+                       _r(d_x) if d_x is not None else None, B, H, W, K, stride, pad, dil, ctx.mask_act)
+        return d_x, d_off, d_mask, None, None
+
+
+def deform_conv_rows(x: torch.Tensor, offset: torch.Tensor, mask: Optional[torch.Tensor], weight: torch.Tensor, bias: Optional[torch.Tensor], B: int, H: int,
+                     W: int, stride: int, pad: int, dil: int, mask_act: bool = False) -> torch.Tensor:
+    """Modulated deformable convolution on rows: x [B*H*W, C], offset [M, 2*K*K], mask [M, K*K] or None, weight [Cout, C, K, K] -> [M, Cout].  The sampler
+    node writes the columns, the GEMM over them is the dense-conv node (_ConvRows: a 1x1 conv over K*K*C channels with weight.permute(0, 2, 3, 1), `bias`
+    as its shift), so data gradient, weight gradient and the AMP operand precision are the dense conv's.  Cout is zero-padded to a multiple of 32 inside."""
+    Cout, C, K, K2 = weight.shape
+    if K != K2 or C % 32 or x.shape[1] != C or weight.dtype != torch.float32:
+        raise FdError(f"deformable conv {tuple(weight.shape)} on {x.shape[1]} channels: square kernel, in_channels % 32 == 0, fp32 weights expected")
+    if not all(_f32(t) for t in (x, offset, mask) if t is not None):
+        raise FdError("deformable conv: fp32 input, offset and mask expected (or any float type under torch.autocast)")
+    cols = _DeformCols.apply(x, offset, mask, (B, H, W, K, stride, pad, dil), mask_act)
+    w = weight.permute(0, 2, 3, 1).reshape(Cout, K * K * C, 1, 1)
+    padn = (-Cout) % 32
+    if padn:
+        w = F.pad(w, (0, 0, 0, 0, 0, 0, 0, padn))
+        bias = F.pad(bias, (0, padn)) if bias is not None else None
+    Ho, Wo = ops.deform_out_hw(H, W, K, stride, pad, dil)
+    y = _ConvRows.apply(cols, w, None, bias, None, Segs.make(B, [(Ho, Wo)]), 1, 0, 1, ACT_NONE, amp_prec(), False)
+    return y[:, :Cout] if padn else y
+
+
+def deformable_conv2d(m: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """DeformableConv2d.forward on NCHW-shaped x: offset_conv and modulator_conv as ONE launch (2*K*K + K*K channels padded to a multiple of 32), the sampler
+    on two channel slices of that buffer (the modulator's 2 * sigmoid applied inside), the GEMM.  No host synchronisation: capturable in a HIP graph."""
+    B, _, H, W = x.shape
+    k, s, p = m.regular_conv.kernel_size[0], m.regular_conv.stride[0], m.regular_conv.padding[0]
+    xr = to_rows(x)
+    om = conv_rows(MergedConv(m.offset_conv, m.modulator_conv), xr, Segs.make(B, [(H, W)]), pad_out=True)
+    y = deform_conv_rows(xr, om[:, :2 * k * k], om[:, 2 * k * k:], m.regular_conv.weight, m.regular_conv.bias, B, H, W, s, p, 1, mask_act=True)
+    return from_rows(y, B, *ops.deform_out_hw(H, W, k, s, p, 1))
 
 
 def mn_block_rows(blk: nn.Module, x: torch.Tensor, segs: Segs) -> torch.Tensor:
