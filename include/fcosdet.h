@@ -101,7 +101,8 @@ const char* fd_last_error(void);
 #define FD_TILE_128x96_SB 12
 #define FD_TILE_128x128_PATCH 13 /* 3x3 stride-1 'same' convs only: the (128-row tile + halo) input patch is staged ONCE per
                                     32-channel chunk in LDS and the 9 taps are formed from it (9x less L2 -> LDS traffic for
-                                    the activations); needs 128 + 2*dil*(W + 1) <= 320 rows, no split-K */
+                                    the activations); needs 128 + 2*dil*(W + 1) <= 320 rows, no split-K; FD_PREC_F32 / FD_PREC_F16X3
+                                    (FD_PREC_F16 has no patch kernel: FD_E_UNSUPPORTED) */
 #define FD_TILE_WINOGRAD 14 /* 3x3 stride-1 'same' convs (dilation 1 or 2), fp32: Winograd F(2x2, 3x3) on the fp32 MFMA -- 16 multiplies
                                per (cin, cout) and 2x2 output tile instead of 36 (fd_conv_wino.hip).  `w` must be the
                                fd_wino_pack_weights_f32 packing; Cin % 8 == 0, Cout % 4 == 0, 16-byte addressable y / res / scale /

@@ -15,6 +15,9 @@ TILES = {1: (128, 128), 2: (128, 64), 3: (64, 128), 4: (64, 64), 5: (128, 32), 6
          12: (128, 96),                              # 128x96, single LDS buffer
          13: (128, 128),                             # 128x128 with the 3x3 input patch staged in LDS (3x3 stride-1 'same' only)
          15: (64, 64)}                               # wave-autonomous 64x64 tiles, one wave per workgroup (1x1 stride-1 layers, needs w_frag)
+# the tiles of TILES the FD_PREC_F16 instantiation of the direct kernel is built for: MUST follow `using F16 = Variant<...>` in csrc/fd_conv.hip (any other id of
+# TILES is FD_E_UNSUPPORTED under FD_PREC_F16; FD_PREC_F32 and FD_PREC_F16X3 have them all)
+F16_TILES = frozenset({1, 2, 3, 4, 5, 6, 7})
 PATCH_TILE = 13
 WAVE_TILE = 15
 # ... and the kernels a tile id names, each with its own weight format (ops.WFormat); not members of TILES

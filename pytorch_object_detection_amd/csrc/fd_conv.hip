@@ -543,8 +543,18 @@ extern "C" int32_t fd_conv2d_nhwc_f32(const fd_conv_params* p, fd_stream_t strea
     FD_REQUIRE(p->y_cs >= p->y_co + p->Cout, FD_E_INVAL, "fd_conv2d: output channel view out of range");
     FD_REQUIRE(!p->res || p->res_cs >= p->res_co + p->Cout, FD_E_INVAL, "fd_conv2d: residual channel view out of range");
     if (p->in.nseg > 1)
-        FD_REQUIRE(p->stride == 1 && 2 * p->pad == p->dil * (p->KH - 1) && p->KH == p->KW, FD_E_INVAL,
-                   "fd_conv2d: multi-level input needs stride 1 and 'same' padding");
+        // (any padding: every level has its own input and output row ranges, m_in / m_out below; the 'same'-only kernels -- Winograd, narrow, patch -- check their own)
+        FD_REQUIRE(p->stride == 1 && p->KH == p->KW, FD_E_INVAL, "fd_conv2d: multi-level input needs stride 1 and a square filter");
+    int patch_wmax = 0;
+    if (p->tile == FD_TILE_128x128_PATCH && !p->gate) {     // the patch tile's whole precondition, once (a gated launch picks its own tile: p->tile is not consulted there)
+        for (int sg = 0; sg < p->in.nseg; ++sg) patch_wmax = p->in.W[sg] > patch_wmax ? p->in.W[sg] : patch_wmax;
+        // (FD_PREC_F16 has no patch kernel: its f16-packed weights would be read as fp32 by the exact-fp32 instantiation)
+        FD_REQUIRE(!stem && p->KH == 3 && p->KW == 3 && p->stride == 1 && p->pad == p->dil && p->ksplit <= 1 && p->sc_H <= 0 && !p->gn_stats &&
+                       p->out_H <= 0 && FD_PATCH_BM + 2 * p->dil * (patch_wmax + 1) <= FD_PATCH_MAXROWS &&
+                       (p->precision == FD_PREC_F32 || p->precision == FD_PREC_F16X3),
+                   FD_E_UNSUPPORTED, "fd_conv2d: FD_TILE_128x128_PATCH needs an fp32 / split-f16 3x3 stride-1 'same' conv with 128 + 2*dil*(W+1) <= %d rows (W=%d dil=%d)",
+                   FD_PATCH_MAXROWS, patch_wmax, p->dil);
+    }
 
     FD_REQUIRE(p->res_mode >= 0 && p->res_mode <= 2, FD_E_INVAL, "fd_conv2d: res_mode %d", p->res_mode);
     if (p->res && p->res_mode == 2) {
@@ -616,7 +626,10 @@ extern "C" int32_t fd_conv2d_nhwc_f32(const fd_conv_params* p, fd_stream_t strea
                  (!p->res || (p->res_cs % 4 == 0 && p->res_co % 4 == 0 && ((uintptr_t)p->res & 15) == 0)))
                     ? 1 : 0;
 
-    a.is_gemm = (!stem && p->KH == 1 && p->KW == 1 && p->stride == 1 && p->pad == 0) ? 1 : 0;
+    // (an explicit output size that is not the input's -- the one-tap parity classes of a k = stride data gradient on an odd map -- decodes its rows: with
+    // GEMM addressing output row m would read input row m)
+    a.is_gemm = (!stem && p->KH == 1 && p->KW == 1 && p->stride == 1 && p->pad == 0 &&
+                 (p->out_H <= 0 || (p->out_H == p->in.H[0] && p->out_W == p->in.W[0]))) ? 1 : 0;
     {
         const long xb = (long)p->in.m_start[p->in.nseg] * p->x_cs * 4, wb = (long)p->Cout * a.Kpacked * 4;
         FD_REQUIRE(xb < 0xC0000000L && wb < 0xC0000000L, FD_E_UNSUPPORTED, "fd_conv2d: input / weight buffer exceeds 3 GiB");
@@ -682,13 +695,7 @@ extern "C" int32_t fd_conv2d_nhwc_f32(const fd_conv_params* p, fd_stream_t strea
         return fd_launch_conv_wave(a, p->w_frag, stream);
     }
     if (p->tile == FD_TILE_128x128_PATCH) {     // 3x3 stride-1 'same' conv with the input patch staged in LDS (fd_conv_patch.hip)
-        int wmax = 0;
-        for (int sg = 0; sg < p->in.nseg; ++sg) wmax = p->in.W[sg] > wmax ? p->in.W[sg] : wmax;
-        FD_REQUIRE(!stem && p->KH == 3 && p->KW == 3 && p->stride == 1 && p->pad == p->dil && p->ksplit <= 1 && !a.sc_on && !p->gn_stats &&
-                       p->out_H <= 0 && FD_PATCH_BM + 2 * p->dil * (wmax + 1) <= FD_PATCH_MAXROWS,
-                   FD_E_UNSUPPORTED, "fd_conv2d: FD_TILE_128x128_PATCH needs a 3x3 stride-1 'same' conv with 128 + 2*dil*(W+1) <= %d rows (W=%d dil=%d)",
-                   FD_PATCH_MAXROWS, wmax, p->dil);
-        a.p_halo = p->dil * (wmax + 1);
+        a.p_halo = p->dil * (patch_wmax + 1);      // (preconditions: checked once, in front of the geometry set-up above)
         return fd_launch_conv_patch(a, p->tag == 1, p->precision == FD_PREC_F16X3, stream);
     }
 
@@ -741,7 +748,7 @@ static int dispatch_conv(const fd_conv_params* p, ConvArgs& a, bool stem, hipStr
         return ResUp::launch(autot ? FD_TILE_64x128_SB : p->tile, a, stream);
     }
     // GEMM-addressed fp32 layers (1x1, no padding, Cin % 32 == 0, no gate): the loader compiled without the tap / bounds arithmetic
-    const bool pointwise = !stem && p->KH == 1 && p->KW == 1 && p->pad == 0;     // any stride: one input address per output row
+    const bool pointwise = !stem && p->KH == 1 && p->KW == 1 && p->pad == 0 && p->out_H <= 0;     // any stride: one input address per output row (an explicit output size may name rows past the input: the bounds-checked loader)
     if (pointwise && p->Cin % 32 == 0 && !a.gate && !a.sc_on && Fp32Gemm::has(p->tile)) return Fp32Gemm::launch(p->tile, a, stream);
     FD_REQUIRE(autot || Fp32::has(p->tile), FD_E_INVAL, "fd_conv2d: unknown tile id %d", p->tile);
     return Fp32::launch(autot ? fp32_auto_tile(a) : p->tile, a, stream);

@@ -180,11 +180,9 @@ def add_conv(plan: Plan, name: str, x: Rows, segs: Segs, conv: torch.nn.Conv2d, 
         raise FdError("add_conv: a tail launch is still pending (_flush_tail_steps right after closing the mark of a tag = 1 conv)")
     w = conv.weight if weight is None else weight
     b = (conv.bias if bias is None else bias)
-    k, stride, pad, dil = conv.kernel_size[0], conv.stride[0], conv.padding, conv.dilation[0]
-    if isinstance(pad, str):  # 'same'
-        pad = dil * (k - 1) // 2
-    else:
-        pad = pad[0]
+    k, stride, pad, dil = conv.kernel_size[0], conv.stride[0], ops.conv_pad(conv), conv.dilation[0]
+    if pad is None:
+        raise FdError(f"add_conv: padding='same' of a {k}x{k} conv with dilation {dil} is asymmetric, which the conv kernels do not take")
     Cin, co = w.shape[1], (w.shape[0] if Cout is None else Cout)
     if res_up and (plan.precision != "f32" or k != 1 or stride != 1 or pad != 0 or segs.nseg != 1 or res is None or gate is not None or gn_stats is not None or x2 is not None):
         raise FdError("add_conv: res_up (a half-resolution addend behind the activation) needs an exact-fp32 1x1 stride-1 single-level conv with a residual")
@@ -698,7 +696,7 @@ def build_his_fpn(plan: Plan, fpn, feats):
 def _predictor_format(plan: Plan, head, segs: Segs, F: int, Cout: int = 5, wino4: bool = True) -> "ops.WFormat":
     """ops.choose_conv's format (= kernel family) for the 1 + 4-wide centre-ness / box predictor of this plan, as add_conv will ask for it."""
     rp = head.reg_pred
-    rp_pad = rp.dilation[0] * (rp.kernel_size[0] - 1) // 2 if isinstance(rp.padding, str) else rp.padding[0]
+    rp_pad = ops.conv_pad(rp)       # (None -- an asymmetric 'same' -- is no narrow / Winograd geometry, and add_conv raises on it)
     return ops.choose_conv(segs, F, Cout, rp.kernel_size[0], rp.stride[0], rp_pad, rp.dilation[0], plan.precision, wino4=wino4).fmt
 
 

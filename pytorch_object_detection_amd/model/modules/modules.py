@@ -12,7 +12,9 @@ from ..._lib import FdError
 
 def _layer_conv(m: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     """m(x) on the HIP kernels: dense convs (Cin % 32 == 0) and depthwise 3x3 stride 1 with autograd (train_ops nodes);
-    other depthwise shapes (k in {3,5,7}, stride 1 / 2, padding k//2) without a backward."""
+    other depthwise shapes (k in {3,5,7}, stride 1 / 2, padding k//2) without a backward.  Padding rule (train_ops._dense_ok): dense convs take any
+    symmetric zero padding -- an int, 'valid' (= 0), or 'same' with dilation * (k - 1) even; a 'same' that torch pads asymmetrically (an even kernel at an
+    odd dilation) raises FdError, as does every other module the kernels do not cover.  A tensor of another shape than m(x) is never returned."""
     from ... import ops, train_ops as T
     T._need_cuda(x)
     if T._STOCK:
@@ -33,7 +35,7 @@ def _layer_conv(m: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
                      None, m.bias.detach() if m.bias is not None else None)
         return T.from_rows(y, B, Ho, Wo)
     raise FdError(f"{type(m).__name__}{tuple(m.weight.shape)}: not covered by the HIP kernels (dense: Cin % 32 == 0, Cout % 4 == 0, "
-                  "square kernel, fp32; depthwise: C % 4 == 0, k in {3,5,7}, stride 1 / 2, padding k//2)")
+                  "square kernel, symmetric zero padding, fp32; depthwise: C % 4 == 0, k in {3,5,7}, stride 1 / 2, padding k//2)")
 
 
 class DepthWiseConv2d(nn.Conv2d):

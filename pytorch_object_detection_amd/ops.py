@@ -918,7 +918,7 @@ def conv_dgrad_strided(dy: Rows, w: torch.Tensor, scale: Optional[torch.Tensor],
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     cls = strided_dgrad_classes(k, stride, pad)
     if Cout % 32 or Cin % 4 or any(T and (T - 1 - c) != 0 for _, T, c in cls):
-        return False                      # (the class convs of k = 3 / pad 1 and k = 1 / pad 0 need no padding; others are not built)
+        return False                      # (the class convs of k = 3 / pad 1, k = 1 / pad 0 and k = stride / pad 0 need no padding; others are not built)
     segs = Segs.make(N, [(Ho, Wo)])
     wd = w.detach()
     fmt = amp_format(Cout, Cin) if precision else WFormat.DIRECT       # AMP: the class convs on FD_TILE_F16K64 where the widths allow
@@ -937,6 +937,18 @@ def conv_dgrad_strided(dy: Rows, w: torch.Tensor, scale: Optional[torch.Tensor],
 def dgrad_weight(w: torch.Tensor) -> torch.Tensor:
     """Packed weights of the stride-1 data-gradient conv: w'[ci][co][r][q] = w[co][ci][K-1-r][K-1-q]."""
     return pack_conv_weight(w.detach().flip(2, 3).transpose(0, 1).contiguous())
+
+
+def conv_pad(m) -> Optional[int]:
+    """The one symmetric zero padding the conv kernels take, read off a square nn.Conv2d-like `m` (kernel_size, dilation, padding): an int / tuple padding
+    as it stands, 'valid' = 0, 'same' = dil * (k - 1) / 2.  None where 'same' has no such padding: with dil * (k - 1) odd (an even kernel at an odd dilation)
+    torch pads one more row / column at the end than at the start, which the kernels do not take -- callers decline that module."""
+    if isinstance(m.padding, str):
+        if m.padding == "valid":
+            return 0
+        total = m.dilation[0] * (m.kernel_size[0] - 1)
+        return None if (m.padding != "same" or total % 2) else total // 2
+    return m.padding[0]
 
 
 def conv_out_segs(segs: Segs, k: int, stride: int, pad: int, dil: int) -> Segs:

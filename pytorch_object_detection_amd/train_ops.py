@@ -17,7 +17,8 @@ over the whole pyramid exactly as at inference.
   groupnorm_rows            GroupNorm + ReLU / SiLU: fd_groupnorm_act_nhwc / fd_groupnorm_act_bwd_nhwc.
   stem_rows                 the trainable 7x7 stem (Cin = 3), opt-in (trunk.hip_stem_train): fd_stem7x7_nhwc4 forward, fd_stem7x7_bwd_weight_nhwc4 backward.
 
-What the kernels do not cover falls back to stock PyTorch-ROCm ops on the GPU: the data gradient of strided layers,
+What the kernels do not cover falls back to stock PyTorch-ROCm ops on the GPU: the data gradient of strided layers other than the
+parity-class geometries and of layers padded by more than dil * (k - 1) (the rungs of _dense_dgrad), a padding='same' that torch pads asymmetrically,
 dense layers with Cin % 32 != 0 (the 7x7 stem when it is trainable and its node is not switched on), BatchNorm in training mode or with trainable
 affine parameters, and SiLU after a BatchNorm (its derivative needs the pre-activation, which the fused epilogue does
 not keep).  Narrow outputs (class / centre-ness / box logits) are padded to 32 channels by `conv_rows(pad_out=True)`.
@@ -141,15 +142,15 @@ def _rv(t: torch.Tensor) -> Optional[Rows]:
     return None
 
 
-def _pad_of(m: nn.Conv2d) -> int:
-    if isinstance(m.padding, str):
-        return m.dilation[0] * (m.kernel_size[0] - 1) // 2
-    return m.padding[0]
+def _pad_of(m: nn.Conv2d) -> Optional[int]:
+    """The kernels' symmetric padding of a square conv (ops.conv_pad): 'valid' is 0, 'same' is dil * (k - 1) / 2, None for a 'same' that torch pads
+    asymmetrically (dil * (k - 1) odd).  _square declines the None case, so behind a coverage predicate this is an int."""
+    return ops.conv_pad(m)
 
 
 def _square(m: nn.Conv2d) -> bool:
     return (m.kernel_size[0] == m.kernel_size[1] and m.stride[0] == m.stride[1] and m.dilation[0] == m.dilation[1]
-            and (isinstance(m.padding, str) or m.padding[0] == m.padding[1]) and m.padding_mode == "zeros")
+            and (_pad_of(m) is not None if isinstance(m.padding, str) else m.padding[0] == m.padding[1]) and m.padding_mode == "zeros")
 
 
 def _f32(x: torch.Tensor) -> bool:
@@ -158,6 +159,10 @@ def _f32(x: torch.Tensor) -> bool:
 
 
 def _dense_ok(m: nn.Conv2d, x: torch.Tensor, pad_out: bool = False) -> bool:
+    """Dense convs the HIP node takes: groups 1, Cin % 32 == 0, Cout % 4 == 0 (any Cout with pad_out), fp32, a square kernel / stride / dilation and a
+    SYMMETRIC zero padding -- an int or (p, p) tuple of any size, 'valid' (= 0), or 'same' with dil * (k - 1) even.  A 'same' that torch pads asymmetrically
+    (an even kernel at an odd dilation) is declined: conv_bn_act then takes the counted stock fallback, the layers raise FdError.  The forward and the weight
+    gradient run on the HIP kernels for every admitted geometry; the data gradient's rungs, stock ones included, are listed in _dense_dgrad."""
     return (m.groups == 1 and m.in_channels % 32 == 0 and (pad_out or m.out_channels % 4 == 0) and _square(m)
             and _f32(x) and m.weight.dtype == torch.float32)
 
@@ -165,7 +170,7 @@ def _dense_ok(m: nn.Conv2d, x: torch.Tensor, pad_out: bool = False) -> bool:
 def _dw_ok(m: nn.Conv2d, x: torch.Tensor) -> bool:
     c4 = m.in_channels // 4
     return (m.groups == m.in_channels == m.out_channels and m.in_channels % 4 == 0 and m.kernel_size == (3, 3)
-            and m.stride == (1, 1) and m.dilation == (1, 1) and _pad_of(m) == 1 and m.padding_mode == "zeros"
+            and m.stride == (1, 1) and m.dilation == (1, 1) and _square(m) and _pad_of(m) == 1      # (_square: padding (1, 1), not (1, q))
             and m.bias is None and ((c4 < 256 and 256 % c4 == 0) or c4 % 256 == 0) and _f32(x))
 
 
@@ -380,24 +385,29 @@ def _dense_dgrad(g: torch.Tensor, x: torch.Tensor, w: torch.Tensor, scale: Optio
     """dX rows of a dense conv layer from dY rows `g`, given the layer as its forward saw it: input map x on `segs`, output on `so` (both tables were made by
     the forward: none is built here), OIHW weight `w`, folded-BN `scale`, geometry k / stride / pad / dil.  `res` is a gradient added to dX, or with res_mask
     the ReLU output of the layer dX flows into (dX is masked by it).  The rungs:
-      stride 1 and Cout % 32 == 0   the conv kernel on dY over `so` with the channel roles swapped, the flipped / transposed / scaled weights and
-                                    pad' = dil * (k - 1) - pad; `res` rides in its epilogue
-      strided, one level, dil 1     one exact-FLOP launch per parity class (ops.conv_dgrad_strided), `res` in their epilogues
-      what is left on one level     (narrow Cout, dilated + strided) the stock op, then one relu_mask launch or the add; counted by stock_fallback
+      stride 1, Cout % 32 == 0      the conv kernel on dY over `so` with the channel roles swapped, the flipped / transposed / scaled weights and
+      and pad <= dil * (k - 1)      pad' = dil * (k - 1) - pad; `res` rides in its epilogue
+      strided, one level, dil 1     one exact-FLOP launch per parity class (ops.conv_dgrad_strided: the classes that need no padding -- k = 3 / pad 1,
+                                    k = 1 / pad 0, k = stride / pad 0), `res` in their epilogues
+      what is left on one level     (narrow Cout, dilated + strided, the other strided geometries, pad > dil * (k - 1): pad' would be negative, a crop the
+                                    kernel does not take) the stock op, then one relu_mask launch or the add; counted by stock_fallback
       what is left over a pyramid   an error
     _BottleneckRows never reaches the last two: bottleneck() admits only widths with Cout % 32 == 0 and dilation 1 to the node."""
     Cout = w.shape[0]
-    if stride == 1 and Cout % 32 == 0:
+    if stride == 1 and Cout % 32 == 0 and pad <= dil * (k - 1):
         gx = torch.empty_like(x)
         pad = dil * (k - 1) - pad
         _conv_launch(g, so, PACKS.get(w, scale, dgrad=True, fmt=conv_format(Cout, w.shape[1], k, 1, pad, dil, so, prec)), gx, k=k, stride=1, pad=pad, dil=dil,
                      res=res, res_mask=res_mask)
         return gx
     if segs.nseg != 1:
+        if stride == 1 and Cout % 32 == 0:
+            raise FdError(f"data gradient of a {k}x{k} conv padded by {pad} > dilation * (k - 1) = {dil * (k - 1)} over a pyramid is not supported: the HIP "
+                          "kernel takes no negative padding and the stock rung is single-level (run the levels one by one, or pad by at most dilation * (k - 1))")
         raise FdError("data gradient of a strided / narrow conv over a pyramid is not supported (pad Cout to 32)")
     if stride > 1 and dil == 1 and (gx := _strided_dgrad(g, w, scale, segs, k, stride, pad, res=res, res_mask=res_mask, prec=prec)) is not None:
         return gx
-    stock_fallback(f"the data gradient of a {k}x{k} stride-{stride} conv with Cout={Cout}")
+    stock_fallback(f"the data gradient of a {k}x{k} stride-{stride} pad-{pad} dilation-{dil} conv with Cout={Cout}")
     weff = w.detach() if scale is None else w.detach() * scale.view(-1, 1, 1, 1)
     B, (H, W), (Ho, Wo) = segs.batch, segs.level_hw()[0], so.level_hw()[0]
     gx = to_rows(torch.ops.aten.convolution_backward(from_rows(g, B, Ho, Wo), from_rows(x, B, H, W), weff, None, [stride, stride], [pad, pad], [dil, dil],
