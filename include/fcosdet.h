@@ -366,7 +366,7 @@ int32_t fd_nhwc_to_nchw(const float* x, int32_t x_cs, int32_t x_co, float* y, in
 /* ------------------------------------------------------------------------------------------- */
 /* Bandwidth-bound layer ops                                                                     */
 /* Channel views (ptr, cs, co, C) of fd_maxpool[_bwd]_nhwc, fd_upsample2x_add_nhwc / fd_upsample2x_bwd_nhwc, fd_dwconv3x3[_gn]_nhwc,
- * fd_dwconv_dilated_nhwc, fd_dwconv2d_nhwc, the two depthwise weight gradients, fd_groupnorm_act / _apply / _stats / _act_bwd_nhwc,
+ * fd_dwconv_dilated_nhwc, fd_dwconv2d_nhwc, fd_dwconv2d_bwd_data_nhwc / fd_dwconv2d_bwd_weight_nhwc, the other two depthwise weight gradients, fd_groupnorm_act / _apply / _stats / _act_bwd_nhwc,
  * fd_coef_apply_nhwc, fd_se_scale[_bwd]_nhwc, fd_act[_bwd]_nhwc[_h] and fd_batchnorm_sync_fwd / _bwd_nhwc are accessed four channels at a
  * time: C, cs and co are multiples of 4, cs >= co + C, ptr is 16-byte aligned (8-byte for the f16 maps of fd_act_bwd_nhwc_h); a view
  * that breaks this returns FD_E_INVAL before any launch (a width the kernel does not cover: FD_E_UNSUPPORTED).  In these entry points cs
@@ -459,6 +459,23 @@ int32_t fd_dwconv2d_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float
                          const float* shift, float* y, int32_t y_cs, int32_t y_co, int32_t N, int32_t H, int32_t W,
                          int32_t C, int32_t K, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo,
                          int32_t act, fd_stream_t stream);
+/* Backward of fd_dwconv2d_nhwc for the MBConv depthwise conv in the train step: k in {3, 5}, stride in {1, 2} (anything else: FD_E_UNSUPPORTED), the
+ * same top / left padding and output size as the forward call, fp32 channel views under the contract above.  Any stream, no host synchronisation, no
+ * float atomics, bitwise reproducible.  Bad views, a missing / misaligned workspace or an Ho x Wo that reaches past the input return FD_E_INVAL before
+ * any launch.
+ *   data gradient    dx[n,h,w,c] = scale[c] * sum_{r,s} dy[n,ho,wo,c] * w[r,s,c] over the taps with h + pad_top - r = stride * ho, 0 <= ho < Ho (same
+ *                    along w); w [K*K][C] as the forward took it, scale optional (a folded frozen BatchNorm).  EVERY pixel of the dx view is written:
+ *                    input rows / columns that no output window reaches come back 0.
+ *   weight gradient  dw[r,s,c] = scale[c] * sum_{n,ho,wo} dy[n,ho,wo,c] * x[n, ho*stride - pad_top + r, wo*stride - pad_left + s, c] over the taps
+ *                    inside the input; layout 0 = [K*K][C], 1 = [C][1][K][K]; workspace = fd_dwconv2d_wgrad_workspace_bytes(N, Ho, Wo, C, K)
+ *                    bytes, 16-byte aligned (-1: bad size, C or K). */
+int32_t fd_dwconv2d_bwd_data_nhwc(const float* dy, int32_t dy_cs, int32_t dy_co, const float* w, const float* scale, float* dx,
+                                  int32_t dx_cs, int32_t dx_co, int32_t N, int32_t H, int32_t W, int32_t C, int32_t K, int32_t stride,
+                                  int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, fd_stream_t stream);
+int64_t fd_dwconv2d_wgrad_workspace_bytes(int32_t N, int32_t Ho, int32_t Wo, int32_t C, int32_t K);
+int32_t fd_dwconv2d_bwd_weight_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co, float* dw,
+                                    int32_t C, int32_t K, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t N, int32_t H, int32_t W,
+                                    int32_t Ho, int32_t Wo, const float* scale, int32_t layout, void* workspace, fd_stream_t stream);
 /* MBConv expand -> depthwise in ONE kernel (efficientnet_pytorch 0.7.1 MBConvBlock.forward behind model/backbone/efficientnetv1.py:11-26):
  *     y = swish(bn1(dwconv_kxk(swish(bn0(conv1x1(x, W_expand))))))   k in {3, 5}, stride in {1, 2}, static "SAME" padding (pad_top / pad_left; zeros on every side)
  * without the expanded map (six times the block input) ever reaching HBM: a workgroup stages the input patch of one TO x TO output tile in LDS, computes the expand

@@ -674,34 +674,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_partial_kernel(const floa
     }
 }
 
-__global__ __launch_bounds__(256) void dw_wgrad_final_kernel(const float* __restrict__ part, float* __restrict__ dw,
-                                                                     int n, int nchunk, const float* __restrict__ scale,
-                                                                     int layout, int C, int T) {
-    // 16 outputs x 16 chunk lanes per workgroup: lane j adds chunks j, j+16, ... in order, lanes are combined in order
-    __shared__ double red[256];
-    const int o = threadIdx.x & 15, j = threadIdx.x >> 4;
-    const int i = blockIdx.x * 16 + o;
-    double s = 0.0;
-    if (i < n)
-        for (int k = j; k < nchunk; k += 16) s += (double)part[(long)k * n + i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    if (j == 0 && i < n) {
-        double t = 0.0;
-        for (int q = 0; q < 16; ++q) t += red[q * 16 + o];
-        const int tap = i / C, c = i - tap * C;
-        float v = (float)t;
-        if (scale) v *= scale[c];
-        dw[layout ? c * T + tap : i] = v;
-    }
-}
-
-static inline int dw_wgrad_chunks(long rows) {
-    long n = (rows + 63) / 64;
-    if (n > 1024) n = 1024;
-    if (n < 1) n = 1;
-    return (int)n;
-}
+#include "fd_dw_wgrad_final.inc"      // dw_wgrad_final_kernel, dw_wgrad_chunks (shared with fd_mbconv_bwd.hip)
 
 extern "C" int64_t fd_dwconv3x3_wgrad_workspace_bytes(const fd_segs* segs, int32_t C) {
     if (!fd_segs_ok(segs) || C < 4) return -1;

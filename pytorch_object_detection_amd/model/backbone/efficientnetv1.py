@@ -17,9 +17,11 @@ from typing import List, Tuple
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
-from ... import engine
-from ..._lib import FdError
+from ... import engine, ops
+from ... import train_ops as T
+from ..._lib import FdError, Segs
 from ..od._planned import PlannedModule
 
 VALID_MODELS = ('efficientnet-b0', 'efficientnet-b1', 'efficientnet-b2', 'efficientnet-b3', 'efficientnet-b4',
@@ -91,6 +93,9 @@ class _EfficientNet(nn.Module):
             raise FdError(f"unknown EfficientNet '{model_name}'")
         width, depth, res, _ = _COEFF[model_name]
         self.model_name, self.image_size = model_name, res
+        # efficientnet_pytorch applies stochastic depth (drop_connect_rate 0.2) in train mode; the HIP training path has no such node and trains without it:
+        # 0.0 here, and trunk_train_forward refuses any other value
+        self.drop_connect_rate = 0.0
         stem = _scaled_width(32, width)
         self._conv_stem = nn.Conv2d(3, stem, 3, 2, bias=False)
         self.stem_pad = static_same_padding(res, 3, 2)
@@ -112,15 +117,89 @@ class _EfficientNet(nn.Module):
         self._fc = nn.Linear(head, 1000)
 
 
+def _out_hw(h: int, w: int, k: int, s: int, pad) -> Tuple[int, int]:
+    return (h + pad[0] + pad[1] - k) // s + 1, (w + pad[0] + pad[1] - k) // s + 1
+
+
+def _trunk_stock(net: "_EfficientNet", x: torch.Tensor):
+    """The trunk on stock PyTorch-ROCm ops (FD_TRAIN_STOCK_CONV=1 only: the diagnostic mode that times the HIP step against them)."""
+    swish = lambda t: t * torch.sigmoid(t)  # noqa: E731
+    bn = lambda m, t: F.batch_norm(t, m.running_mean, m.running_var, m.weight, m.bias, False, 0.0, m.eps)  # noqa: E731
+    same = lambda t, pad: F.pad(t, (pad[0], pad[1], pad[0], pad[1])) if (pad[0] or pad[1]) else t  # noqa: E731
+    with torch.no_grad():
+        x = swish(bn(net._bn0, F.conv2d(same(x, net.stem_pad), net._conv_stem.weight, None, 2)))
+    ends, blocks = [], list(net._blocks)
+    for i, blk in enumerate(blocks):
+        inp = x
+        if blk.expand != 1:
+            x = swish(bn(blk._bn0, F.conv2d(x, blk._expand_conv.weight)))
+        x = swish(bn(blk._bn1, F.conv2d(same(x, blk.pad), blk._depthwise_conv.weight, None, blk.stride, 0, 1, x.shape[1])))
+        sq = swish(F.conv2d(F.adaptive_avg_pool2d(x, 1), blk._se_reduce.weight, blk._se_reduce.bias))
+        x = torch.sigmoid(F.conv2d(sq, blk._se_expand.weight, blk._se_expand.bias)) * x
+        x = bn(blk._bn2, F.conv2d(x, blk._project_conv.weight))
+        if blk.skip:
+            x = x + inp
+        if i + 1 == len(blocks) or blocks[i + 1].stride > 1:
+            ends.append(x)
+    return tuple(ends[-3:])
+
+
+def trunk_train_forward(net: "_EfficientNet", x: torch.Tensor):
+    """The EfficientNet trunk of a training step on the HIP autograd nodes: image batch [B, 3, H, W] -> (C3, C4, C5), the endpoints reduction_3/4/5 as
+    NCHW-shaped channels-last views.  The stem (_conv_stem + _bn0 + swish) is frozen and runs on the inference kernel without a graph; every MBConv block
+    is train_ops.mbconv_rows.  Every map from the stem output to the endpoints is held at its width ROUNDED UP TO 32 with pad channels that are exactly
+    zero (forward and backward), so the returned maps are round32(48 / 136 / 384) wide: FeaturePyramidNetwork.train_forward pads its lateral weights."""
+    if net.drop_connect_rate:
+        raise FdError(f"EfficientNet trunk: drop_connect_rate={net.drop_connect_rate} is not supported on the HIP training path (it trains without "
+                      "stochastic depth: set model.drop_connect_rate = 0.0)")
+    if not T.bn_is_frozen(net._bn0) or net._conv_stem.weight.requires_grad:
+        raise FdError("EfficientNet trunk: the HIP training path needs a frozen stem (_conv_stem, _bn0) and frozen BatchNorm layers "
+                      "(FCOS(..., freeze_bn=True).enable_training(); batch statistics in the MBConv trunk are out of scope)")
+    if x.dim() != 4 or x.shape[1] != 3 or not T._f32(x) or x.requires_grad:
+        raise FdError("EfficientNet trunk: expected an image batch [B, 3, H, W] that needs no gradient")
+    if T._STOCK:
+        return _trunk_stock(net, x.float())
+    B, _, H, W = x.shape
+    dev = x.device
+    with torch.no_grad():
+        x4 = torch.empty(B * H * W, 4, dtype=torch.float32, device=dev)
+        ops.nchw3_to_nhwc4(x.float().contiguous(), x4)
+        C0 = net._conv_stem.out_channels
+        h, w = _out_hw(H, W, 3, 2, net.stem_pad)
+        if h < 1 or w < 1:
+            raise FdError("EfficientNet: input too small")
+        sc, sf = T._bn_fold(net._bn0)
+        buf = (torch.zeros if T.round32(C0) != C0 else torch.empty)(B * h * w, T.round32(C0), dtype=torch.float32, device=dev)
+        ops.stem_conv3(x4, ops.pack_stem3_weight(net._conv_stem.weight), ops.Rows(buf, 0, C0), B, H, W, 3, 2, net.stem_pad[0], net.stem_pad[0], h, w,
+                       sc, sf, ops.ACT_SILU)
+    t, segs = buf, Segs.make(B, [(h, w)])
+    ends, blocks = [], list(net._blocks)
+    for i, blk in enumerate(blocks):
+        t, segs = T.mbconv_rows(blk, t, segs)
+        if i + 1 == len(blocks) or blocks[i + 1].stride > 1:
+            ends.append(T.from_rows(t, B, segs.H[0], segs.W[0]))
+    return tuple(ends[-3:])
+
+
 class EfficientNetV1(PlannedModule):
     """Reference model/backbone/efficientnetv1.py:11-26.  forward(x [B,3,H,W] fp32 CUDA) -> list of the five endpoints
     reduction_1..reduction_5 (strides 2, 4, 8, 16, 32; B3: 24, 32, 48, 136, 384 channels) as NCHW-shaped channels-last
-    views of plan-owned buffers.  Inference only: BatchNorm runs folded (eval), the HIP path has no MBConv backward."""
+    views of plan-owned buffers.  Stand-alone the wrapper is inference only (BatchNorm folded, eval); the trunk TRAINS inside FCOS(efficientnet=True)
+    after enable_training(), through trunk_train_forward (MBConv blocks on the HIP autograd nodes, frozen stem and BatchNorm, no drop-connect)."""
 
     def __init__(self, backbone_number: int, memory_efficient: bool = False):
         super().__init__()
         self.model = _EfficientNet(VALID_MODELS[backbone_number])
         self.memory_efficient = memory_efficient      # swish variant of the reference: same forward arithmetic
+
+    @property
+    def drop_connect_rate(self) -> float:
+        """Stochastic-depth rate of the training path: 0.0 (efficientnet_pytorch trains at 0.2; the HIP path has no such node and refuses anything else)."""
+        return self.model.drop_connect_rate
+
+    @drop_connect_rate.setter
+    def drop_connect_rate(self, v: float) -> None:
+        self.model.drop_connect_rate = float(v)
 
     @property
     def endpoint_channels(self) -> List[int]:

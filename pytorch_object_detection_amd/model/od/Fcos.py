@@ -33,12 +33,22 @@ class FeaturePyramidNetwork(PlannedModule):
         self.P7_c1 = nn.Conv2d(feature, feature, 3, 2, 1)
         self.apply(init_conv_kaiming)
 
+    @staticmethod
+    def _lateral(m: nn.Conv2d, c: torch.Tensor) -> torch.Tensor:
+        """m(c); a map WIDER than m.in_channels is an EfficientNet endpoint held at its width rounded up to 32 with zero pad channels
+        (trunk_train_forward): the lateral weight gets zero input columns inside the autograd graph (train_ops.conv_rows_wide)."""
+        if c.shape[1] == m.in_channels or T._STOCK:
+            return tconv(m, c)
+        T._need_cuda(c)
+        B, _, H, W = c.shape
+        return T.from_rows(T.conv_rows_wide(m, T.to_rows(c), T.Segs.make(B, [(H, W)])), B, H, W)[:, :m.out_channels]
+
     def train_forward(self, x):
         c3, c4, c5 = x
         up = lambda t: F.interpolate(t, scale_factor=2.0, mode="nearest")  # noqa: E731
-        p5 = tconv(self.P5, c5)
-        p4 = tconv(self.P4_c1, up(p5) + tconv(self.P4, c4))
-        p3 = tconv(self.P3_c1, up(p4) + tconv(self.P3, c3))
+        p5 = self._lateral(self.P5, c5)
+        p4 = tconv(self.P4_c1, up(p5) + self._lateral(self.P4, c4))
+        p3 = tconv(self.P3_c1, up(p4) + self._lateral(self.P3, c3))
         p5 = tconv(self.P5_c1, p5)
         p6 = cba(self.P6_c1, None, p5, ACT_RELU)   # the reference's in-place ReLU rectifies the returned P6 (Fcos.py:90)
         return p3, p4, p5, p6, tconv(self.P7_c1, p6)
@@ -107,6 +117,8 @@ class FCOS(PlannedModule):
     reduction_3/4/5 (strides 8/16/32) go to the FPN as (C3, C4, C5); in_channel must be their widths reversed
     (B0 [320, 112, 40], B3 [384, 136, 48])."""
 
+    hip_train = False       # efficientnet=True: opt-in training on the HIP autograd nodes (enable_training())
+
     def __init__(self, in_channel: List[int], num_class: int, feature: int, freeze_bn: bool = True,
                  efficientnet: bool = False, backbone_number: int = 0):
         super().__init__()
@@ -146,11 +158,39 @@ class FCOS(PlannedModule):
         self.backbone.hip_stem_train = True
         return self
 
+    def enable_training(self):
+        """FCOS(efficientnet=True): opt in to training on the HIP autograd nodes (the MBConv trunk through train_ops.mbconv_rows).  Freezes the stem
+        (_conv_stem, _bn0: the Cin = 3 conv has no weight-gradient kernel, as MNFCOS freezes its 7x7 stem) -- the one departure from the reference's
+        trainable set -- and the never-run _conv_head / _bn1 / _fc, so that DDP needs no find_unused_parameters.  Build the optimizer after this call.
+        With the ResNet trunk, which trains as constructed, it does nothing.  Returns self."""
+        if not self.efficientnet:
+            return self
+        net = self.backbone.model
+        if net._conv_stem.weight.requires_grad:
+            import warnings
+            warnings.warn("FCOS.enable_training() freezes the EfficientNet stem (backbone.model._conv_stem / _bn0); an optimizer built before this call "
+                          "holds a parameter that no longer receives a gradient", stacklevel=2)
+        for m in (net._conv_stem, net._bn0, net._conv_head, net._bn1, net._fc):
+            for p in m.parameters():
+                p.requires_grad = False
+        self.hip_train = True
+        return self
+
+    def _train_forward_effnet(self, x: torch.Tensor):
+        from ..backbone.efficientnetv1 import trunk_train_forward
+        self._check_train_input(x)
+        if not self.backbone_freeze:
+            raise FdError("FCOS(efficientnet=True, freeze_bn=False): the HIP training path folds the backbone's BatchNorm layers frozen; batch statistics "
+                          "in the MBConv trunk are out of scope (construct the model with freeze_bn=True)")
+        T.PACKS.refresh()
+        return self.head.train_forward(self.FPN.train_forward(trunk_train_forward(self.backbone.model, x)))
+
     def forward(self, x: torch.Tensor, events=None):
         if not self.training:
             return self._eval_forward(x, events)
         if self.efficientnet:
-            self._check_train_input(x)
-            raise FdError("FCOS(efficientnet=True) is inference-only on the HIP path: the MBConv trunk has no backward "
-                          "kernels (the reference's train.py:92-97 never builds it); call model.eval()")
+            if not self.hip_train:
+                raise FdError("FCOS(efficientnet=True) is inference-only on the HIP path as constructed; call model.eval(), or opt in to training on "
+                              "the HIP autograd nodes with model.enable_training() (frozen stem and BatchNorm, no drop-connect)")
+            return self._train_forward_effnet(x)
         return self._train_forward(x)

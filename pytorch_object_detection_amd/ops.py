@@ -1013,6 +1013,37 @@ def dwconv2d(x: Rows, wkc: torch.Tensor, y: Rows, N: int, H: int, W: int, K: int
                                       pad_top, pad_left, Ho, Wo, act, _stream()), "fd_dwconv2d_nhwc")
 
 
+def dwconv2d_dgrad(dy: Rows, wkc: torch.Tensor, dx: Rows, N: int, H: int, W: int, K: int, stride: int, pad_top: int, pad_left: int,
+                   Ho: int, Wo: int, scale: Optional[torch.Tensor] = None) -> None:
+    """Data gradient of dwconv2d (K in {3, 5}, stride 1 / 2, the forward's padding and sizes): dx = scale * sum of dy * w over the taps that meet each input
+    pixel; wkc is the forward's [K*K][C].  Every pixel of dx is written (unreached rows / columns as 0)."""
+    _need_gpu(dy.buf, dx.buf, wkc, scale)
+    if dy.C != dx.C or dy.rows != N * Ho * Wo or dx.rows != N * H * W or dy.f16 or dx.f16 or tuple(wkc.shape) != (K * K, dx.C):
+        raise FdError(f"dwconv2d_dgrad: fp32 dy [{N}*{Ho}*{Wo}, C] / dx [{N}*{H}*{W}, C] views and w [{K * K}, C] expected "
+                      f"(got {dy.rows} x {dy.C}, {dx.rows} x {dx.C}, {tuple(wkc.shape)})")
+    check(_lib.lib().fd_dwconv2d_bwd_data_nhwc(dy.ptr, dy.cs, dy.co, wkc.data_ptr(), scale.data_ptr() if scale is not None else None, dx.ptr, dx.cs, dx.co,
+                                               N, H, W, dx.C, K, stride, pad_top, pad_left, Ho, Wo, _stream()), "fd_dwconv2d_bwd_data_nhwc")
+
+
+def dwconv2d_wgrad(x: Rows, dy: Rows, N: int, H: int, W: int, K: int, stride: int, pad_top: int, pad_left: int, Ho: int, Wo: int,
+                   scale: Optional[torch.Tensor] = None, torch_layout: bool = False) -> torch.Tensor:
+    """Weight gradient of dwconv2d given dy: [K*K][C], or [C][1][K][K] with torch_layout; `scale` multiplies it per channel (a frozen BatchNorm folded
+    into the forward).  Deterministic; two launches, no host sync."""
+    dev = x.buf.device
+    _need_gpu(x.buf, dy.buf, scale)
+    if dy.C != x.C or dy.rows != N * Ho * Wo or x.rows != N * H * W or dy.f16 or x.f16:
+        raise FdError(f"dwconv2d_wgrad: fp32 x [{N}*{H}*{W}, C] / dy [{N}*{Ho}*{Wo}, C] views expected (got {x.rows} x {x.C}, {dy.rows} x {dy.C})")
+    nb = _lib.lib().fd_dwconv2d_wgrad_workspace_bytes(N, Ho, Wo, x.C, K)
+    if nb < 0:
+        raise FdError(f"fd_dwconv2d_wgrad_workspace_bytes: bad arguments (N={N}, Ho={Ho}, Wo={Wo}, C={x.C}, K={K})")
+    ws = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+    dw = torch.empty((x.C, 1, K, K) if torch_layout else (K * K, x.C), dtype=torch.float32, device=dev)
+    check(_lib.lib().fd_dwconv2d_bwd_weight_nhwc(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, dw.data_ptr(), x.C, K, stride, pad_top, pad_left, N, H, W, Ho, Wo,
+                                                 scale.data_ptr() if scale is not None else None, 1 if torch_layout else 0, ws.data_ptr(), _stream()),
+          "fd_dwconv2d_bwd_weight_nhwc")
+    return dw
+
+
 def mbconv_fused_ok(Cin: int, mid: int, K: int, stride: int) -> bool:
     """Shapes fd_mbconv_expand_dw_nhwc covers (the input patch of a tile and two expanded tiles must fit LDS: Cin <= 48)."""
     return K in (3, 5) and stride in (1, 2) and 8 <= Cin <= 48 and Cin % 8 == 0 and mid % 4 == 0

@@ -10,6 +10,8 @@ over the whole pyramid exactly as at inference.
                             elementwise pass from the saved output), data gradient = the same conv kernel on dY with
                             flipped / transposed weights (stride-1 layers), weight gradient = fd_conv2d_bwd_weight_f32.
   dw_rows                   depthwise 3x3: fd_dwconv3x3_nhwc forward and data gradient, fd_dwconv3x3_bwd_weight_nhwc.
+  dw_kxk_rows               strided depthwise k x k with asymmetric padding (MBConv): fd_dwconv2d_nhwc forward, fd_dwconv2d_bwd_data_nhwc /
+                            fd_dwconv2d_bwd_weight_nhwc backward; mbconv_rows = the whole MBConv block on maps held at widths rounded up to 32.
   dw_dilated_rows           dilated depthwise k x k (MNBlock): fd_dwconv_dilated_nhwc forward and data gradient, fd_dwconv_dilated_bwd_weight_nhwc;
                             mn_block_rows = the whole MNBlock (depthwise, BatchNorm frozen or on batch statistics, PW1 + SiLU, PW2 + residual).
   deform_conv_rows          modulated deformable conv (DeformableConv2d): the sampler node fd_deform_im2col_nhwc / fd_deform_bwd_nhwc writes the columns,
@@ -683,6 +685,129 @@ def dw_dilated_rows(m: nn.Conv2d, x: torch.Tensor, segs: Segs, bn: Optional[nn.M
     if bn is not None:
         scale, shift = _bn_fold(bn)
     return _DwDilatedRows.apply(x, m.weight, scale, shift, segs, m.kernel_size[0], m.dilation[0])
+
+
+# ------------------------------------------------------- MBConv (EfficientNet trunk): strided depthwise k x k, whole block
+def round32(c: int) -> int:
+    return (c + 31) // 32 * 32
+
+
+class _DwKxKRows(torch.autograd.Function):
+    """Depthwise k x k (k in {3, 5}, stride in {1, 2}, asymmetric static "SAME" padding, no bias) on single-level rows: z = dw(x, w) * scale + shift,
+    scale / shift constants (a frozen BatchNorm), no activation (the swish behind it is an act_rows node that keeps z).  Forward fd_dwconv2d_nhwc,
+    backward fd_dwconv2d_bwd_data_nhwc / fd_dwconv2d_bwd_weight_nhwc.  fp32 under autocast, like the other depthwise nodes."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, weight, scale, shift, geom):
+        N, H, W, K, stride, pad_t, pad_l, Ho, Wo = geom
+        x = x.contiguous()
+        wkc = ops.pack_dwk_weight(weight)
+        y = torch.empty(N * Ho * Wo, x.shape[1], dtype=torch.float32, device=x.device)
+        ops.dwconv2d(_r(x), wkc, _r(y), N, H, W, K, stride, pad_t, pad_l, Ho, Wo, scale, shift, ACT_NONE)
+        ctx.save_for_backward(x, wkc, scale)
+        ctx.geom = geom
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        x, wkc, scale = ctx.saved_tensors
+        N, H, W, K, stride, pad_t, pad_l, Ho, Wo = ctx.geom
+        g = resolve_pending(gy).contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            ops.dwconv2d_dgrad(_r(g), wkc, _r(gx), N, H, W, K, stride, pad_t, pad_l, Ho, Wo, scale)
+        if ctx.needs_input_grad[1]:
+            gw = ops.dwconv2d_wgrad(_r(x), _r(g), N, H, W, K, stride, pad_t, pad_l, Ho, Wo, scale, torch_layout=True)
+        return gx, gw, None, None, None
+
+
+def _pad_affine(scale: torch.Tensor, shift: torch.Tensor, padn: int):
+    """A folded BatchNorm widened by `padn` pad channels: scale 1, shift 0 (a zero channel stays zero)."""
+    return (F.pad(scale, (0, padn), value=1.0), F.pad(shift, (0, padn))) if padn else (scale, shift)
+
+
+def dw_kxk_rows(m: nn.Conv2d, x: torch.Tensor, segs: Segs, pad, bn: Optional[nn.Module] = None) -> torch.Tensor:
+    """bn(m(x)) on single-level rows for an MBConv depthwise conv `m` (k in {3, 5}, stride in {1, 2}; `pad` = its static (before, after) padding) and a FROZEN
+    BatchNorm, or m(x) with bn=None.  x may be wider than m (a map held at its width rounded up to 32): the extra channels get zero taps, scale 1 and
+    shift 0 inside the autograd graph, so they stay exactly zero and the weight gradient comes back at m's own shape."""
+    K, s, Cc = m.kernel_size[0], m.stride[0], m.in_channels
+    if not (m.groups == Cc == m.out_channels and m.kernel_size == (K, K) and m.stride == (s, s) and K in (3, 5) and s in (1, 2) and m.dilation == (1, 1)
+            and m.bias is None and m.weight.dtype == torch.float32 and _f32(x) and x.shape[1] % 4 == 0 and x.shape[1] >= Cc and segs.nseg == 1
+            and 0 <= pad[0] < K and 0 <= pad[1] < K):
+        raise FdError(f"depthwise conv {tuple(m.weight.shape)} stride {m.stride} on {x.shape[1]} channels: the HIP nodes cover k in {{3, 5}}, "
+                      "stride in {1, 2}, no bias, fp32, C % 4 == 0, one level")
+    if bn is not None and not bn_is_frozen(bn):
+        raise FdError("dw_kxk_rows folds a FROZEN BatchNorm only")
+    N, (H, W) = segs.batch, segs.level_hw()[0]
+    Ho, Wo = (H + pad[0] + pad[1] - K) // s + 1, (W + pad[0] + pad[1] - K) // s + 1
+    if Ho < 1 or Wo < 1:
+        raise FdError(f"depthwise {K}x{K} stride {s} padding {tuple(pad)}: the {H}x{W} map is too small")
+    padn = x.shape[1] - Cc
+    w = F.pad(m.weight, (0, 0, 0, 0, 0, 0, 0, padn)) if padn else m.weight
+    scale = shift = None
+    if bn is not None:
+        scale, shift = _pad_affine(*_bn_fold(bn), padn)
+    return _DwKxKRows.apply(x, w, scale, shift, (N, H, W, K, s, pad[0], pad[0], Ho, Wo))
+
+
+def conv_rows_wide(m: nn.Conv2d, x: torch.Tensor, segs: Segs, bn: Optional[nn.Module] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_rows for maps held at their width rounded up to 32 with exactly-zero pad channels (the MBConv trunk: widths 16 / 24 / 40 / 48 / 112 / 136 / ...):
+    the weight is zero-padded inside the autograd graph -- columns up to x's width, rows up to round32(Cout) -- the folded BatchNorm with scale 1 / shift 0,
+    a bias with 0, and the output KEEPS its padded width (its pad channels are zero again).  Autograd slices the parameter gradients back."""
+    w, b = m.weight, m.bias
+    Cout, Cin = w.shape[0], w.shape[1]
+    pin, pout = x.shape[1] - Cin, round32(Cout) - Cout
+    if pin < 0 or x.shape[1] % 32:
+        raise FdError(f"conv_rows_wide: a {x.shape[1]}-channel map for a conv with {Cin} input channels (expected that width rounded up to 32)")
+    if pin or pout:
+        w = F.pad(w, (0, 0, 0, 0, 0, pin, 0, pout))
+        b = F.pad(b, (0, pout)) if (b is not None and pout) else b
+    scale = shift = None
+    if bn is not None:
+        scale, shift = _pad_affine(*_bn_fold(bn), pout)
+    if b is not None:
+        shift = b if scale is None else b * scale + shift
+    return _ConvRows.apply(x, w, scale, shift, residual, segs, m.stride[0], _pad_of(m), m.dilation[0], ACT_NONE, amp_prec(), False)
+
+
+def _mbconv_check(blk: nn.Module, x: torch.Tensor, segs: Segs) -> None:
+    bns = [blk._bn1, blk._bn2] + ([blk._bn0] if blk.expand != 1 else [])
+    if not all(bn_is_frozen(b) for b in bns):
+        raise FdError("MBConv: the HIP training nodes fold FROZEN BatchNorm layers only (batch statistics in the MBConv trunk are out of scope: "
+                      "build the model with freeze_bn=True and keep the backbone's BatchNorm layers in eval mode)")
+    convs = [blk._project_conv] + ([blk._expand_conv] if blk.expand != 1 else [])
+    if not all(c.kernel_size == (1, 1) and c.stride == (1, 1) and c.groups == 1 and c.bias is None and c.weight.dtype == torch.float32 for c in convs):
+        raise FdError("MBConv: 1x1 fp32 expand / project convs without bias expected")
+    if x.dim() != 2 or x.shape[1] != round32(blk.cin) or not _f32(x) or segs.nseg != 1 or x.shape[0] != segs.rows:
+        raise FdError(f"MBConv: block input must be single-level rows of width round32({blk.cin}) = {round32(blk.cin)} (got {tuple(x.shape)})")
+    se_c, se_r = blk._se_reduce, blk._se_expand
+    if se_c.bias is None or se_r.bias is None or round32(se_c.in_channels) > 4096 or se_c.out_channels > 1024:
+        raise FdError("MBConv: squeeze-excitation with biases, at most 4096 channels and 1024 squeezed channels expected")
+
+
+def mbconv_rows(blk: nn.Module, x: torch.Tensor, segs: Segs):
+    """One MBConvBlock (efficientnet_pytorch 0.7.1, parameters in model/backbone/efficientnetv1._MBConv) on single-level rows held at widths rounded up to 32
+    with zero pad channels, every op a differentiable HIP node: [expand 1x1 + bn0 -> swish] -> depthwise k x k + bn1 -> swish -> squeeze-excitation ->
+    project 1x1 + bn2 (+ the block input when blk.skip).  Returns (rows of width round32(blk.cout), their Segs).  Frozen BatchNorm only; no drop-connect.
+    What is not covered raises FdError: there is no stock fallback."""
+    _mbconv_check(blk, x, segs)
+    N, (H, W) = segs.batch, segs.level_hw()[0]
+    t = x
+    if blk.expand != 1:
+        t = act_rows(conv_rows_wide(blk._expand_conv, x, segs, blk._bn0), ACT_SILU)
+    t = act_rows(dw_kxk_rows(blk._depthwise_conv, t, segs, blk.pad, blk._bn1), ACT_SILU)
+    K, s = blk.kernel, blk.stride
+    Ho, Wo = (H + blk.pad[0] + blk.pad[1] - K) // s + 1, (W + blk.pad[0] + blk.pad[1] - K) // s + 1
+    so = Segs.make(N, [(Ho, Wo)])
+    padn = t.shape[1] - blk._se_reduce.in_channels
+    w1, w2, b2 = blk._se_reduce.weight, blk._se_expand.weight, blk._se_expand.bias
+    if padn:
+        w1, w2, b2 = F.pad(w1, (0, 0, 0, 0, 0, padn)), F.pad(w2, (0, 0, 0, 0, 0, 0, 0, padn)), F.pad(b2, (0, padn))
+    t = _SERows.apply(t, w1, blk._se_reduce.bias, w2, b2, N, Ho * Wo)
+    return conv_rows_wide(blk._project_conv, t, so, blk._bn2, residual=x if blk.skip else None), so
 
 
 # ------------------------------------------------------------------- modulated deformable conv (DeformableConv2d)
