@@ -501,6 +501,16 @@ int32_t fd_stem_conv_nhwc4(const float* x4, const float* w, const float* scale, 
                            int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, int32_t act,
                            fd_stream_t stream);
 
+/* Weight gradient of the 3-channel stem convolution fd_stem_conv_nhwc4 (EfficientNet._conv_stem): K = 3, stride = 2, Cout % 4 == 0, Cout <= 64 (anything else:
+ * FD_E_UNSUPPORTED).  dw[co][ci][ky][kx] = scale[co] * sum dy[n][oy][ox][co] * x4[n][2 oy - pad_top + ky][2 ox - pad_left + kx][ci]; taps outside the
+ * image contribute zero, channel 3 of x4 is ignored, scale may be NULL.  dy: a Cout-channel view of the [N][Ho][Wo] rows.  dw: torch's [Cout][3][3][3].
+ * Exact-fp32 MFMA over a fixed split of the output tiles (a function of the geometry alone); the slabs in `workspace`
+ * (fd_stem_conv_wgrad_workspace_bytes, -1 for an unsupported shape) are added in index order in fp64 by a second launch: no atomics, bit-identical repeats. */
+int64_t fd_stem_conv_wgrad_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t Cout, int32_t Ho, int32_t Wo);
+int32_t fd_stem_conv_bwd_weight_nhwc4(const float* x4, const float* dy, int32_t dy_cs, int32_t dy_co, const float* scale, float* dw, void* workspace,
+                                      int64_t workspace_bytes, int32_t N, int32_t H, int32_t W, int32_t Cout, int32_t K, int32_t stride,
+                                      int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, fd_stream_t stream);
+
 /* Mixed-aspect batch assembly on the device (dataset/voc.py:128-132 pad-to-32, :141-156 collate_fn):
  * N resized uint8 images of different sizes -> ONE normalised fp32 [N][H][W][4] batch (the stem's input layout).
  * images_dev: DEVICE array of N device pointers to [h_n][w_n][3] uint8; hw_dev: DEVICE int32 [N][2] = (h_n, w_n);
@@ -737,6 +747,31 @@ int32_t fd_batchnorm_sync_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, c
                                    const float* gamma, const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma,
                                    float* dbeta, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums,
                                    double total_rows, const void* fwd_workspace, void* workspace, fd_stream_t stream);
+
+/* nn.BatchNorm2d on BATCH statistics at any width: C % 4 == 0, 4 <= C <= 4096, 2 <= rows < 2^31, act in {NONE, RELU, SILU}, fp32 channel views under the layer
+ * kernels' view contract (nothing outside the C-channel views is read or written).  The fd_groupnorm_* / fd_batchnorm_sync_* route above serves only the
+ * widths whose quad count divides 256; these entry points serve every width (the EfficientNet trunk: 16 ... 2304; ResNet layer4: 2048).
+ *   forward   y = act((x - mean) * rstd * gamma + beta) with the biased batch variance; running_mean / running_var (both or neither) are updated as
+ *             nn.BatchNorm2d does (momentum, unbiased variance).  workspace = fd_batchnorm_train_workspace_bytes(rows, C) bytes, 8-byte aligned; the
+ *             forward leaves double mean[C], double rstd[C] (rstd rounded to fp32) at its start for the backward.
+ *   backward  dz = dy * act'(z) with z recomputed from x; dgamma = sum dz * xhat, dbeta = sum dz,
+ *             dx = rstd * (gamma * dz - mean(gamma * dz) - xhat * mean(gamma * dz * xhat)).  fwd_workspace: the forward's; workspace: another of the same size.
+ * Sums run in fp64 over a partition of the rows that is a function of (rows, C) alone and are added in index order: no atomics, two runs are bit-identical;
+ * no host synchronisation, no allocation.  Statistics and apply are separate launches.  Wrong shapes / activations: FD_E_UNSUPPORTED, bad pointers, views or
+ * workspaces: FD_E_INVAL, both before any launch.  The workspace query returns -1 for an unsupported shape. */
+int64_t fd_batchnorm_train_workspace_bytes(int64_t rows, int32_t C);
+int32_t fd_batchnorm_train_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
+                                    int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, float momentum, float* running_mean,
+                                    float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream);
+int32_t fd_batchnorm_train_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
+                                    const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows,
+                                    int32_t C, float eps, int32_t act, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
+                                    fd_stream_t stream);
+
+/* Drop-connect (stochastic depth) on [N][HW][C] fp32 channel views: y = a * s[n] + r, s = N floats on the device, r may be NULL; y may alias a.
+ * Two roundings, like the torch expression a * s + r. */
+int32_t fd_sample_scale_add_nhwc(const float* a, int32_t a_cs, int32_t a_co, const float* s, const float* r, int32_t r_cs, int32_t r_co, float* y,
+                                 int32_t y_cs, int32_t y_co, int32_t N, int32_t HW, int32_t C, fd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------- */
 /* Detection post-processing (reference model/modules/head.py:8-102,152-162, utill/utills.py:58-73)   */

@@ -1,0 +1,285 @@
+// fd_batchnorm.hip -- BatchNorm2d on BATCH STATISTICS at any width C % 4 == 0, 4 <= C <= 4096 (the EfficientNet trunk: 16 ... 2304 channels, ResNet layer4:
+// 2048), forward and backward on fp32 NHWC channel views, and the per-sample scale-add of drop-connect.
+//
+// The GroupNorm-with-G-=-C route of fd_layers.hip (fd_groupnorm_*, fd_batchnorm_sync_*) maps a thread to one channel quad of the WHOLE width and therefore
+// takes only widths whose quad count divides 256.  Here the width is cut into `ntile` channel tiles of QT <= 64 quads and the rows into `nchunk` row chunks;
+// a workgroup owns one (tile, chunk), thread t the quad t % QT on the row lane t / QT (RT = 256 / QT lanes; the 256 - QT * RT threads left over idle):
+//     ntile = ceil(C/4 / 64),  QT = ceil(C/4 / ntile),  nchunk = min(1024, ceil(rows / 32)) re-derived so that no chunk is empty
+// -- a function of (rows, C) alone.  Every sum is fp64: per thread over its rows in row order, the RT lanes in lane order (LDS), the chunks in index order by
+// a second launch (4 interleaved chunk lanes, added in lane order).  No atomics: two runs are bit-identical.  Statistics and apply are separate launches.
+//   forward    partial (sum x, sum x^2) -> final (mean, rstd, running statistics) -> apply y = act((x - mean) * rstd * gamma + beta)
+//   backward   partial (sum dz, sum dz * xhat; dz = dy * act'(z), z recomputed from x exactly as the forward computed it) -> final (dgamma, dbeta and the two
+//              per-channel constants c1 = rstd * gamma * mean(dz), c2 = rstd * gamma * mean(dz * xhat)) -> apply dx = rstd * gamma * dz - c1 - xhat * c2
+// workspace (both directions, fd_batchnorm_train_workspace_bytes): double [2][C] then double [nchunk][2][C].  The forward leaves mean[C], rstd[C] in the first
+// block (rstd rounded to fp32 first: the value the apply kernels multiply by); the backward leaves c1[C], c2[C] there.
+#include "fd_common.h"
+
+#define BN_MAXCHUNK 1024
+#define BN_MAXC 4096
+
+struct BnPart { int ntile, QT, RT, nchunk; long rows_per; };
+
+static BnPart bn_partition(int64_t rows, int32_t C) {
+    BnPart p;
+    const int C4 = C / 4;
+    p.ntile = (C4 + 63) / 64;
+    p.QT = (C4 + p.ntile - 1) / p.ntile;
+    p.RT = 256 / p.QT;
+    const int64_t want = (rows + 31) / 32 < BN_MAXCHUNK ? (rows + 31) / 32 : BN_MAXCHUNK;
+    p.rows_per = (long)((rows + want - 1) / want);
+    p.nchunk = (int)((rows + p.rows_per - 1) / p.rows_per);
+    return p;
+}
+
+static inline bool bn_view_ok(const void* p, int cs, int co, int C) {
+    return p && cs % 4 == 0 && co % 4 == 0 && co >= 0 && cs >= co + C && ((uintptr_t)p & 15) == 0;
+}
+
+__device__ __forceinline__ float bn_act_grad(float z, int act) {
+    if (act == FD_ACT_RELU) return z > 0.f ? 1.f : 0.f;
+    if (act == FD_ACT_SILU) { const float sg = fd_sigmoid(z); return sg * (1.f + z * (1.f - sg)); }
+    return 1.f;
+}
+
+struct BnArgs {
+    const float* x; const float* dy; const float* gamma; const float* beta; float* out;
+    int x_cs, x_co, dy_cs, dy_co, out_cs, out_co, C, QT, RT, act;
+    long rows, rows_per;
+};
+
+// per (tile, chunk): forward (sum x, sum x^2), backward (sum dz, sum dz * xhat) -> part[chunk][2][C]
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_partial_kernel(BnArgs a, const double* __restrict__ stat, double* __restrict__ part) {
+    __shared__ double s_a[1024], s_b[1024];          // [row lane][quad of the tile][4], at most 256 x 4
+    const int tid = threadIdx.x, ql = tid % a.QT, rt = tid / a.QT;
+    const int q = blockIdx.x * a.QT + ql, chunk = blockIdx.y;
+    const bool lane_ok = rt < a.RT, live = lane_ok && q < a.C / 4;
+    double sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
+    if (live) {
+        float mean[4], rstd[4], gm[4], bt[4];
+        if constexpr (BWD) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                mean[e] = (float)stat[4 * q + e]; rstd[e] = (float)stat[a.C + 4 * q + e]; gm[e] = a.gamma[4 * q + e]; bt[e] = a.beta[4 * q + e];
+            }
+        }
+        const long r_begin = (long)chunk * a.rows_per, r_end = min(a.rows, r_begin + a.rows_per);
+#pragma unroll 4
+        for (long r = r_begin + rt; r < r_end; r += a.RT) {
+            const float4 v4 = *reinterpret_cast<const float4*>(a.x + r * a.x_cs + a.x_co + 4 * q);
+            const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+            if constexpr (BWD) {
+                const float4 g4 = *reinterpret_cast<const float4*>(a.dy + r * a.dy_cs + a.dy_co + 4 * q);
+                const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float xh = (v[e] - mean[e]) * rstd[e];
+                    const float dz = g[e] * bn_act_grad(xh * gm[e] + bt[e], a.act);
+                    sa[e] += (double)dz; sb[e] += (double)dz * (double)xh;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { sa[e] += (double)v[e]; sb[e] += (double)v[e] * (double)v[e]; }
+            }
+        }
+    }
+    if (lane_ok) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { s_a[(rt * a.QT + ql) * 4 + e] = sa[e]; s_b[(rt * a.QT + ql) * 4 + e] = sb[e]; }
+    }
+    __syncthreads();
+    const int TC = a.QT * 4;
+    for (int i = tid; i < TC; i += 256) {
+        const int c = blockIdx.x * TC + i;
+        if (c >= a.C) continue;
+        double sum_a = 0, sum_b = 0;
+        for (int r = 0; r < a.RT; ++r) { sum_a += s_a[r * TC + i]; sum_b += s_b[r * TC + i]; }
+        part[((long)chunk * 2) * a.C + c] = sum_a;
+        part[((long)chunk * 2 + 1) * a.C + c] = sum_b;
+    }
+}
+
+// the chunk sums of 64 channels per workgroup: 4 chunk lanes walk the chunks 4 apart in index order and are added in lane order
+__device__ __forceinline__ bool bn_chunk_sums(const double* __restrict__ part, int nchunk, int C, double* s_a, double* s_b, int& c, double& A, double& B) {
+    const int tid = threadIdx.x, cl = tid & 63, kl = tid >> 6;
+    c = blockIdx.x * 64 + cl;
+    double a = 0, b = 0;
+    if (c < C)
+        for (int k = kl; k < nchunk; k += 4) { a += part[((long)k * 2) * C + c]; b += part[((long)k * 2 + 1) * C + c]; }
+    s_a[tid] = a; s_b[tid] = b;
+    __syncthreads();
+    if (kl != 0 || c >= C) return false;
+    A = ((a + s_a[64 + cl]) + s_a[128 + cl]) + s_a[192 + cl];
+    B = ((b + s_b[64 + cl]) + s_b[128 + cl]) + s_b[192 + cl];
+    return true;
+}
+
+__global__ __launch_bounds__(256) void bn_fwd_final_kernel(const double* __restrict__ part, int nchunk, int C, double count, float eps, float momentum,
+                                                            double* __restrict__ stat, float* __restrict__ rmean, float* __restrict__ rvar) {
+    __shared__ double s_a[256], s_b[256];
+    int c; double A, B;
+    if (!bn_chunk_sums(part, nchunk, C, s_a, s_b, c, A, B)) return;
+    const double mean = A / count;
+    double var = B / count - mean * mean;               // the biased batch variance
+    if (var < 0) var = 0;
+    stat[c] = mean;
+    stat[C + c] = (double)(float)(1.0 / sqrt(var + (double)eps));
+    if (rmean) {                                        // nn.BatchNorm2d: momentum update with the UNBIASED variance
+        const double unbiased = var * count / (count - 1.0);
+        rmean[c] = (float)((1.0 - (double)momentum) * (double)rmean[c] + (double)momentum * mean);
+        rvar[c] = (float)((1.0 - (double)momentum) * (double)rvar[c] + (double)momentum * unbiased);
+    }
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_final_kernel(const double* __restrict__ part, int nchunk, int C, double count, const float* __restrict__ gamma,
+                                                            const double* __restrict__ stat, double* __restrict__ coef, float* __restrict__ dgamma,
+                                                            float* __restrict__ dbeta) {
+    __shared__ double s_a[256], s_b[256];
+    int c; double A, B;
+    if (!bn_chunk_sums(part, nchunk, C, s_a, s_b, c, A, B)) return;
+    dbeta[c] = (float)A;
+    dgamma[c] = (float)B;
+    const double k = stat[C + c] * (double)gamma[c] / count;
+    coef[c] = k * A;
+    coef[C + c] = k * B;
+}
+
+// forward: y = act(xhat * gamma + beta); backward: dx = rstd * gamma * dz - c1 - xhat * c2.  Same (tile, chunk) ownership as the partial kernel.
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_apply_kernel(BnArgs a, const double* __restrict__ stat, const double* __restrict__ coef) {
+    const int tid = threadIdx.x, ql = tid % a.QT, rt = tid / a.QT;
+    const int q = blockIdx.x * a.QT + ql, chunk = blockIdx.y;
+    if (rt >= a.RT || q >= a.C / 4) return;
+    float mean[4], rstd[4], gm[4], bt[4], k1[4], c1[4], c2[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        mean[e] = (float)stat[4 * q + e]; rstd[e] = (float)stat[a.C + 4 * q + e]; gm[e] = a.gamma[4 * q + e]; bt[e] = a.beta[4 * q + e];
+        if constexpr (BWD) { k1[e] = rstd[e] * gm[e]; c1[e] = (float)coef[4 * q + e]; c2[e] = (float)coef[a.C + 4 * q + e]; }
+    }
+    const long r_begin = (long)chunk * a.rows_per, r_end = min(a.rows, r_begin + a.rows_per);
+#pragma unroll 4
+    for (long r = r_begin + rt; r < r_end; r += a.RT) {
+        const float4 v4 = *reinterpret_cast<const float4*>(a.x + r * a.x_cs + a.x_co + 4 * q);
+        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+        float o[4];
+        if constexpr (BWD) {
+            const float4 g4 = *reinterpret_cast<const float4*>(a.dy + r * a.dy_cs + a.dy_co + 4 * q);
+            const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float xh = (v[e] - mean[e]) * rstd[e];
+                const float dz = g[e] * bn_act_grad(xh * gm[e] + bt[e], a.act);
+                o[e] = (k1[e] * dz - c1[e]) - xh * c2[e];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = fd_act1((v[e] - mean[e]) * rstd[e] * gm[e] + bt[e], a.act, 0.f);
+        }
+        *reinterpret_cast<float4*>(a.out + r * a.out_cs + a.out_co + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+static bool bn_shape_ok(int64_t rows, int32_t C) { return C >= 4 && C <= BN_MAXC && C % 4 == 0 && rows >= 2 && rows < (1LL << 31); }
+
+extern "C" int64_t fd_batchnorm_train_workspace_bytes(int64_t rows, int32_t C) {
+    if (!bn_shape_ok(rows, C)) return -1;
+    const BnPart p = bn_partition(rows, C);
+    return ((int64_t)2 * C + (int64_t)p.nchunk * 2 * C) * (int64_t)sizeof(double);
+}
+
+extern "C" int32_t fd_batchnorm_train_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
+                                               int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, float momentum, float* running_mean,
+                                               float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    FD_REQUIRE(bn_shape_ok(rows, C), FD_E_UNSUPPORTED, "fd_batchnorm_train_fwd: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 2 <= rows < 2^31)",
+               (long long)rows, C, BN_MAXC);
+    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || act == FD_ACT_SILU, FD_E_UNSUPPORTED, "fd_batchnorm_train_fwd: activation %d unsupported", act);
+    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && bn_view_ok(y, y_cs, y_co, C) && gamma && beta, FD_E_INVAL,
+               "fd_batchnorm_train_fwd: bad pointer / channel view (C=%d)", C);
+    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "fd_batchnorm_train_fwd: running_mean and running_var go together");
+    FD_REQUIRE(eps >= 0.f, FD_E_INVAL, "fd_batchnorm_train_fwd: eps must not be negative");
+    const int64_t need = fd_batchnorm_train_workspace_bytes(rows, C);
+    FD_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
+               "fd_batchnorm_train_fwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes, (long long)need);
+    const BnPart p = bn_partition(rows, C);
+    BnArgs a;
+    a.x = x; a.dy = nullptr; a.gamma = gamma; a.beta = beta; a.out = y;
+    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = 0; a.dy_co = 0; a.out_cs = y_cs; a.out_co = y_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
+    a.rows = (long)rows; a.rows_per = p.rows_per;
+    double* stat = (double*)workspace;
+    double* part = stat + 2 * (long)C;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, part);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (partial)");
+    hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)part, p.nchunk, C, (double)rows, eps, momentum, stat,
+                       running_mean, running_var);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (statistics)");
+    hipLaunchKernelGGL((bn_apply_kernel<false>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, (const double*)nullptr);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (apply)");
+    return FD_OK;
+}
+
+extern "C" int32_t fd_batchnorm_train_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
+                                               const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows,
+                                               int32_t C, float eps, int32_t act, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
+                                               fd_stream_t stream) {
+    (void)eps;                                          // (rstd comes from the forward's workspace)
+    FD_REQUIRE(bn_shape_ok(rows, C), FD_E_UNSUPPORTED, "fd_batchnorm_train_bwd: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 2 <= rows < 2^31)",
+               (long long)rows, C, BN_MAXC);
+    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || act == FD_ACT_SILU, FD_E_UNSUPPORTED, "fd_batchnorm_train_bwd: activation %d has no backward", act);
+    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && bn_view_ok(dy, dy_cs, dy_co, C) && bn_view_ok(dx, dx_cs, dx_co, C) && gamma && beta && dgamma && dbeta,
+               FD_E_INVAL, "fd_batchnorm_train_bwd: bad pointer / channel view (C=%d)", C);
+    const int64_t need = fd_batchnorm_train_workspace_bytes(rows, C);
+    FD_REQUIRE(fwd_workspace && ((uintptr_t)fwd_workspace & 7) == 0 && workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
+               "fd_batchnorm_train_bwd: the forward's workspace and a workspace of %lld bytes needed (got %lld; 8-byte aligned)", (long long)need,
+               (long long)workspace_bytes);
+    const BnPart p = bn_partition(rows, C);
+    BnArgs a;
+    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.out = dx;
+    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = dy_cs; a.dy_co = dy_co; a.out_cs = dx_cs; a.out_co = dx_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
+    a.rows = (long)rows; a.rows_per = p.rows_per;
+    const double* stat = (const double*)fwd_workspace;
+    double* coef = (double*)workspace;
+    double* part = coef + 2 * (long)C;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL((bn_partial_kernel<true>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, stat, part);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (partial)");
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)part, p.nchunk, C, (double)rows, gamma, stat, coef, dgamma,
+                       dbeta);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (sums)");
+    hipLaunchKernelGGL((bn_apply_kernel<true>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, stat, (const double*)coef);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (apply)");
+    return FD_OK;
+}
+
+// ---- drop-connect: y = a * s[n] + r on [N][HW][C] channel views, s one fp32 per sample ON THE DEVICE (0 or 1 / (1 - p)), r may be NULL (the backward of the
+// branch: the incoming gradient times s).  Elementwise with two roundings like the torch expression a * s + r; y may alias a.
+__global__ __launch_bounds__(256) void sample_scale_add_kernel(const float* a, int a_cs, int a_co, const float* __restrict__ s, const float* r, int r_cs,
+                                                                int r_co, float* y, int y_cs, int y_co, int HW, int C4, long total) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        int q, px;
+        const long m = fd_div(i, C4, q);
+        const long n = fd_div(m, HW, px);
+        const float sc = s[n];
+        const float4 v = *reinterpret_cast<const float4*>(a + m * a_cs + a_co + 4 * q);
+        float4 o = make_float4(v.x * sc, v.y * sc, v.z * sc, v.w * sc);
+        if (r) {
+            const float4 u = *reinterpret_cast<const float4*>(r + m * r_cs + r_co + 4 * q);
+            o.x += u.x; o.y += u.y; o.z += u.z; o.w += u.w;
+        }
+        *reinterpret_cast<float4*>(y + m * y_cs + y_co + 4 * q) = o;
+    }
+}
+
+extern "C" int32_t fd_sample_scale_add_nhwc(const float* a, int32_t a_cs, int32_t a_co, const float* s, const float* r, int32_t r_cs, int32_t r_co, float* y,
+                                            int32_t y_cs, int32_t y_co, int32_t N, int32_t HW, int32_t C, fd_stream_t stream) {
+    FD_REQUIRE(N >= 1 && HW >= 1 && C >= 4 && C % 4 == 0 && (int64_t)N * HW < (1LL << 31), FD_E_INVAL,
+               "fd_sample_scale_add: N >= 1, HW >= 1, N * HW < 2^31, C %% 4 == 0 (got N=%d HW=%d C=%d)", N, HW, C);
+    FD_REQUIRE(bn_view_ok(a, a_cs, a_co, C) && bn_view_ok(y, y_cs, y_co, C) && (!r || bn_view_ok(r, r_cs, r_co, C)) && s && ((uintptr_t)s & 3) == 0, FD_E_INVAL,
+               "fd_sample_scale_add: bad pointer / channel view (C=%d)", C);
+    const long total = (long)N * HW * (C / 4);
+    const long blocks = (total + 255) / 256;
+    hipLaunchKernelGGL(sample_scale_add_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, (hipStream_t)stream, a, a_cs, a_co, s, r, r_cs,
+                       r_co, y, y_cs, y_co, HW, C / 4, total);
+    FD_CHECK_LAUNCH("fd_sample_scale_add_nhwc");
+    return FD_OK;
+}

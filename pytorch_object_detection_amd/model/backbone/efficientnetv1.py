@@ -87,14 +87,19 @@ class _MBConv(nn.Module):
 class _EfficientNet(nn.Module):
     """`EfficientNet.from_name(model_name)` as a parameter container (state_dict keys of efficientnet_pytorch 0.7.1)."""
 
+    # the opt-in switches of FCOS.enable_training(train_stem, batch_stats, drop_connect_rate); set on the instance only by that call
+    train_stem = False
+    batch_stats = False
+    drop_connect_accepted = 0.0
+
     def __init__(self, model_name: str):
         super().__init__()
         if model_name not in _COEFF:
             raise FdError(f"unknown EfficientNet '{model_name}'")
         width, depth, res, _ = _COEFF[model_name]
         self.model_name, self.image_size = model_name, res
-        # efficientnet_pytorch applies stochastic depth (drop_connect_rate 0.2) in train mode; the HIP training path has no such node and trains without it:
-        # 0.0 here, and trunk_train_forward refuses any other value (INTEGRATION.md)
+        # efficientnet_pytorch applies stochastic depth (drop_connect_rate 0.2) in train mode; the HIP training path trains without it unless
+        # FCOS.enable_training(drop_connect_rate=r) opts in: 0.0 here, and trunk_train_forward refuses any value that call did not accept (INTEGRATION.md)
         self.drop_connect_rate = 0.0
         stem = _scaled_width(32, width)
         self._conv_stem = nn.Conv2d(3, stem, 3, 2, bias=False)
@@ -121,14 +126,44 @@ def _out_hw(h: int, w: int, k: int, s: int, pad) -> Tuple[int, int]:
     return (h + pad[0] + pad[1] - k) // s + 1, (w + pad[0] + pad[1] - k) // s + 1
 
 
-def _trunk_stock(net: "_EfficientNet", x: torch.Tensor):
-    """The trunk on stock PyTorch-ROCm ops (FD_TRAIN_STOCK_CONV=1 only: the diagnostic mode that times the HIP step against them)."""
+def _drop_scales(net: "_EfficientNet", B: int, device, drop_u):
+    """Per block the drop-connect scales [B] (train_ops.drop_connect_scale) or None: p = rate * idx / len(blocks), applied only to skip blocks and only when
+    p > 0 (block 0 never drops).  drop_u: optional [len(blocks), B] uniform numbers (tests); else torch.rand on the device, one draw per dropping block."""
+    blocks = list(net._blocks)
+    rate = float(net.drop_connect_rate)
+    if drop_u is not None and (drop_u.dim() != 2 or tuple(drop_u.shape) != (len(blocks), B)):
+        raise FdError(f"EfficientNet trunk: drop_u must be [len(blocks), B] = [{len(blocks)}, {B}] (got {tuple(drop_u.shape)})")
+    out = []
+    for i, blk in enumerate(blocks):
+        p = rate * i / len(blocks)
+        if not (blk.skip and p > 0):
+            out.append(None)
+            continue
+        u = drop_u[i].to(device) if drop_u is not None else torch.rand(B, dtype=torch.float32, device=device)
+        out.append(T.drop_connect_scale(p, u))
+    return out
+
+
+def _trunk_stock(net: "_EfficientNet", x: torch.Tensor, drop_u=None):
+    """The trunk on stock PyTorch-ROCm ops (FD_TRAIN_STOCK_CONV=1 only: the diagnostic mode that times the HIP step against them); follows the train_stem /
+    batch_stats / drop-connect switches of enable_training with the same drop_u."""
     swish = lambda t: t * torch.sigmoid(t)  # noqa: E731
-    bn = lambda m, t: F.batch_norm(t, m.running_mean, m.running_var, m.weight, m.bias, False, 0.0, m.eps)  # noqa: E731
+    frozen = lambda m, t: F.batch_norm(t, m.running_mean, m.running_var, m.weight, m.bias, False, 0.0, m.eps)  # noqa: E731
+
+    def batch(m, t):
+        if m.num_batches_tracked is not None:
+            m.num_batches_tracked.add_(1)
+        return F.batch_norm(t, m.running_mean, m.running_var, m.weight, m.bias, True, m.momentum, m.eps)
+
+    bn = batch if net.batch_stats else frozen
     same = lambda t, pad: F.pad(t, (pad[0], pad[1], pad[0], pad[1])) if (pad[0] or pad[1]) else t  # noqa: E731
-    with torch.no_grad():
+    if net.train_stem:
         x = swish(bn(net._bn0, F.conv2d(same(x, net.stem_pad), net._conv_stem.weight, None, 2)))
+    else:
+        with torch.no_grad():
+            x = swish(frozen(net._bn0, F.conv2d(same(x, net.stem_pad), net._conv_stem.weight, None, 2)))
     ends, blocks = [], list(net._blocks)
+    scales = _drop_scales(net, x.shape[0], x.device, drop_u)
     for i, blk in enumerate(blocks):
         inp = x
         if blk.expand != 1:
@@ -138,44 +173,57 @@ def _trunk_stock(net: "_EfficientNet", x: torch.Tensor):
         x = torch.sigmoid(F.conv2d(sq, blk._se_expand.weight, blk._se_expand.bias)) * x
         x = bn(blk._bn2, F.conv2d(x, blk._project_conv.weight))
         if blk.skip:
-            x = x + inp
+            x = (x if scales[i] is None else x * scales[i].view(-1, 1, 1, 1)) + inp
         if i + 1 == len(blocks) or blocks[i + 1].stride > 1:
             ends.append(x)
     return tuple(ends[-3:])
 
 
-def trunk_train_forward(net: "_EfficientNet", x: torch.Tensor):
+def trunk_train_forward(net: "_EfficientNet", x: torch.Tensor, drop_u=None):
     """The EfficientNet trunk of a training step on the HIP autograd nodes: image batch [B, 3, H, W] -> (C3, C4, C5), the endpoints reduction_3/4/5 as
-    NCHW-shaped channels-last views.  The stem (_conv_stem + _bn0 + swish) is frozen and runs on the inference kernel without a graph; every MBConv block
-    is train_ops.mbconv_rows.  Every map from the stem output to the endpoints is held at its width ROUNDED UP TO 32 with pad channels that are exactly
-    zero (forward and backward), so the returned maps are round32(48 / 136 / 384) wide: FeaturePyramidNetwork.train_forward pads its lateral weights."""
-    if net.drop_connect_rate:
+    NCHW-shaped channels-last views.  As FCOS.enable_training() leaves the model, the stem (_conv_stem + _bn0 + swish) is frozen and runs on the inference
+    kernel without a graph, and every MBConv block is train_ops.mbconv_rows on frozen BatchNorm layers.  The switches of enable_training change that:
+    net.train_stem (the stem is train_ops.effnet_stem_rows, with its weight gradient), net.batch_stats (every BatchNorm of the blocks, and the stem's when it
+    trains, on batch statistics) and a drop_connect_rate accepted there (stochastic depth on the skip blocks; drop_u: optional [len(blocks), B] uniform
+    numbers that replace the torch.rand draws).  Every map from the stem output to the endpoints is held at its width ROUNDED UP TO 32 with pad channels that
+    are exactly zero (forward and backward), so the returned maps are round32(48 / 136 / 384) wide: FeaturePyramidNetwork.train_forward pads its lateral
+    weights."""
+    if net.drop_connect_rate and net.drop_connect_rate != net.drop_connect_accepted:
         raise FdError(f"EfficientNet trunk: drop_connect_rate={net.drop_connect_rate} is not supported on the HIP training path (it trains without "
                       "stochastic depth: set model.drop_connect_rate = 0.0)")
-    if not T.bn_is_frozen(net._bn0) or net._conv_stem.weight.requires_grad:
+    if not net.train_stem and not net.batch_stats and (not T.bn_is_frozen(net._bn0) or net._conv_stem.weight.requires_grad):
         raise FdError("EfficientNet trunk: the HIP training path needs a frozen stem (_conv_stem, _bn0) and frozen BatchNorm layers "
                       "(FCOS(..., freeze_bn=True).enable_training(); batch statistics in the MBConv trunk are out of scope)")
+    if not net.train_stem and (net._conv_stem.weight.requires_grad or net._bn0.weight.requires_grad):
+        raise FdError("EfficientNet trunk: without train_stem the stem (_conv_stem, _bn0) must not require gradients (FCOS.enable_training() freezes it)")
     if x.dim() != 4 or x.shape[1] != 3 or not T._f32(x) or x.requires_grad:
         raise FdError("EfficientNet trunk: expected an image batch [B, 3, H, W] that needs no gradient")
     if T._STOCK:
-        return _trunk_stock(net, x.float())
+        return _trunk_stock(net, x.float(), drop_u)
     B, _, H, W = x.shape
     dev = x.device
-    with torch.no_grad():
-        x4 = torch.empty(B * H * W, 4, dtype=torch.float32, device=dev)
-        ops.nchw3_to_nhwc4(x.float().contiguous(), x4)
-        C0 = net._conv_stem.out_channels
-        h, w = _out_hw(H, W, 3, 2, net.stem_pad)
-        if h < 1 or w < 1:
-            raise FdError("EfficientNet: input too small")
-        sc, sf = T._bn_fold(net._bn0)
-        buf = (torch.zeros if T.round32(C0) != C0 else torch.empty)(B * h * w, T.round32(C0), dtype=torch.float32, device=dev)
-        ops.stem_conv3(x4, ops.pack_stem3_weight(net._conv_stem.weight), ops.Rows(buf, 0, C0), B, H, W, 3, 2, net.stem_pad[0], net.stem_pad[0], h, w,
-                       sc, sf, ops.ACT_SILU)
+    C0 = net._conv_stem.out_channels
+    h, w = _out_hw(H, W, 3, 2, net.stem_pad)
+    if h < 1 or w < 1:
+        raise FdError("EfficientNet: input too small")
+    if net.train_stem:
+        buf = T.effnet_stem_rows(net, x.float(), h, w, net.batch_stats)
+    else:
+        with torch.no_grad():           # (folded on the running statistics whatever _bn0.training says)
+            x4 = torch.empty(B * H * W, 4, dtype=torch.float32, device=dev)
+            ops.nchw3_to_nhwc4(x.float().contiguous(), x4)
+            sc, sf = T._bn_fold(net._bn0)
+            buf = (torch.zeros if T.round32(C0) != C0 else torch.empty)(B * h * w, T.round32(C0), dtype=torch.float32, device=dev)
+            ops.stem_conv3(x4, ops.pack_stem3_weight(net._conv_stem.weight), ops.Rows(buf, 0, C0), B, H, W, 3, 2, net.stem_pad[0], net.stem_pad[0], h, w,
+                           sc, sf, ops.ACT_SILU)
     t, segs = buf, Segs.make(B, [(h, w)])
     ends, blocks = [], list(net._blocks)
+    scales = _drop_scales(net, B, dev, drop_u) if net.drop_connect_rate else [None] * len(blocks)
     for i, blk in enumerate(blocks):
-        t, segs = T.mbconv_rows(blk, t, segs)
+        if net.batch_stats or scales[i] is not None:
+            t, segs = T.mbconv_rows(blk, t, segs, batch_stats=net.batch_stats, drop_scale=scales[i])
+        else:
+            t, segs = T.mbconv_rows(blk, t, segs)
         if i + 1 == len(blocks) or blocks[i + 1].stride > 1:
             ends.append(T.from_rows(t, B, segs.H[0], segs.W[0]))
     return tuple(ends[-3:])
@@ -185,7 +233,8 @@ class EfficientNetV1(PlannedModule):
     """Reference model/backbone/efficientnetv1.py:11-26.  forward(x [B,3,H,W] fp32 CUDA) -> list of the five endpoints
     reduction_1..reduction_5 (strides 2, 4, 8, 16, 32; B3: 24, 32, 48, 136, 384 channels) as NCHW-shaped channels-last
     views of plan-owned buffers.  Stand-alone the wrapper is inference only (BatchNorm folded, eval); the trunk TRAINS inside FCOS(efficientnet=True)
-    after enable_training(), through trunk_train_forward (MBConv blocks on the HIP autograd nodes, frozen stem and BatchNorm, no drop-connect)."""
+    after enable_training(), through trunk_train_forward (MBConv blocks on the HIP autograd nodes; frozen stem and BatchNorm and no drop-connect unless that
+    call's train_stem / batch_stats / drop_connect_rate switches opt in)."""
 
     def __init__(self, backbone_number: int, memory_efficient: bool = False):
         super().__init__()
@@ -194,7 +243,8 @@ class EfficientNetV1(PlannedModule):
 
     @property
     def drop_connect_rate(self) -> float:
-        """Stochastic-depth rate of the training path: 0.0 (efficientnet_pytorch trains at 0.2; the HIP path has no such node and refuses anything else)."""
+        """Stochastic-depth rate of the training path: 0.0 (efficientnet_pytorch trains at 0.2); the HIP path refuses any value that
+        FCOS.enable_training(drop_connect_rate=r) did not accept."""
         return self.model.drop_connect_rate
 
     @drop_connect_rate.setter

@@ -158,39 +158,53 @@ class FCOS(PlannedModule):
         self.backbone.hip_stem_train = True
         return self
 
-    def enable_training(self):
-        """FCOS(efficientnet=True): opt in to training on the HIP autograd nodes (the MBConv trunk through train_ops.mbconv_rows).  Freezes the stem
-        (_conv_stem, _bn0: the Cin = 3 conv has no weight-gradient kernel, as MNFCOS freezes its 7x7 stem) -- the one departure from the reference's
-        trainable set -- and the never-run _conv_head / _bn1 / _fc, so that DDP needs no find_unused_parameters.  Build the optimizer after this call.
-        With the ResNet trunk, which trains as constructed, it does nothing.  Returns self."""
+    def enable_training(self, train_stem: bool = False, batch_stats: bool = False, drop_connect_rate: float = 0.0):
+        """FCOS(efficientnet=True): opt in to training on the HIP autograd nodes (the MBConv trunk through train_ops.mbconv_rows).  As called without
+        arguments it freezes the stem (_conv_stem, _bn0) -- the one departure from the reference's trainable set -- and the never-run _conv_head / _bn1 /
+        _fc, so that DDP needs no find_unused_parameters, and trains on frozen BatchNorm layers without drop-connect.  Three switches close those departures
+        from how efficientnet_pytorch trains:
+          train_stem=True          _conv_stem stays trainable (fd_stem_conv_bwd_weight_nhwc4), and _bn0 with it when batch_stats is on
+          batch_stats=True         the trunk's BatchNorm layers run on batch statistics with trainable affine parameters (fd_batchnorm_train_*); needs a model
+                                   constructed with freeze_bn=False.  With train_stem=False the stem stays folded on its running statistics
+          drop_connect_rate=r      stochastic depth on the skip blocks at the package's per-block rate r * idx / len(blocks) (fd_sample_scale_add_nhwc)
+        Build the optimizer after this call.  With the ResNet trunk, which trains as constructed, it does nothing.  Returns self."""
         if not self.efficientnet:
             return self
         net = self.backbone.model
-        if net._conv_stem.weight.requires_grad:
+        if batch_stats and self.backbone_freeze:
+            raise FdError("FCOS.enable_training(batch_stats=True) needs a model constructed with freeze_bn=False (this one froze its BatchNorm layers)")
+        if not 0.0 <= float(drop_connect_rate) < 1.0:
+            raise FdError(f"FCOS.enable_training: drop_connect_rate must be in [0, 1) (got {drop_connect_rate})")
+        stem_on = bool(train_stem)
+        if not stem_on and net._conv_stem.weight.requires_grad:
             import warnings
             warnings.warn("FCOS.enable_training() freezes the EfficientNet stem (backbone.model._conv_stem / _bn0); an optimizer built before this call "
                           "holds a parameter that no longer receives a gradient", stacklevel=2)
-        for m in (net._conv_stem, net._bn0, net._conv_head, net._bn1, net._fc):
+        frozen = (net._conv_head, net._bn1, net._fc) + (() if stem_on else (net._conv_stem, net._bn0))
+        for m in frozen:
             for p in m.parameters():
                 p.requires_grad = False
+        if stem_on or batch_stats or drop_connect_rate:
+            net.train_stem, net.batch_stats = stem_on, bool(batch_stats)
+            net.drop_connect_rate = net.drop_connect_accepted = float(drop_connect_rate)
         self.hip_train = True
         return self
 
-    def _train_forward_effnet(self, x: torch.Tensor):
+    def _train_forward_effnet(self, x: torch.Tensor, drop_u=None):
         from ..backbone.efficientnetv1 import trunk_train_forward
         self._check_train_input(x)
-        if not self.backbone_freeze:
+        if not self.backbone_freeze and not self.backbone.model.batch_stats:
             raise FdError("FCOS(efficientnet=True, freeze_bn=False): the HIP training path folds the backbone's BatchNorm layers frozen; batch statistics "
                           "in the MBConv trunk are out of scope (construct the model with freeze_bn=True)")
         T.PACKS.refresh()
-        return self.head.train_forward(self.FPN.train_forward(trunk_train_forward(self.backbone.model, x)))
+        return self.head.train_forward(self.FPN.train_forward(trunk_train_forward(self.backbone.model, x, drop_u)))
 
-    def forward(self, x: torch.Tensor, events=None):
+    def forward(self, x: torch.Tensor, events=None, drop_u=None):
         if not self.training:
             return self._eval_forward(x, events)
         if self.efficientnet:
             if not self.hip_train:
                 raise FdError("FCOS(efficientnet=True) is inference-only on the HIP path as constructed; call model.eval(), or opt in to training on "
                               "the HIP autograd nodes with model.enable_training() (frozen stem and BatchNorm, no drop-connect)")
-            return self._train_forward_effnet(x)
+            return self._train_forward_effnet(x, drop_u)
         return self._train_forward(x)

@@ -1640,6 +1640,78 @@ def batchnorm_update_running_dev(gn_ws: torch.Tensor, count: torch.Tensor, Cc: i
                                                      running_var.data_ptr(), _stream()), "fd_batchnorm_update_running_dev")
 
 
+def batchnorm_train_workspace(rows: int, Cc: int, device) -> torch.Tensor:
+    """A workspace of batchnorm_train_fwd / _bwd (fd_batchnorm_train_workspace_bytes) as float64 elements: the forward leaves mean[C], rstd[C] at its start."""
+    nb = _lib.lib().fd_batchnorm_train_workspace_bytes(rows, Cc)
+    if nb < 0:
+        raise FdError(f"batch-statistics BatchNorm over {rows} rows of {Cc} channels: the HIP kernels cover C % 4 == 0, 4 <= C <= 4096, 2 <= rows < 2^31",
+                      rc=_lib.E_UNSUPPORTED)
+    return torch.empty(nb // 8, dtype=torch.float64, device=device)
+
+
+def batchnorm_train_fwd(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, y: Rows, eps: float, act_id: int = ACT_NONE, momentum: Optional[float] = None,
+                        running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = act(BatchNorm(x)) on the batch statistics of the fp32 channel view x (fd_batchnorm_train_fwd_nhwc: any C % 4 == 0 up to 4096).  With `momentum`
+    and the running tensors given they are updated in place like nn.BatchNorm2d's.  Returns the workspace batchnorm_train_bwd needs."""
+    _need_gpu(x.buf, y.buf, gamma, beta, running_mean, running_var, ws)
+    if x.f16 or y.f16 or x.C != y.C or x.rows != y.rows or gamma.numel() != x.C or beta.numel() != x.C:
+        raise FdError("batchnorm_train_fwd: fp32 views of the same shape and C-element gamma / beta expected")
+    if ws is None:
+        ws = batchnorm_train_workspace(x.rows, x.C, x.buf.device)
+    upd = momentum is not None and running_mean is not None and running_var is not None
+    check(_lib.lib().fd_batchnorm_train_fwd_nhwc(x.ptr, x.cs, x.co, gamma.data_ptr(), beta.data_ptr(), y.ptr, y.cs, y.co, x.rows, x.C, float(eps), act_id,
+                                                 float(momentum) if upd else 0.0, running_mean.data_ptr() if upd else None,
+                                                 running_var.data_ptr() if upd else None, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+          "fd_batchnorm_train_fwd_nhwc")
+    return ws
+
+
+def batchnorm_train_bwd(x: Rows, dy: Rows, gamma: torch.Tensor, beta: torch.Tensor, dx: Rows, eps: float, act_id: int, fwd_ws: torch.Tensor,
+                        ws: Optional[torch.Tensor] = None):
+    """The backward of batchnorm_train_fwd (fd_batchnorm_train_bwd_nhwc): writes dx, returns (dgamma, dbeta)."""
+    _need_gpu(x.buf, dy.buf, dx.buf, gamma, beta, fwd_ws, ws)
+    if x.f16 or dy.f16 or dx.f16 or not (x.C == dy.C == dx.C) or not (x.rows == dy.rows == dx.rows):
+        raise FdError("batchnorm_train_bwd: fp32 views of the same shape expected")
+    if ws is None:
+        ws = batchnorm_train_workspace(x.rows, x.C, x.buf.device)
+    dgamma = torch.empty(x.C, dtype=torch.float32, device=x.buf.device)
+    dbeta = torch.empty(x.C, dtype=torch.float32, device=x.buf.device)
+    check(_lib.lib().fd_batchnorm_train_bwd_nhwc(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gamma.data_ptr(), beta.data_ptr(), dx.ptr, dx.cs, dx.co,
+                                                 dgamma.data_ptr(), dbeta.data_ptr(), x.rows, x.C, float(eps), act_id, fwd_ws.data_ptr(), ws.data_ptr(),
+                                                 ws.numel() * ws.element_size(), _stream()), "fd_batchnorm_train_bwd_nhwc")
+    return dgamma, dbeta
+
+
+def sample_scale_add(a: Rows, s: torch.Tensor, r: Optional[Rows], y: Rows, N: int, HW: int) -> None:
+    """y = a * s[n] + r on [N * HW, C] fp32 channel views (fd_sample_scale_add_nhwc: drop-connect); s = N fp32 on the device, r may be None, y may alias a."""
+    _need_gpu(a.buf, s, r.buf if r is not None else None, y.buf)
+    if a.f16 or y.f16 or (r is not None and r.f16) or s.dtype != torch.float32 or s.numel() != N or not s.is_contiguous():
+        raise FdError("sample_scale_add: fp32 views and N contiguous fp32 scales expected")
+    if a.rows != N * HW or y.rows != N * HW or a.C != y.C or (r is not None and (r.rows != N * HW or r.C != a.C)):
+        raise FdError(f"sample_scale_add: views do not match N={N}, HW={HW}")
+    check(_lib.lib().fd_sample_scale_add_nhwc(a.ptr, a.cs, a.co, s.data_ptr(), r.ptr if r is not None else None, r.cs if r is not None else 0,
+                                              r.co if r is not None else 0, y.ptr, y.cs, y.co, N, HW, a.C, _stream()), "fd_sample_scale_add_nhwc")
+
+
+def stem_conv3_wgrad(x4: torch.Tensor, dy: Rows, N: int, H: int, W: int, K: int, stride: int, pad_top: int, pad_left: int, Ho: int, Wo: int,
+                     scale: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Weight gradient [Cout, 3, 3, 3] of stem_conv3 given dy, a Cout-channel view of the [N * Ho * Wo] output rows (fd_stem_conv_bwd_weight_nhwc4); `scale`
+    multiplies the result per output channel (a frozen BatchNorm folded into the forward).  Deterministic; two launches, no host sync."""
+    _need_gpu(x4, dy.buf, scale, ws)
+    if x4.dtype != torch.float32 or x4.dim() != 2 or x4.shape != (N * H * W, 4) or not x4.is_contiguous() or dy.f16 or dy.rows != N * Ho * Wo:
+        raise FdError(f"stem_conv3_wgrad: the fp32 [N*H*W, 4] image buffer and fp32 gradient rows [N*Ho*Wo] expected (N={N}, H={H}, W={W}, Ho={Ho}, Wo={Wo})")
+    if ws is None:
+        nb = _lib.lib().fd_stem_conv_wgrad_workspace_bytes(N, H, W, dy.C, Ho, Wo)
+        if nb < 0:
+            raise FdError(f"stem_conv3_wgrad: Cout % 4 == 0, Cout <= 64 and a non-empty geometry expected (Cout={dy.C})", rc=_lib.E_UNSUPPORTED)
+        ws = torch.empty(nb // 4, dtype=torch.float32, device=dy.buf.device)
+    dw = torch.empty(dy.C, 3, K, K, dtype=torch.float32, device=dy.buf.device)
+    check(_lib.lib().fd_stem_conv_bwd_weight_nhwc4(x4.data_ptr(), dy.ptr, dy.cs, dy.co, scale.data_ptr() if scale is not None else None, dw.data_ptr(),
+                                                   ws.data_ptr(), ws.numel() * ws.element_size(), N, H, W, dy.C, K, stride, pad_top, pad_left, Ho, Wo,
+                                                   _stream()), "fd_stem_conv_bwd_weight_nhwc4")
+    return dw
+
+
 # ---------------------------------------------------------------------------------------------------- post-process
 def fcos_decode(cls: Rows, cnt: Rows, reg: Rows, segs: Segs, strides: Sequence[int]):
     """-> scores [N,L] f32, classes [N,L] i32, boxes [N,L,4] f32 (levels concatenated per image)."""

@@ -773,9 +773,13 @@ def conv_rows_wide(m: nn.Conv2d, x: torch.Tensor, segs: Segs, bn: Optional[nn.Mo
     return _ConvRows.apply(x, w, scale, shift, residual, segs, m.stride[0], _pad_of(m), m.dilation[0], ACT_NONE, amp_prec(), False)
 
 
-def _mbconv_check(blk: nn.Module, x: torch.Tensor, segs: Segs) -> None:
+def _mbconv_check(blk: nn.Module, x: torch.Tensor, segs: Segs, batch_stats: bool = False) -> None:
     bns = [blk._bn1, blk._bn2] + ([blk._bn0] if blk.expand != 1 else [])
-    if not all(bn_is_frozen(b) for b in bns):
+    if batch_stats:
+        if not all(_bn_train_wide_ok(b, x) for b in bns):
+            raise FdError("MBConv: batch_stats=True needs every BatchNorm of the block in training mode with affine parameters and running statistics "
+                          "(C % 4 == 0, C <= 4096)")
+    elif not all(bn_is_frozen(b) for b in bns):
         raise FdError("MBConv: the HIP training nodes fold FROZEN BatchNorm layers only (batch statistics in the MBConv trunk are out of scope: "
                       "build the model with freeze_bn=True and keep the backbone's BatchNorm layers in eval mode)")
     convs = [blk._project_conv] + ([blk._expand_conv] if blk.expand != 1 else [])
@@ -788,17 +792,27 @@ def _mbconv_check(blk: nn.Module, x: torch.Tensor, segs: Segs) -> None:
         raise FdError("MBConv: squeeze-excitation with biases, at most 4096 channels and 1024 squeezed channels expected")
 
 
-def mbconv_rows(blk: nn.Module, x: torch.Tensor, segs: Segs):
+def mbconv_rows(blk: nn.Module, x: torch.Tensor, segs: Segs, batch_stats: bool = False, drop_scale: Optional[torch.Tensor] = None):
     """One MBConvBlock (efficientnet_pytorch 0.7.1, parameters in model/backbone/efficientnetv1._MBConv) on single-level rows held at widths rounded up to 32
     with zero pad channels, every op a differentiable HIP node: [expand 1x1 + bn0 -> swish] -> depthwise k x k + bn1 -> swish -> squeeze-excitation ->
-    project 1x1 + bn2 (+ the block input when blk.skip).  Returns (rows of width round32(blk.cout), their Segs).  Frozen BatchNorm only; no drop-connect.
-    What is not covered raises FdError: there is no stock fallback."""
-    _mbconv_check(blk, x, segs)
+    project 1x1 + bn2 (+ the block input when blk.skip).  Returns (rows of width round32(blk.cout), their Segs).  Frozen BatchNorm layers fold into the conv
+    launches; with batch_stats=True (opt-in) the three BatchNorms run on batch statistics (batchnorm_train_wide_rows, the swish fused into it).
+    drop_scale: the block's drop-connect scales [N] (drop_connect_scale; skip blocks only): the project conv + bn2 run without the fused residual and
+    _SampleScaleAddRows computes branch * scale[n] + input.  What is not covered raises FdError: there is no stock fallback."""
+    _mbconv_check(blk, x, segs, batch_stats)
+    if drop_scale is not None and not blk.skip:
+        raise FdError("MBConv: drop-connect applies to blocks with a skip connection only")
     N, (H, W) = segs.batch, segs.level_hw()[0]
     t = x
     if blk.expand != 1:
-        t = act_rows(conv_rows_wide(blk._expand_conv, x, segs, blk._bn0), ACT_SILU)
-    t = act_rows(dw_kxk_rows(blk._depthwise_conv, t, segs, blk.pad, blk._bn1), ACT_SILU)
+        if batch_stats:
+            t = batchnorm_train_wide_rows(blk._bn0, conv_rows_wide(blk._expand_conv, x, segs), ACT_SILU)
+        else:
+            t = act_rows(conv_rows_wide(blk._expand_conv, x, segs, blk._bn0), ACT_SILU)
+    if batch_stats:
+        t = batchnorm_train_wide_rows(blk._bn1, dw_kxk_rows(blk._depthwise_conv, t, segs, blk.pad), ACT_SILU)
+    else:
+        t = act_rows(dw_kxk_rows(blk._depthwise_conv, t, segs, blk.pad, blk._bn1), ACT_SILU)
     K, s = blk.kernel, blk.stride
     Ho, Wo = (H + blk.pad[0] + blk.pad[1] - K) // s + 1, (W + blk.pad[0] + blk.pad[1] - K) // s + 1
     so = Segs.make(N, [(Ho, Wo)])
@@ -807,7 +821,17 @@ def mbconv_rows(blk: nn.Module, x: torch.Tensor, segs: Segs):
     if padn:
         w1, w2, b2 = F.pad(w1, (0, 0, 0, 0, 0, padn)), F.pad(w2, (0, 0, 0, 0, 0, 0, 0, padn)), F.pad(b2, (0, padn))
     t = _SERows.apply(t, w1, blk._se_reduce.bias, w2, b2, N, Ho * Wo)
-    return conv_rows_wide(blk._project_conv, t, so, blk._bn2, residual=x if blk.skip else None), so
+    if not batch_stats and drop_scale is None:
+        return conv_rows_wide(blk._project_conv, t, so, blk._bn2, residual=x if blk.skip else None), so
+    if batch_stats:
+        t = batchnorm_train_wide_rows(blk._bn2, conv_rows_wide(blk._project_conv, t, so), ACT_NONE)
+    else:
+        t = conv_rows_wide(blk._project_conv, t, so, blk._bn2)
+    if blk.skip:
+        if drop_scale is None:
+            drop_scale = torch.ones(N, dtype=torch.float32, device=t.device)
+        t = _SampleScaleAddRows.apply(t, drop_scale, x, N, Ho * Wo)
+    return t, so
 
 
 # ------------------------------------------------------------------- modulated deformable conv (DeformableConv2d)
@@ -1263,6 +1287,142 @@ def _is_sync(bn: nn.Module) -> bool:
     return False
 
 
+class _BatchNormWideRows(torch.autograd.Function):
+    """nn.BatchNorm2d in TRAINING mode + ReLU / SiLU at ANY width C % 4 == 0 up to 4096 (fd_batchnorm_train_fwd_nhwc / _bwd_nhwc), on the real-width view of a
+    map that may be held wider (the MBConv trunk: round32(C) with zero pad channels): x [rows, Cw >= C], gamma / beta [C].  The output and the input gradient
+    have x's width and exactly-zero pad channels.  fp32 under autocast, like the other normalisation nodes."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, gamma, beta, rmean, rvar, momentum, eps, act):
+        x = x.contiguous()
+        rows, Cw = x.shape
+        Cc = gamma.numel()
+        y = (torch.zeros if Cw != Cc else torch.empty)(rows, Cw, dtype=torch.float32, device=x.device)
+        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
+        ws = ops.batchnorm_train_fwd(Rows(x, 0, Cc), gm, bt, Rows(y, 0, Cc), eps, act, momentum, rmean, rvar)
+        ctx.save_for_backward(x, gm, bt, ws)
+        ctx.geom = (eps, act)
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        x, gm, bt, ws = ctx.saved_tensors
+        eps, act = ctx.geom
+        Cc = gm.numel()
+        g = resolve_pending(gy).contiguous()
+        gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
+        dgamma, dbeta = ops.batchnorm_train_bwd(Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, Rows(gx, 0, Cc), eps, act, ws)
+        return gx, dgamma, dbeta, None, None, None, None, None
+
+
+def _bn_train_wide_ok(bn: nn.Module, x: torch.Tensor) -> bool:
+    """A BatchNorm in training mode that batchnorm_train_wide_rows takes: any width C % 4 == 0 up to 4096 (x may be held wider)."""
+    Cc = getattr(bn, "num_features", 0)
+    return (not _STOCK and isinstance(bn, BN_TYPES) and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and Cc % 4 == 0 and 4 <= Cc <= 4096 and _f32(x))
+
+
+def batchnorm_train_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) -> torch.Tensor:
+    """act(bn(x)) with batch statistics on rows at any width C % 4 == 0 up to 4096 (check with _bn_train_wide_ok); x is [rows, C] or a map held at
+    round32(C) with zero pad channels, which the output keeps.  Running statistics and num_batches_tracked move like nn.BatchNorm2d's.  These kernels have no
+    synchronised form: an nn.SyncBatchNorm spanning more than one rank raises."""
+    Cc = bn.num_features
+    if _is_sync(bn):
+        raise FdError(f"SyncBatchNorm({Cc}) over more than one rank: the batch-statistics kernels for widths outside C / 4 dividing 256, C <= 1024 "
+                      "(fd_batchnorm_train_*) have no synchronised form; keep this layer an nn.BatchNorm2d or freeze it")
+    if x.dim() != 2 or x.shape[1] < Cc or x.shape[1] % 4 or x.shape[0] < 2:
+        raise FdError(f"batch-statistics BatchNorm({Cc}) on rows of shape {tuple(x.shape)}: at least 2 rows of at least {Cc} channels (a multiple of 4) expected")
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return _BatchNormWideRows.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act)
+
+
+class _SampleScaleAddRows(torch.autograd.Function):
+    """y = a * s[n] + r on single-level rows [N * HW, C] (fd_sample_scale_add_nhwc): the drop-connect of an MBConv skip block -- a = the branch, r = the block
+    input, s = N fp32 on the device (0 or 1 / (1 - p)).  Backward: the branch's gradient is the same launch on the incoming gradient without r, the skip
+    path's is the incoming gradient itself."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, a, s, r, N, HW):
+        a, r, s = a.contiguous(), r.contiguous(), s.detach().float().contiguous()
+        y = torch.empty_like(a)
+        ops.sample_scale_add(_r(a), s, _r(r), _r(y), N, HW)
+        ctx.save_for_backward(s)
+        ctx.geom = (N, HW)
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        s, = ctx.saved_tensors
+        N, HW = ctx.geom
+        g = resolve_pending(gy).contiguous()
+        ga = None
+        if ctx.needs_input_grad[0]:
+            ga = torch.empty_like(g)
+            ops.sample_scale_add(_r(g), s, None, _r(ga), N, HW)
+        return ga, None, (g if ctx.needs_input_grad[2] else None), None, None
+
+
+def drop_connect_scale(p: float, u: torch.Tensor) -> torch.Tensor:
+    """efficientnet_pytorch's drop_connect mask from uniform numbers u [B] on the device: floor((1 - p) + u) / (1 - p), 0 or 1 / (1 - p) per sample."""
+    keep = 1.0 - p
+    return torch.floor(keep + u.detach().float()) / keep
+
+
+class _Stem3Rows(torch.autograd.Function):
+    """_conv_stem (3x3 stride 2, 3 -> C0, static "SAME" padding, no bias) of the EfficientNet trunk on an NCHW fp32 image batch that needs no gradient, as rows
+    [B * h * w, round32(C0)] with zero pad channels: z = conv(x, w) * scale + shift, scale / shift the constants of a frozen _bn0 or None (the raw conv in
+    front of a BatchNorm on batch statistics).  No activation: the swish behind it is an act_rows node that keeps z.  Forward fd_nchw3_to_nhwc4 +
+    fd_stem_conv_nhwc4, backward fd_stem_conv_bwd_weight_nhwc4; there is no data gradient.  fp32 under autocast."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, weight, scale, shift, geom):
+        pad, h, w = geom
+        B, _, H, W = x.shape
+        C0 = weight.shape[0]
+        x4 = torch.empty(B * H * W, 4, dtype=torch.float32, device=x.device)
+        ops.nchw3_to_nhwc4(x.contiguous(), x4)
+        y = (torch.zeros if round32(C0) != C0 else torch.empty)(B * h * w, round32(C0), dtype=torch.float32, device=x.device)
+        ops.stem_conv3(x4, ops.pack_stem3_weight(weight.detach()), Rows(y, 0, C0), B, H, W, 3, 2, pad, pad, h, w, scale, shift, ACT_NONE)
+        ctx.save_for_backward(x4, scale)
+        ctx.geom = (B, H, W, C0, pad, h, w)
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        x4, scale = ctx.saved_tensors
+        B, H, W, C0, pad, h, w = ctx.geom
+        gw = None
+        if ctx.needs_input_grad[1]:
+            g = resolve_pending(gy).contiguous()
+            gw = ops.stem_conv3_wgrad(x4, Rows(g, 0, C0), B, H, W, 3, 2, pad, pad, h, w, scale)
+        return None, gw, None, None, None
+
+
+def effnet_stem_rows(net: nn.Module, x: torch.Tensor, h: int, w: int, batch_stats: bool) -> torch.Tensor:
+    """swish(_bn0(_conv_stem(x))) of a TRAINABLE EfficientNet stem as rows of width round32(C0): _Stem3Rows with a frozen _bn0 folded into the launch, or the
+    raw conv + batchnorm_train_wide_rows when _bn0 runs on batch statistics; the swish is an act_rows node in both cases."""
+    m, bn = net._conv_stem, net._bn0
+    if tuple(m.weight.shape[1:]) != (3, 3, 3) or m.bias is not None or m.weight.dtype != torch.float32 or m.out_channels % 4 or m.out_channels > 64:
+        raise FdError(f"EfficientNet stem {tuple(m.weight.shape)}: the HIP weight-gradient kernel covers [Cout, 3, 3, 3] fp32 without bias, Cout % 4 == 0, Cout <= 64")
+    if batch_stats:
+        if not _bn_train_wide_ok(bn, x):
+            raise FdError("EfficientNet stem: batch_stats=True needs _bn0 in training mode with affine parameters and running statistics")
+        t = batchnorm_train_wide_rows(bn, _Stem3Rows.apply(x, m.weight, None, None, (net.stem_pad[0], h, w)), ACT_NONE)
+    else:
+        if not bn_is_frozen(bn):
+            raise FdError("EfficientNet stem: train_stem=True without batch_stats folds a FROZEN _bn0")
+        sc, sf = _bn_fold(bn)
+        t = _Stem3Rows.apply(x, m.weight, sc, sf, (net.stem_pad[0], h, w))
+    return act_rows(t, ACT_SILU)
+
+
 class NormHandle:
     """What conv_norm_begin returns: either the finished tensor (`y`) or a SyncBatchNorm whose all-reduce is in flight (`sync`)."""
     __slots__ = ("y", "sync")
@@ -1303,8 +1463,13 @@ def conv_norm_act_rows(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, s
         if act in (ACT_NONE, ACT_RELU):
             return conv(m, x, segs, bn, act)
         return act_rows(conv(m, x, segs, bn, ACT_NONE), act)
-    if not _bn_train_ok(bn, x) or (dw and m.bias is not None):
+    if dw and m.bias is not None:
         return None
+    if not _bn_train_ok(bn, x):
+        # widths the GroupNorm-route kernels refuse (C / 4 not dividing 256, C > 1024): the any-width kernels, where the result used to be None
+        if not _bn_train_wide_ok(bn, x) or _is_sync(bn):
+            return None
+        return batchnorm_train_wide_rows(bn, conv(m, x, segs, None, ACT_NONE), act)
     return batchnorm_train_rows(bn, conv(m, x, segs, None, ACT_NONE), act)
 
 

@@ -7,6 +7,11 @@
   step       the whole training step (forward, targets, loss, backward, SGD) of FCOS([384, 136, 48], 20, 256, efficientnet=True,
              backbone_number=3).enable_training(), fp32 and under autocast(float16) + GradScaler
   stock      the same step in a child process started with FD_TRAIN_STOCK_CONV=1 (every layer on stock PyTorch-ROCm ops), for scale
+  full       the launches and steps of enable_training(train_stem=True, batch_stats=True, drop_connect_rate=0.2) on a freeze_bn=False model:
+             fd_batchnorm_train_fwd / _bwd on the 144-channel 256^2 map and on 816 x 32^2 (touch-once bytes: x read + y written; x and dy read + dx
+             written -- the kernels read x, resp. x and dy, TWICE: statistics, then apply), fd_stem_conv_bwd_weight_nhwc4 at Cout 40 (x4 and dy read),
+             fd_sample_scale_add_nhwc on a skip block's 48-channel 64^2 map held at 64 channels (branch and input read, output written); the whole
+             fp32 / AMP step with the three switches on ("step_full_*"), HIP and stock (the stock trunk follows the same switches)
 
 Method: 10 warm-up launches / 3 warm-up steps, then `REPS` timed runs of a fixed batch of launches / steps; the median and the spread (min .. max) of
 the runs are reported, with the clocks rocm-smi shows before and after (read-only query, when the tool is there).
@@ -83,6 +88,43 @@ def time_launches(reps):
     return res
 
 
+def _row(name, launch, C, rows, runs, nbytes):
+    us = statistics.median(runs)
+    return {"layer": name, "launch": launch, "C": C, "rows": rows, "us": round(us, 2), "us_min": round(min(runs), 2), "us_max": round(max(runs), 2),
+            "touch_once_bytes": nbytes, "bound_us_at_hbm_peak": round(nbytes / HBM_PEAK * 1e6, 2),
+            "hbm_peak_fraction": round(nbytes / (us * 1e-6) / HBM_PEAK, 4)}
+
+
+def time_full_launches(reps):
+    """The four launches the three switches add, at B3's real shapes for the 16 x 512 x 512 batch."""
+    res = []
+    for name, C, H in (("blocks.2 _bn0/_bn1 144 x 256^2", 144, 256), ("blocks.14 _bn0/_bn1 816 x 32^2", 816, 32)):
+        rows, Cw = B * H * H, (C + 31) // 32 * 32
+        x, dy = torch.randn(rows, Cw, device=DEV), torch.randn(rows, Cw, device=DEV)
+        y, dx = torch.zeros_like(x), torch.zeros_like(x)
+        gm, bt = torch.rand(C, device=DEV) + 0.5, torch.randn(C, device=DEV)
+        rm, rv = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+        xr, gr, yr, dr = (ops.Rows(t, 0, C) for t in (x, dy, y, dx))
+        ws, ws2 = ops.batchnorm_train_workspace(rows, C, DEV), ops.batchnorm_train_workspace(rows, C, DEV)
+        fwd = lambda: ops.batchnorm_train_fwd(xr, gm, bt, yr, 1e-3, ops.ACT_SILU, 0.01, rm, rv, ws)  # noqa: E731
+        bwd = lambda: ops.batchnorm_train_bwd(xr, gr, gm, bt, dr, 1e-3, ops.ACT_SILU, ws, ws2)  # noqa: E731
+        res.append(_row(name, "batchnorm_train_fwd", C, rows, _time(fwd, reps), 2 * rows * C * 4))
+        res.append(_row(name, "batchnorm_train_bwd", C, rows, _time(bwd, reps), 3 * rows * C * 4))
+    Ho, C0 = S // 2, 40
+    x4 = torch.randn(B * S * S, 4, device=DEV)
+    dy = torch.randn(B * Ho * Ho, 64, device=DEV)
+    sc = torch.rand(C0, device=DEV) + 0.5
+    gr = ops.Rows(dy, 0, C0)
+    runs = _time(lambda: ops.stem_conv3_wgrad(x4, gr, B, S, S, 3, 2, 0, 0, Ho, Ho, sc), reps, n=20)
+    res.append(_row("_conv_stem 3 -> 40, 512^2 -> 256^2", "stem_conv_bwd_weight", C0, B * Ho * Ho, runs, (x4.numel() + B * Ho * Ho * C0) * 4))
+    HW, C = 64 * 64, 64
+    a, r, y = (torch.randn(B * HW, C, device=DEV) for _ in range(3))
+    s = torch.tensor([0.0, 1.25] * (B // 2), device=DEV)
+    runs = _time(lambda: ops.sample_scale_add(ops.Rows(a), s, ops.Rows(r), ops.Rows(y), B, HW), reps)
+    res.append(_row("blocks.6 skip 48 (held at 64) x 64^2", "sample_scale_add", C, B * HW, runs, 3 * B * HW * C * 4))
+    return res
+
+
 def batch():
     g = torch.Generator(device=DEV).manual_seed(7)
     x = torch.randn(B, 3, S, S, device=DEV, generator=g)
@@ -93,11 +135,12 @@ def batch():
     return x, gt, labels
 
 
-def time_step(amp, reps, steps=5):
+def time_step(amp, reps, steps=5, full=False):
     torch.manual_seed(0)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        model = FCOS([384, 136, 48], 20, 256, efficientnet=True, backbone_number=3).enable_training().to(DEV).train()
+        model = FCOS([384, 136, 48], 20, 256, freeze_bn=not full, efficientnet=True, backbone_number=3)
+        model = (model.enable_training(train_stem=True, batch_stats=True, drop_connect_rate=0.2) if full else model.enable_training()).to(DEV).train()
     x, gt, labels = batch()
     gen = FCOSGenTargets([8, 16, 32, 64, 128], [[-1, 32], [32, 96], [96, 192], [192, 384], [384, 9999999]])
     crit = FCOSLoss("giou")
@@ -137,13 +180,17 @@ def main():
     ap.add_argument("--stock", action="store_true", help="(internal, with --steps-only) the child process that runs with FD_TRAIN_STOCK_CONV=1")
     args = ap.parse_args()
     if args.steps_only:
-        print(json.dumps({"fp32": time_step(False, args.reps), "amp": time_step(True, args.reps)}))
+        print(json.dumps({"fp32": time_step(False, args.reps), "amp": time_step(True, args.reps),
+                          "full_fp32": time_step(False, args.reps, full=True), "full_amp": time_step(True, args.reps, full=True)}))
         return
     res = {"tool": "time_effnet_train", "device": torch.cuda.get_device_name(0), "model": "FCOS EfficientNet-B3", "batch": B, "input": S, "reps": args.reps,
            "clocks_before": clocks()}
     res["launches"] = time_launches(args.reps)
     res["step_hip_fp32"] = time_step(False, args.reps)
     res["step_hip_amp"] = time_step(True, args.reps)
+    res["launches_full"] = time_full_launches(args.reps)
+    res["step_full_hip_fp32"] = time_step(False, args.reps, full=True)
+    res["step_full_hip_amp"] = time_step(True, args.reps, full=True)
     if not args.no_stock:
         torch.cuda.empty_cache()
         out = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps-only", "--stock", "--reps", str(args.reps)], capture_output=True, text=True)
@@ -151,6 +198,7 @@ def main():
             raise SystemExit(f"the FD_TRAIN_STOCK_CONV=1 child failed ({out.returncode}):\n{out.stderr[-2000:]}")
         stock = json.loads(out.stdout.strip().splitlines()[-1])
         res["step_stock_fp32"], res["step_stock_amp"] = stock["fp32"], stock["amp"]
+        res["step_full_stock_fp32"], res["step_full_stock_amp"] = stock["full_fp32"], stock["full_amp"]
     res["clocks_after"] = clocks()
     print(json.dumps(res))
 
