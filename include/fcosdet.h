@@ -768,6 +768,32 @@ int32_t fd_batchnorm_train_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, 
                                     int32_t C, float eps, int32_t act, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
                                     fd_stream_t stream);
 
+/* The same kernels for nn.SyncBatchNorm (statistics over ALL ranks' rows), each direction cut in two around ONE all-reduce that the CALLER issues, with the
+ * argument conventions of fd_batchnorm_sync_*: phase in {1, 2}; sums = double[2C + 1], the global row count riding in sums[2C]; total_rows = the global row
+ * count as a host value (>= this rank's rows, >= 2), or -1: read from sums[2C] on the device (ranks with different row counts need no host round trip).
+ *   forward   phase 1: sums[c], sums[C + c] = this rank's sum x, sum x^2 of channel c; NOTHING else is written (not sums[2C], not the workspace's first
+ *                      [2][C] block, not the running statistics, not y); gamma, beta, y may be NULL                         -> all-reduce(sums, count in sums[2C])
+ *             phase 2: mean / rstd from the global sums and count into the workspace's first [2][C] block (the backward reads them there), the running
+ *                      statistics updated with the global count, y = act((x - mean) * rstd * gamma + beta) on this rank's rows
+ *   backward  phase 1: sums[c], sums[C + c] = this rank's sum dz, sum dz * xhat (global mean / rstd from fwd_workspace); dgamma / dbeta from THESE local sums
+ *                      (DistributedDataParallel averages them, as with torch's SyncBatchNorm); dx may be NULL                        -> all-reduce(sums[0 .. 2C))
+ *             phase 2: c1, c2 from the global sums and count into the workspace's first [2][C] block, then dx; dgamma, dbeta may be NULL
+ * Both phases of a direction take the SAME workspace (fd_batchnorm_train_sync_workspace_bytes: the layout of fd_batchnorm_train_workspace_bytes, for
+ * rows >= 1 -- a rank may hold one row, only the global count must reach 2).  At most two launches per phase, no atomics, no host synchronisation, no
+ * allocation.  ONE rank (rows >= 2, sums handed from phase 1 to phase 2 untouched, total_rows = rows in either form) gives bit for bit what
+ * fd_batchnorm_train_fwd_nhwc / _bwd_nhwc give: y, the statistics block, the running statistics, dx, dgamma, dbeta, the coefficient block.
+ * FD_E_UNSUPPORTED: C % 4 != 0, C < 4, C > 4096, rows < 1, an activation outside {NONE, RELU, SILU}, phase outside {1, 2}.  FD_E_INVAL: 0 < total_rows < rows
+ * (or < 2), bad pointers / views / alignment, a short workspace, running_mean without running_var.  Both before any launch. */
+int64_t fd_batchnorm_train_sync_workspace_bytes(int64_t rows, int32_t C);
+int32_t fd_batchnorm_train_sync_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
+                                         int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums, double total_rows,
+                                         float momentum, float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes,
+                                         fd_stream_t stream);
+int32_t fd_batchnorm_train_sync_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
+                                         const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows, int32_t C,
+                                         float eps, int32_t act, int32_t phase, double* sums, double total_rows, const void* fwd_workspace, void* workspace,
+                                         int64_t workspace_bytes, fd_stream_t stream);
+
 /* Drop-connect (stochastic depth) on [N][HW][C] fp32 channel views: y = a * s[n] + r, s = N floats on the device, r may be NULL; y may alias a.
  * Two roundings, like the torch expression a * s + r. */
 int32_t fd_sample_scale_add_nhwc(const float* a, int32_t a_cs, int32_t a_co, const float* s, const float* r, int32_t r_cs, int32_t r_co, float* y,

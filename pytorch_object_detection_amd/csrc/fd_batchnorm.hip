@@ -12,6 +12,7 @@
 //              per-channel constants c1 = rstd * gamma * mean(dz), c2 = rstd * gamma * mean(dz * xhat)) -> apply dx = rstd * gamma * dz - c1 - xhat * c2
 // workspace (both directions, fd_batchnorm_train_workspace_bytes): double [2][C] then double [nchunk][2][C].  The forward leaves mean[C], rstd[C] in the first
 // block (rstd rounded to fp32 first: the value the apply kernels multiply by); the backward leaves c1[C], c2[C] there.
+// The same kernels serve nn.SyncBatchNorm (fd_batchnorm_train_sync_*, below): each direction in two phases around an all-reduce the caller issues.
 #include "fd_common.h"
 
 #define BN_MAXCHUNK 1024
@@ -114,11 +115,10 @@ __device__ __forceinline__ bool bn_chunk_sums(const double* __restrict__ part, i
     return true;
 }
 
-__global__ __launch_bounds__(256) void bn_fwd_final_kernel(const double* __restrict__ part, int nchunk, int C, double count, float eps, float momentum,
-                                                            double* __restrict__ stat, float* __restrict__ rmean, float* __restrict__ rvar) {
-    __shared__ double s_a[256], s_b[256];
-    int c; double A, B;
-    if (!bn_chunk_sums(part, nchunk, C, s_a, s_b, c, A, B)) return;
+// channel c's statistics from its two sums over `count` rows (one rank's, or all ranks' behind an all-reduce): shared by the unsynchronised final kernel and
+// the synchronised one, so that one rank gives the same bits through either
+__device__ __forceinline__ void bn_fwd_stats(int c, int C, double A, double B, double count, float eps, float momentum, double* __restrict__ stat,
+                                             float* __restrict__ rmean, float* __restrict__ rvar) {
     const double mean = A / count;
     double var = B / count - mean * mean;               // the biased batch variance
     if (var < 0) var = 0;
@@ -131,6 +131,22 @@ __global__ __launch_bounds__(256) void bn_fwd_final_kernel(const double* __restr
     }
 }
 
+// the two per-channel constants of the backward apply from (sum dz, sum dz * xhat) over `count` rows
+__device__ __forceinline__ void bn_bwd_coef(int c, int C, double A, double B, double count, const float* __restrict__ gamma, const double* __restrict__ stat,
+                                            double* __restrict__ coef) {
+    const double k = stat[C + c] * (double)gamma[c] / count;
+    coef[c] = k * A;
+    coef[C + c] = k * B;
+}
+
+__global__ __launch_bounds__(256) void bn_fwd_final_kernel(const double* __restrict__ part, int nchunk, int C, double count, float eps, float momentum,
+                                                            double* __restrict__ stat, float* __restrict__ rmean, float* __restrict__ rvar) {
+    __shared__ double s_a[256], s_b[256];
+    int c; double A, B;
+    if (!bn_chunk_sums(part, nchunk, C, s_a, s_b, c, A, B)) return;
+    bn_fwd_stats(c, C, A, B, count, eps, momentum, stat, rmean, rvar);
+}
+
 __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const double* __restrict__ part, int nchunk, int C, double count, const float* __restrict__ gamma,
                                                             const double* __restrict__ stat, double* __restrict__ coef, float* __restrict__ dgamma,
                                                             float* __restrict__ dbeta) {
@@ -139,9 +155,7 @@ __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const double* __restr
     if (!bn_chunk_sums(part, nchunk, C, s_a, s_b, c, A, B)) return;
     dbeta[c] = (float)A;
     dgamma[c] = (float)B;
-    const double k = stat[C + c] * (double)gamma[c] / count;
-    coef[c] = k * A;
-    coef[C + c] = k * B;
+    bn_bwd_coef(c, C, A, B, count, gamma, stat, coef);
 }
 
 // forward: y = act(xhat * gamma + beta); backward: dx = rstd * gamma * dz - c1 - xhat * c2.  Same (tile, chunk) ownership as the partial kernel.
@@ -248,6 +262,136 @@ extern "C" int32_t fd_batchnorm_train_bwd_nhwc(const float* x, int32_t x_cs, int
     FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (sums)");
     hipLaunchKernelGGL((bn_apply_kernel<true>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, stat, (const double*)coef);
     FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (apply)");
+    return FD_OK;
+}
+
+// ---- The synchronised form (nn.SyncBatchNorm at these widths): each direction cut in two around ONE all-reduce that the CALLER issues.
+//   forward   phase 1: partial -> sums[c], sums[C + c] = this rank's sum x, sum x^2                         -> all-reduce(sums[0 .. 2C], the row count in sums[2C])
+//             phase 2: (mean, rstd, running statistics) from the global sums and the global count -> apply on this rank's rows
+//   backward  phase 1: partial (global mean / rstd from the forward's workspace) -> sums[c], sums[C + c] = this rank's sum dz, sum dz * xhat, and
+//                      dgamma / dbeta from THESE local sums (DDP averages them, as with torch's SyncBatchNorm)  -> all-reduce(sums[0 .. 2C))
+//             phase 2: (c1, c2) from the global sums and the global count -> apply
+// The partial and apply kernels are the ones above; the chunk reduction is bn_chunk_sums and the per-channel finals are bn_fwd_stats / bn_bwd_coef, so one rank
+// whose sums pass from phase 1 to phase 2 untouched gives the unsynchronised launch's bits.  count <= 0: the global count is read from sums[2C] on the device.
+__global__ __launch_bounds__(256) void bn_wide_sync_sums_kernel(const double* __restrict__ part, int nchunk, int C, double* __restrict__ sums,
+                                                            float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    __shared__ double s_a[256], s_b[256];
+    int c; double A, B;
+    if (!bn_chunk_sums(part, nchunk, C, s_a, s_b, c, A, B)) return;
+    sums[c] = A;
+    sums[C + c] = B;
+    if (dgamma) { dbeta[c] = (float)A; dgamma[c] = (float)B; }
+}
+
+__global__ __launch_bounds__(256) void bn_wide_sync_fwd_final_kernel(const double* __restrict__ sums, int C, double count, float eps, float momentum,
+                                                                 double* __restrict__ stat, float* __restrict__ rmean, float* __restrict__ rvar) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    if (count <= 0.0) count = sums[2 * C];
+    bn_fwd_stats(c, C, sums[c], sums[C + c], count, eps, momentum, stat, rmean, rvar);
+}
+
+__global__ __launch_bounds__(256) void bn_wide_sync_bwd_coef_kernel(const double* __restrict__ sums, int C, double count, const float* __restrict__ gamma,
+                                                                const double* __restrict__ stat, double* __restrict__ coef) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    if (count <= 0.0) count = sums[2 * C];
+    bn_bwd_coef(c, C, sums[c], sums[C + c], count, gamma, stat, coef);
+}
+
+// a rank may hold ONE row: only the global count must reach 2
+static bool bn_sync_shape_ok(int64_t rows, int32_t C) { return C >= 4 && C <= BN_MAXC && C % 4 == 0 && rows >= 1 && rows < (1LL << 31); }
+// the global count: a host value >= this rank's rows (and >= 2), or <= 0 = "read sums[2C] on the device"
+static bool bn_sync_count_ok(double total_rows, int64_t rows) { return total_rows <= 0.0 || (total_rows >= (double)rows && total_rows >= 2.0); }
+
+extern "C" int64_t fd_batchnorm_train_sync_workspace_bytes(int64_t rows, int32_t C) {
+    if (!bn_sync_shape_ok(rows, C)) return -1;
+    const BnPart p = bn_partition(rows, C);
+    return ((int64_t)2 * C + (int64_t)p.nchunk * 2 * C) * (int64_t)sizeof(double);
+}
+
+extern "C" int32_t fd_batchnorm_train_sync_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
+                                                    int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums,
+                                                    double total_rows, float momentum, float* running_mean, float* running_var, void* workspace,
+                                                    int64_t workspace_bytes, fd_stream_t stream) {
+    FD_REQUIRE(bn_sync_shape_ok(rows, C), FD_E_UNSUPPORTED,
+               "fd_batchnorm_train_sync_fwd: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 1 <= rows < 2^31)", (long long)rows, C, BN_MAXC);
+    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || act == FD_ACT_SILU, FD_E_UNSUPPORTED, "fd_batchnorm_train_sync_fwd: activation %d unsupported", act);
+    FD_REQUIRE(phase == 1 || phase == 2, FD_E_UNSUPPORTED, "fd_batchnorm_train_sync_fwd: phase %d (1: this rank's sums, 2: statistics + apply)", phase);
+    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && sums && ((uintptr_t)sums & 7) == 0, FD_E_INVAL,
+               "fd_batchnorm_train_sync_fwd: bad pointer / channel view (C=%d; sums: [2C + 1] doubles)", C);
+    FD_REQUIRE(phase == 1 || (bn_view_ok(y, y_cs, y_co, C) && gamma && beta), FD_E_INVAL, "fd_batchnorm_train_sync_fwd: phase 2 needs y, gamma and beta (C=%d)", C);
+    FD_REQUIRE(bn_sync_count_ok(total_rows, rows), FD_E_INVAL,
+               "fd_batchnorm_train_sync_fwd: total_rows=%g: the global row count (>= this rank's %lld rows, >= 2), or -1: read from sums[2C] on the device",
+               total_rows, (long long)rows);
+    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "fd_batchnorm_train_sync_fwd: running_mean and running_var go together");
+    FD_REQUIRE(eps >= 0.f, FD_E_INVAL, "fd_batchnorm_train_sync_fwd: eps must not be negative");
+    const int64_t need = fd_batchnorm_train_sync_workspace_bytes(rows, C);
+    FD_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
+               "fd_batchnorm_train_sync_fwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes, (long long)need);
+    const BnPart p = bn_partition(rows, C);
+    BnArgs a;
+    a.x = x; a.dy = nullptr; a.gamma = gamma; a.beta = beta; a.out = y;
+    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = 0; a.dy_co = 0; a.out_cs = y_cs; a.out_co = y_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
+    a.rows = (long)rows; a.rows_per = p.rows_per;
+    double* stat = (double*)workspace;
+    double* part = stat + 2 * (long)C;
+    hipStream_t st = (hipStream_t)stream;
+    if (phase == 1) {
+        hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, part);
+        FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (partial)");
+        hipLaunchKernelGGL(bn_wide_sync_sums_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)part, p.nchunk, C, sums, (float*)nullptr, (float*)nullptr);
+        FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (sums)");
+        return FD_OK;
+    }
+    hipLaunchKernelGGL(bn_wide_sync_fwd_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const double*)sums, C, total_rows, eps, momentum, stat, running_mean,
+                       running_var);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (statistics)");
+    hipLaunchKernelGGL((bn_apply_kernel<false>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, (const double*)nullptr);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (apply)");
+    return FD_OK;
+}
+
+extern "C" int32_t fd_batchnorm_train_sync_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co,
+                                                    const float* gamma, const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta,
+                                                    int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums, double total_rows,
+                                                    const void* fwd_workspace, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    (void)eps;                                          // (rstd comes from the forward's workspace)
+    FD_REQUIRE(bn_sync_shape_ok(rows, C), FD_E_UNSUPPORTED,
+               "fd_batchnorm_train_sync_bwd: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 1 <= rows < 2^31)", (long long)rows, C, BN_MAXC);
+    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || act == FD_ACT_SILU, FD_E_UNSUPPORTED, "fd_batchnorm_train_sync_bwd: activation %d has no backward", act);
+    FD_REQUIRE(phase == 1 || phase == 2, FD_E_UNSUPPORTED, "fd_batchnorm_train_sync_bwd: phase %d (1: this rank's sums, dgamma, dbeta; 2: dx)", phase);
+    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && bn_view_ok(dy, dy_cs, dy_co, C) && gamma && beta && sums && ((uintptr_t)sums & 7) == 0, FD_E_INVAL,
+               "fd_batchnorm_train_sync_bwd: bad pointer / channel view (C=%d; sums: [2C + 1] doubles)", C);
+    FD_REQUIRE(phase == 1 ? (dgamma && dbeta) : bn_view_ok(dx, dx_cs, dx_co, C), FD_E_INVAL,
+               "fd_batchnorm_train_sync_bwd: phase 1 needs dgamma and dbeta, phase 2 needs dx (C=%d)", C);
+    FD_REQUIRE(bn_sync_count_ok(total_rows, rows), FD_E_INVAL,
+               "fd_batchnorm_train_sync_bwd: total_rows=%g: the global row count (>= this rank's %lld rows, >= 2), or -1: read from sums[2C] on the device",
+               total_rows, (long long)rows);
+    const int64_t need = fd_batchnorm_train_sync_workspace_bytes(rows, C);
+    FD_REQUIRE(fwd_workspace && ((uintptr_t)fwd_workspace & 7) == 0 && workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
+               "fd_batchnorm_train_sync_bwd: the forward's workspace and a workspace of %lld bytes needed (got %lld; 8-byte aligned)", (long long)need,
+               (long long)workspace_bytes);
+    const BnPart p = bn_partition(rows, C);
+    BnArgs a;
+    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.out = dx;
+    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = dy_cs; a.dy_co = dy_co; a.out_cs = dx_cs; a.out_co = dx_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
+    a.rows = (long)rows; a.rows_per = p.rows_per;
+    const double* stat = (const double*)fwd_workspace;
+    double* coef = (double*)workspace;
+    double* part = coef + 2 * (long)C;
+    hipStream_t st = (hipStream_t)stream;
+    if (phase == 1) {
+        hipLaunchKernelGGL((bn_partial_kernel<true>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, stat, part);
+        FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (partial)");
+        hipLaunchKernelGGL(bn_wide_sync_sums_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)part, p.nchunk, C, sums, dgamma, dbeta);
+        FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (sums)");
+        return FD_OK;
+    }
+    hipLaunchKernelGGL(bn_wide_sync_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const double*)sums, C, total_rows, gamma, stat, coef);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (coefficients)");
+    hipLaunchKernelGGL((bn_apply_kernel<true>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, stat, (const double*)coef);
+    FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (apply)");
     return FD_OK;
 }
 

@@ -79,9 +79,10 @@ class PlannedModule(nn.Module):
         return tuple([torch.cat([p[g][lv] for p in parts], 0) for lv in range(5)] for g in range(3))
 
     def freeze_batchnorm(self) -> None:
-        """Every BatchNorm2d below this module in eval mode with its affine parameters frozen (the detectors' constructors)."""
+        """Every BatchNorm2d (or, behind SyncBatchNorm.convert_sync_batchnorm, SyncBatchNorm) below this module in eval mode with its affine parameters frozen
+        (the detectors' constructors)."""
         for m in self.modules():
-            if isinstance(m, nn.BatchNorm2d):
+            if isinstance(m, (nn.BatchNorm2d, nn.SyncBatchNorm)):
                 m.eval()
                 for p in m.parameters():
                     p.requires_grad = False

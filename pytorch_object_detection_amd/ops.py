@@ -1682,6 +1682,62 @@ def batchnorm_train_bwd(x: Rows, dy: Rows, gamma: torch.Tensor, beta: torch.Tens
     return dgamma, dbeta
 
 
+def batchnorm_train_sync_workspace(rows: int, Cc: int, device) -> torch.Tensor:
+    """A workspace of batchnorm_train_sync_fwd / _bwd (fd_batchnorm_train_sync_workspace_bytes: batchnorm_train_workspace's layout, from ONE row up)."""
+    nb = _lib.lib().fd_batchnorm_train_sync_workspace_bytes(rows, Cc)
+    if nb < 0:
+        raise FdError(f"synchronised batch-statistics BatchNorm over {rows} rows of {Cc} channels: the HIP kernels cover C % 4 == 0, 4 <= C <= 4096, "
+                      "1 <= rows < 2^31", rc=_lib.E_UNSUPPORTED)
+    return torch.empty(nb // 8, dtype=torch.float64, device=device)
+
+
+def batchnorm_train_sync_fwd(phase: int, x: Rows, sums: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                             y: Optional[Rows] = None, eps: float = 1e-5, act_id: int = ACT_NONE, total_rows: float = -1.0, momentum: Optional[float] = None,
+                             running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
+                             ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One phase of SyncBatchNorm's forward at any width (fd_batchnorm_train_sync_fwd_nhwc).  Phase 1 writes this rank's sum x, sum x^2 to sums[:2C] (`sums`:
+    [2C + 1] float64; the caller puts its row count in sums[2C] and all-reduces); phase 2 normalises x into y with the global statistics, `total_rows` the
+    global count or -1 = sums[2C] on the device, and updates the running tensors when `momentum` and both are given.  Returns the workspace: hand phase 1's
+    to phase 2, and phase 2's to batchnorm_train_sync_bwd."""
+    _need_gpu(x.buf, sums, gamma, beta, y.buf if y is not None else None, running_mean, running_var, ws)
+    if x.f16 or (y is not None and (y.f16 or y.C != x.C or y.rows != x.rows)) or any(t is not None and t.numel() != x.C for t in (gamma, beta)):
+        raise FdError("batchnorm_train_sync_fwd: fp32 views of the same shape and C-element gamma / beta expected")
+    if sums.dtype != torch.float64 or sums.numel() != 2 * x.C + 1 or not sums.is_contiguous():
+        raise FdError(f"batchnorm_train_sync_fwd: sums must be {2 * x.C + 1} contiguous float64 elements")
+    if ws is None:
+        ws = batchnorm_train_sync_workspace(x.rows, x.C, x.buf.device)
+    upd = momentum is not None and running_mean is not None and running_var is not None
+    check(_lib.lib().fd_batchnorm_train_sync_fwd_nhwc(x.ptr, x.cs, x.co, gamma.data_ptr() if gamma is not None else None,
+                                                      beta.data_ptr() if beta is not None else None, y.ptr if y is not None else None,
+                                                      y.cs if y is not None else 0, y.co if y is not None else 0, x.rows, x.C, float(eps), act_id, phase,
+                                                      sums.data_ptr(), float(total_rows), float(momentum) if upd else 0.0,
+                                                      running_mean.data_ptr() if upd else None, running_var.data_ptr() if upd else None, ws.data_ptr(),
+                                                      ws.numel() * ws.element_size(), _stream()), f"fd_batchnorm_train_sync_fwd_nhwc (phase {phase})")
+    return ws
+
+
+def batchnorm_train_sync_bwd(phase: int, x: Rows, dy: Rows, gamma: torch.Tensor, beta: torch.Tensor, sums: torch.Tensor, fwd_ws: torch.Tensor,
+                             dx: Optional[Rows] = None, dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None, eps: float = 1e-5,
+                             act_id: int = ACT_NONE, total_rows: float = -1.0, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One phase of SyncBatchNorm's backward at any width (fd_batchnorm_train_sync_bwd_nhwc).  Phase 1 writes this rank's sum dz, sum dz * xhat to sums[:2C]
+    and dgamma / dbeta (from those local sums); the caller all-reduces sums[:2C]; phase 2 writes dx, `total_rows` as in the forward.  fwd_ws: the forward's
+    phase-2 workspace.  Returns the workspace: hand phase 1's to phase 2."""
+    _need_gpu(x.buf, dy.buf, dx.buf if dx is not None else None, gamma, beta, sums, fwd_ws, dgamma, dbeta, ws)
+    if x.f16 or dy.f16 or x.C != dy.C or x.rows != dy.rows or (dx is not None and (dx.f16 or dx.C != x.C or dx.rows != x.rows)):
+        raise FdError("batchnorm_train_sync_bwd: fp32 views of the same shape expected")
+    if sums.dtype != torch.float64 or sums.numel() != 2 * x.C + 1 or not sums.is_contiguous():
+        raise FdError(f"batchnorm_train_sync_bwd: sums must be {2 * x.C + 1} contiguous float64 elements")
+    if ws is None:
+        ws = batchnorm_train_sync_workspace(x.rows, x.C, x.buf.device)
+    check(_lib.lib().fd_batchnorm_train_sync_bwd_nhwc(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gamma.data_ptr(), beta.data_ptr(),
+                                                      dx.ptr if dx is not None else None, dx.cs if dx is not None else 0, dx.co if dx is not None else 0,
+                                                      dgamma.data_ptr() if dgamma is not None else None, dbeta.data_ptr() if dbeta is not None else None,
+                                                      x.rows, x.C, float(eps), act_id, phase, sums.data_ptr(), float(total_rows), fwd_ws.data_ptr(),
+                                                      ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+          f"fd_batchnorm_train_sync_bwd_nhwc (phase {phase})")
+    return ws
+
+
 def sample_scale_add(a: Rows, s: torch.Tensor, r: Optional[Rows], y: Rows, N: int, HW: int) -> None:
     """y = a * s[n] + r on [N * HW, C] fp32 channel views (fd_sample_scale_add_nhwc: drop-connect); s = N fp32 on the device, r may be None, y may alias a."""
     _need_gpu(a.buf, s, r.buf if r is not None else None, y.buf)

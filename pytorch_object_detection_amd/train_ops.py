@@ -806,11 +806,11 @@ def mbconv_rows(blk: nn.Module, x: torch.Tensor, segs: Segs, batch_stats: bool =
     t = x
     if blk.expand != 1:
         if batch_stats:
-            t = batchnorm_train_wide_rows(blk._bn0, conv_rows_wide(blk._expand_conv, x, segs), ACT_SILU)
+            t = _bn_wide_rows(blk._bn0, conv_rows_wide(blk._expand_conv, x, segs), ACT_SILU)
         else:
             t = act_rows(conv_rows_wide(blk._expand_conv, x, segs, blk._bn0), ACT_SILU)
     if batch_stats:
-        t = batchnorm_train_wide_rows(blk._bn1, dw_kxk_rows(blk._depthwise_conv, t, segs, blk.pad), ACT_SILU)
+        t = _bn_wide_rows(blk._bn1, dw_kxk_rows(blk._depthwise_conv, t, segs, blk.pad), ACT_SILU)
     else:
         t = act_rows(dw_kxk_rows(blk._depthwise_conv, t, segs, blk.pad, blk._bn1), ACT_SILU)
     K, s = blk.kernel, blk.stride
@@ -824,7 +824,7 @@ def mbconv_rows(blk: nn.Module, x: torch.Tensor, segs: Segs, batch_stats: bool =
     if not batch_stats and drop_scale is None:
         return conv_rows_wide(blk._project_conv, t, so, blk._bn2, residual=x if blk.skip else None), so
     if batch_stats:
-        t = batchnorm_train_wide_rows(blk._bn2, conv_rows_wide(blk._project_conv, t, so), ACT_NONE)
+        t = _bn_wide_rows(blk._bn2, conv_rows_wide(blk._project_conv, t, so), ACT_NONE)
     else:
         t = conv_rows_wide(blk._project_conv, t, so, blk._bn2)
     if blk.skip:
@@ -1162,24 +1162,34 @@ def flush_pending() -> None:
 
 
 class _SyncHandle:
-    __slots__ = ("bn", "x", "act", "group", "buf", "ws", "work", "launches_at_issue", "defer")
+    __slots__ = ("bn", "x", "act", "group", "buf", "ws", "work", "launches_at_issue", "defer", "wide")
 
 
-def syncbn_begin(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE, defer_backward: bool = False) -> "_SyncHandle":
-    """Phase 1 of nn.SyncBatchNorm's forward on rows + the asynchronous all-reduce of the [2C + 1] fp64 buffer (sums and row count)."""
+def syncbn_begin(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE, defer_backward: bool = False, wide: bool = False) -> "_SyncHandle":
+    """Phase 1 of nn.SyncBatchNorm's forward on rows + the asynchronous all-reduce of the [2C + 1] fp64 buffer (sums and row count).  wide: the any-width
+    kernel family (fd_batchnorm_train_sync_*; check with _bn_train_wide_ok) on the C-channel view of x [rows, Cw >= C] -- the MBConv trunk's round32(C) maps
+    with zero pad channels, which the output and the input gradient keep; otherwise the GroupNorm-route family (fd_batchnorm_sync_*; _bn_train_ok) on
+    x [rows, C].  Everything behind phase 1 -- the collective, the handle, SYNC_TRACE, the deferred backward -- is the same."""
     import torch.distributed as dist
     h = _SyncHandle()
-    h.bn, h.act, h.defer = bn, act, defer_backward
+    h.bn, h.act, h.defer, h.wide = bn, act, defer_backward, wide
     h.group = bn.process_group if bn.process_group is not None else dist.group.WORLD
     with torch.no_grad():
         xd = x.detach().float().contiguous()
         rows, Cc = xd.shape
-        segs = Segs.make(1, [(rows, 1)])
-        h.ws = ops.groupnorm_workspace(segs, Cc, xd.device)
-        h.buf = torch.empty(2 * Cc + 1, dtype=torch.float64, device=xd.device)
-        fn = _lib.lib().fd_batchnorm_sync_fwd_nhwc
-        ops.check(fn(xd.data_ptr(), Cc, 0, None, None, None, 0, 0, rows, Cc, bn.eps, act, 1, h.buf.data_ptr(), 0.0, h.ws.data_ptr(), ops._stream()),
-                  "fd_batchnorm_sync_fwd_nhwc (stats)")
+        if wide:
+            Cc = bn.num_features
+            if xd.shape[1] < Cc or xd.shape[1] % 4:
+                raise FdError(f"SyncBatchNorm({Cc}) on rows of shape {tuple(x.shape)}: rows of at least {Cc} channels (a multiple of 4) expected")
+            h.buf = torch.empty(2 * Cc + 1, dtype=torch.float64, device=xd.device)
+            h.ws = ops.batchnorm_train_sync_fwd(1, Rows(xd, 0, Cc), h.buf, act_id=act)
+        else:
+            segs = Segs.make(1, [(rows, 1)])
+            h.ws = ops.groupnorm_workspace(segs, Cc, xd.device)
+            h.buf = torch.empty(2 * Cc + 1, dtype=torch.float64, device=xd.device)
+            fn = _lib.lib().fd_batchnorm_sync_fwd_nhwc
+            ops.check(fn(xd.data_ptr(), Cc, 0, None, None, None, 0, 0, rows, Cc, bn.eps, act, 1, h.buf.data_ptr(), 0.0, h.ws.data_ptr(), ops._stream()),
+                      "fd_batchnorm_sync_fwd_nhwc (stats)")
         h.buf[2 * Cc] = float(rows)                               # this rank's row count rides behind the 2C sums (a device-side fill, no sync)
         h.work = dist.all_reduce(h.buf, group=h.group, async_op=True)       # THE forward collective of this layer (C3), not waited for here
     h.x = x
@@ -1205,18 +1215,21 @@ class _SyncBatchNormApply(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, rmean, rvar, momentum, eps, act, h):
         import ctypes as C
         x = x.contiguous()
-        rows, Cc = x.shape
-        y = torch.empty_like(x)
+        rows, Cc = x.shape[0], gamma.numel()
+        y = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)      # (wide: the pad channels stay exactly 0)
         gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
         SYNC_TRACE.append(("fwd", ops.LAUNCHES[0] - h.launches_at_issue))
         h.work.wait()
-        fn, st = _lib.lib().fd_batchnorm_sync_fwd_nhwc, ops._stream()
-        ops.check(fn(x.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), y.data_ptr(), Cc, 0, rows, Cc, eps, act, 2, h.buf.data_ptr(),
-                     C.c_double(-1.0), h.ws.data_ptr(), st), "fd_batchnorm_sync_fwd_nhwc (apply)")
-        if rmean is not None and momentum is not None:
-            ops.batchnorm_update_running_dev(h.ws, h.buf[2 * Cc:], Cc, momentum, eps, rmean, rvar)
+        if h.wide:          # statistics, running statistics (global count from buf[2C] on the device) and apply in one call
+            ops.batchnorm_train_sync_fwd(2, Rows(x, 0, Cc), h.buf, gm, bt, Rows(y, 0, Cc), eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
+        else:
+            fn, st = _lib.lib().fd_batchnorm_sync_fwd_nhwc, ops._stream()
+            ops.check(fn(x.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), y.data_ptr(), Cc, 0, rows, Cc, eps, act, 2, h.buf.data_ptr(),
+                         C.c_double(-1.0), h.ws.data_ptr(), st), "fd_batchnorm_sync_fwd_nhwc (apply)")
+            if rmean is not None and momentum is not None:
+                ops.batchnorm_update_running_dev(h.ws, h.buf[2 * Cc:], Cc, momentum, eps, rmean, rvar)
         ctx.save_for_backward(x, gm, bt, h.ws, h.buf)
-        ctx.geom = (eps, act, h.group, h.defer)
+        ctx.geom = (eps, act, h.group, h.defer, h.wide)
         return y
 
     @staticmethod
@@ -1225,26 +1238,32 @@ class _SyncBatchNormApply(torch.autograd.Function):
         import ctypes as C
         import torch.distributed as dist
         x, gm, bt, ws, buf = ctx.saved_tensors
-        eps, act, group, defer = ctx.geom
-        rows, Cc = x.shape
+        eps, act, group, defer, wide = ctx.geom
+        rows, Cc = x.shape[0], gm.numel()
         g = gy.contiguous()
-        gx = torch.empty_like(x)
+        gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
         dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device)
         dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        segs = Segs.make(1, [(rows, 1)])
-        nb = _lib.lib().fd_groupnorm_bwd_workspace_bytes(C.byref(segs), Cc)
-        bws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
         sums = torch.empty(2 * Cc + 1, dtype=torch.float64, device=x.device)       # [sum dz | sum dz * xhat | global row count]
-        fn = _lib.lib().fd_batchnorm_sync_bwd_nhwc
-        ops.check(fn(x.data_ptr(), Cc, 0, g.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), None, 0, 0, dgamma.data_ptr(), dbeta.data_ptr(),
-                     rows, Cc, eps, act, 1, sums.data_ptr(), 0.0, ws.data_ptr(), bws.data_ptr(), ops._stream()), "fd_batchnorm_sync_bwd_nhwc (sums)")
+        if wide:
+            bws = ops.batchnorm_train_sync_bwd(1, Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, sums, ws, None, dgamma, dbeta, eps, act)
+        else:
+            segs = Segs.make(1, [(rows, 1)])
+            nb = _lib.lib().fd_groupnorm_bwd_workspace_bytes(C.byref(segs), Cc)
+            bws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
+            fn = _lib.lib().fd_batchnorm_sync_bwd_nhwc
+            ops.check(fn(x.data_ptr(), Cc, 0, g.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), None, 0, 0, dgamma.data_ptr(), dbeta.data_ptr(),
+                         rows, Cc, eps, act, 1, sums.data_ptr(), 0.0, ws.data_ptr(), bws.data_ptr(), ops._stream()), "fd_batchnorm_sync_bwd_nhwc (sums)")
         sums[2 * Cc:].copy_(buf[2 * Cc:])                       # the forward's all-reduced row count, device to device (its own slot: not all-reduced again)
         work = dist.all_reduce(sums[:2 * Cc], group=group, async_op=True)     # THE backward collective of this layer
         at_issue = ops.LAUNCHES[0]
 
-        def finish(x=x, g=g, gm=gm, bt=bt, gx=gx, sums=sums, ws=ws, work=work):
+        def finish(x=x, g=g, gm=gm, bt=bt, gx=gx, sums=sums, ws=ws, bws=bws, work=work):
             SYNC_TRACE.append(("bwd", ops.LAUNCHES[0] - at_issue))
             work.wait()
+            if wide:
+                ops.batchnorm_train_sync_bwd(2, Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, sums, ws, Rows(gx, 0, Cc), None, None, eps, act, -1.0, ws=bws)
+                return
             ops.check(fn(x.data_ptr(), Cc, 0, g.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), gx.data_ptr(), Cc, 0, None, None,
                          rows, Cc, eps, act, 2, sums.data_ptr(), C.c_double(-1.0), ws.data_ptr(), None, ops._stream()), "fd_batchnorm_sync_bwd_nhwc (apply)")
 
@@ -1326,8 +1345,9 @@ def _bn_train_wide_ok(bn: nn.Module, x: torch.Tensor) -> bool:
 
 def batchnorm_train_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) -> torch.Tensor:
     """act(bn(x)) with batch statistics on rows at any width C % 4 == 0 up to 4096 (check with _bn_train_wide_ok); x is [rows, C] or a map held at
-    round32(C) with zero pad channels, which the output keeps.  Running statistics and num_batches_tracked move like nn.BatchNorm2d's.  These kernels have no
-    synchronised form: an nn.SyncBatchNorm spanning more than one rank raises."""
+    round32(C) with zero pad channels, which the output keeps.  Running statistics and num_batches_tracked move like nn.BatchNorm2d's.  This is the
+    UNSYNCHRONISED entry point: an nn.SyncBatchNorm spanning more than one rank raises here.  Its synchronised form is syncbn_begin(..., wide=True) /
+    syncbn_finish (fd_batchnorm_train_sync_*), which the callers pick through _bn_wide_rows before this function is reached."""
     Cc = bn.num_features
     if _is_sync(bn):
         raise FdError(f"SyncBatchNorm({Cc}) over more than one rank: the batch-statistics kernels for widths outside C / 4 dividing 256, C <= 1024 "
@@ -1337,6 +1357,14 @@ def batchnorm_train_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NON
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return _BatchNormWideRows.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act)
+
+
+def _bn_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) -> torch.Tensor:
+    """batchnorm_train_wide_rows, or for an nn.SyncBatchNorm spanning ranks its synchronised form in one shot (the MBConv chain is strictly sequential:
+    nothing independent exists to enqueue under the collective)."""
+    if _is_sync(bn):
+        return syncbn_finish(syncbn_begin(bn, x, act, wide=True))
+    return batchnorm_train_wide_rows(bn, x, act)
 
 
 class _SampleScaleAddRows(torch.autograd.Function):
@@ -1414,7 +1442,7 @@ def effnet_stem_rows(net: nn.Module, x: torch.Tensor, h: int, w: int, batch_stat
     if batch_stats:
         if not _bn_train_wide_ok(bn, x):
             raise FdError("EfficientNet stem: batch_stats=True needs _bn0 in training mode with affine parameters and running statistics")
-        t = batchnorm_train_wide_rows(bn, _Stem3Rows.apply(x, m.weight, None, None, (net.stem_pad[0], h, w)), ACT_NONE)
+        t = _bn_wide_rows(bn, _Stem3Rows.apply(x, m.weight, None, None, (net.stem_pad[0], h, w)), ACT_NONE)
     else:
         if not bn_is_frozen(bn):
             raise FdError("EfficientNet stem: train_stem=True without batch_stats folds a FROZEN _bn0")
@@ -1436,11 +1464,12 @@ def conv_norm_begin(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, segs
     that does not need the normalised tensor, then calls conv_norm_finish.  (Any other layer kind is simply computed here.)"""
     if bn is not None and not bn_is_frozen(bn) and _is_sync(bn):
         dense, dw = _dense_ok(m, x), _dw_ok(m, x)
-        if _STOCK or not (dense or dw) or not _bn_train_ok(bn, x) or (dw and m.bias is not None):
+        narrow = _bn_train_ok(bn, x)
+        if _STOCK or not (dense or dw) or not (narrow or _bn_train_wide_ok(bn, x)) or (dw and m.bias is not None):
             return None
         pre = conv_rows(m, x, segs, None, ACT_NONE) if dense else dw_rows(m, x, segs, None, ACT_NONE)
         # the conv node just created is the only consumer of the BatchNorm's input gradient: its backward resolves the deferred second phase
-        return NormHandle(sync=syncbn_begin(bn, pre, act, defer_backward=True))
+        return NormHandle(sync=syncbn_begin(bn, pre, act, defer_backward=True, wide=not narrow))
     y = conv_norm_act_rows(m, bn, x, segs, act)
     return None if y is None else NormHandle(y=y)
 
@@ -1467,9 +1496,9 @@ def conv_norm_act_rows(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, s
         return None
     if not _bn_train_ok(bn, x):
         # widths the GroupNorm-route kernels refuse (C / 4 not dividing 256, C > 1024): the any-width kernels, where the result used to be None
-        if not _bn_train_wide_ok(bn, x) or _is_sync(bn):
+        if not _bn_train_wide_ok(bn, x):
             return None
-        return batchnorm_train_wide_rows(bn, conv(m, x, segs, None, ACT_NONE), act)
+        return _bn_wide_rows(bn, conv(m, x, segs, None, ACT_NONE), act)
     return batchnorm_train_rows(bn, conv(m, x, segs, None, ACT_NONE), act)
 
 

@@ -12,11 +12,14 @@
              written -- the kernels read x, resp. x and dy, TWICE: statistics, then apply), fd_stem_conv_bwd_weight_nhwc4 at Cout 40 (x4 and dy read),
              fd_sample_scale_add_nhwc on a skip block's 48-channel 64^2 map held at 64 channels (branch and input read, output written); the whole
              fp32 / AMP step with the three switches on ("step_full_*"), HIP and stock (the stock trunk follows the same switches)
+  sync       fd_batchnorm_train_sync_fwd / _bwd (SyncBatchNorm at these widths) on ONE device at the two BatchNorm shapes above: phase 1 then phase 2 back
+             to back, no collective, timed in the same run as the unsynchronised launches and ALTERNATING with them ("launches_full_sync": per shape and
+             direction an unsynchronised and a synchronised row, same warm-up, repetitions and median); --sync-only prints that section alone
 
 Method: 10 warm-up launches / 3 warm-up steps, then `REPS` timed runs of a fixed batch of launches / steps; the median and the spread (min .. max) of
 the runs are reported, with the clocks rocm-smi shows before and after (read-only query, when the tool is there).
 
-    python tools/time_effnet_train.py [--reps 5] [--no-stock]
+    python tools/time_effnet_train.py [--reps 5] [--no-stock] [--sync-only]
 """
 import argparse
 import json
@@ -65,6 +68,24 @@ def _time(fn, reps, n=50):
         e1.record()
         torch.cuda.synchronize()
         runs.append(e0.elapsed_time(e1) * 1e3 / n)
+    return runs
+
+
+def _time_alternating(fns, reps, n=50):
+    """_time for several launches measured against each other: every repetition times one batch of n of each, in turn."""
+    for fn in fns:
+        for _ in range(10):
+            fn()
+    runs = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            runs[i].append(e0.elapsed_time(e1) * 1e3 / n)
     return runs
 
 
@@ -125,6 +146,41 @@ def time_full_launches(reps):
     return res
 
 
+def time_sync_launches(reps):
+    """The synchronised form of the batch-statistics BatchNorm on one device (phase 1, phase 2, no collective in between; the global count read from
+    sums[2C] on the device as the autograd node does) against the unsynchronised launch at the same shape, alternating in one run."""
+    res = []
+    for name, C, H in (("blocks.2 _bn0/_bn1 144 x 256^2", 144, 256), ("blocks.14 _bn0/_bn1 816 x 32^2", 816, 32)):
+        rows, Cw = B * H * H, (C + 31) // 32 * 32
+        x, dy = torch.randn(rows, Cw, device=DEV), torch.randn(rows, Cw, device=DEV)
+        y, dx = torch.zeros_like(x), torch.zeros_like(x)
+        gm, bt = torch.rand(C, device=DEV) + 0.5, torch.randn(C, device=DEV)
+        rm, rv = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+        dg, db = torch.empty(C, device=DEV), torch.empty(C, device=DEV)
+        xr, gr, yr, dr = (ops.Rows(t, 0, C) for t in (x, dy, y, dx))
+        ws, ws2 = ops.batchnorm_train_workspace(rows, C, DEV), ops.batchnorm_train_workspace(rows, C, DEV)
+        sums, bsums = (torch.zeros(2 * C + 1, dtype=torch.float64, device=DEV) for _ in range(2))
+        sums[2 * C], bsums[2 * C] = float(rows), float(rows)
+        fwd = lambda: ops.batchnorm_train_fwd(xr, gm, bt, yr, 1e-3, ops.ACT_SILU, 0.01, rm, rv, ws)  # noqa: E731
+        bwd = lambda: ops.batchnorm_train_bwd(xr, gr, gm, bt, dr, 1e-3, ops.ACT_SILU, ws, ws2)  # noqa: E731
+
+        def sync_fwd():
+            ops.batchnorm_train_sync_fwd(1, xr, sums, act_id=ops.ACT_SILU, ws=ws)
+            ops.batchnorm_train_sync_fwd(2, xr, sums, gm, bt, yr, 1e-3, ops.ACT_SILU, -1.0, 0.01, rm, rv, ws=ws)
+
+        def sync_bwd():
+            ops.batchnorm_train_sync_bwd(1, xr, gr, gm, bt, bsums, ws, None, dg, db, 1e-3, ops.ACT_SILU, ws=ws2)
+            ops.batchnorm_train_sync_bwd(2, xr, gr, gm, bt, bsums, ws, dr, None, None, 1e-3, ops.ACT_SILU, -1.0, ws=ws2)
+
+        r_fwd, r_sfwd = _time_alternating((fwd, sync_fwd), reps)
+        r_bwd, r_sbwd = _time_alternating((bwd, sync_bwd), reps)
+        res.append(_row(name, "batchnorm_train_fwd", C, rows, r_fwd, 2 * rows * C * 4))
+        res.append(_row(name, "batchnorm_train_sync_fwd (phase 1 + 2)", C, rows, r_sfwd, 2 * rows * C * 4))
+        res.append(_row(name, "batchnorm_train_bwd", C, rows, r_bwd, 3 * rows * C * 4))
+        res.append(_row(name, "batchnorm_train_sync_bwd (phase 1 + 2)", C, rows, r_sbwd, 3 * rows * C * 4))
+    return res
+
+
 def batch():
     g = torch.Generator(device=DEV).manual_seed(7)
     x = torch.randn(B, 3, S, S, device=DEV, generator=g)
@@ -176,6 +232,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-stock", action="store_true")
+    ap.add_argument("--sync-only", action="store_true", help="time the synchronised BatchNorm launches against the unsynchronised ones only")
     ap.add_argument("--steps-only", action="store_true", help="(internal) time the two steps only and print them")
     ap.add_argument("--stock", action="store_true", help="(internal, with --steps-only) the child process that runs with FD_TRAIN_STOCK_CONV=1")
     args = ap.parse_args()
@@ -185,10 +242,16 @@ def main():
         return
     res = {"tool": "time_effnet_train", "device": torch.cuda.get_device_name(0), "model": "FCOS EfficientNet-B3", "batch": B, "input": S, "reps": args.reps,
            "clocks_before": clocks()}
+    if args.sync_only:
+        res["launches_full_sync"] = time_sync_launches(args.reps)
+        res["clocks_after"] = clocks()
+        print(json.dumps(res))
+        return
     res["launches"] = time_launches(args.reps)
     res["step_hip_fp32"] = time_step(False, args.reps)
     res["step_hip_amp"] = time_step(True, args.reps)
     res["launches_full"] = time_full_launches(args.reps)
+    res["launches_full_sync"] = time_sync_launches(args.reps)
     res["step_full_hip_fp32"] = time_step(False, args.reps, full=True)
     res["step_full_hip_amp"] = time_step(True, args.reps, full=True)
     if not args.no_stock:
