@@ -25,7 +25,8 @@
 //     workspace, the direct kernel's combine launch finishes (fd_launch_splitk_reduce);
 //   * epilogue: the two halves of the 32 tiles in turn -- all waves put that half of their accumulators into LDS planes, then every thread gathers the
 //     36 frequencies of (tile, 4 couts), applies A^T . A for two of the four output rows and y = act(v * scale + shift (+ | mask) res) and stores
-//     16 bytes per pixel.
+//     16 bytes per pixel.  Where its tile lies it reads from a table of 32 records that the loader's set-up leaves in LDS (behind V and the scratch); its stores and
+//     residual loads are raw buffer accesses at a 32-bit offset, OOB for a pixel outside the image.
 // DESIGN 4.1d has the measurements (head tower 1.39 -> 0.92 ms against F(2x2)) and what did and did not matter on the way there.
 #include "fd_conv_common.h"
 #include <type_traits>
@@ -49,6 +50,7 @@ struct Wino4Args {
     int mtiles, ntiles, mt_per;   // M tiles (32 tiles each), N tiles (64 cout), M tiles per XCD
     int blk0;                     // first workgroup of this launch in the layer's grid (fd_conv_params.wg_first; a multiple of 8: the XCD of a workgroup is unchanged)
     unsigned x_bytes, u_bytes;
+    unsigned y_bytes, res_bytes;  // extent of the output (per split-K slice) / residual view; 0 where one of them is too large for 32-bit byte offsets (output pass: plain pointers)
     // persistent stream-K form (SK kernels; fd_conv_params.sk_wgs): 8 * wpx workgroups, each walks a contiguous range of its XCD's (item, chunk) units
     int wpx;                      // workgroups per XCD
     int sk_P;                     // pieces a remainder item is queued as
@@ -79,6 +81,12 @@ struct Wino4Args {
 #define W4_STAGE (36 * W4_PLANE)            // floats per V stage (36 KB)
 #define W4_SBLK 37                          // float4s per (tile, channel quad) block of the scratch: 36 + 1, odd, so that 64 lanes = 64 blocks never share a bank
 #define W4_SSTAGE (64 * W4_SBLK * 4)        // floats per scratch stage (37 KB)
+// behind V and the scratch (the epilogue's frequency planes reuse bytes 0 .. 147 455 only): the SK form's claim word, then the workgroup's tile table -- one record of
+// two int4 per tile, written by the loader's set-up (which decodes the tile anyway), read by the output pass:
+//   [0] = {ok | level << 1, image, first output row, first output column (image coordinates: h0 * dil + ph, w0 * dil + pw)}   [1] = {H, W, m0 + image * H * W, seg_param}
+#define W4_CLAIM_OFF ((2 * W4_STAGE + 2 * W4_SSTAGE) * 4)
+#define W4_TAB_OFF (W4_CLAIM_OFF + 16)
+#define W4_LDS_BYTES (W4_TAB_OFF + W4_TB * 32)      // 147.0 KB
 
 struct Tile4 { int s, n, h0, w0, ph, pw; bool ok; };     // h0, w0: first output of the tile in sub-grid coordinates
 
@@ -169,7 +177,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino4_kernel(Wino4Args a) {
     // SK: the XCD's queue = sk_W whole items, then the pieces of the remaining items; u = the unit this workgroup holds
     int sk_W = 0, sk_units = 0, u = 0;
     int* const sk_ctr = a.flags + (SK ? W4_SK_MAX_WGS + xcd : 0);
-    int* const claim_lds = reinterpret_cast<int*>(smem + (2 * W4_STAGE + 2 * W4_SSTAGE) * 4);
+    int* const claim_lds = reinterpret_cast<int*>(smem + W4_CLAIM_OFF);
+    int4* const tab = reinterpret_cast<int4*>(smem + W4_TAB_OFF);
     if constexpr (SK) {
         const int items = max(cnt, 0) * a.ntiles;
         const int rem = items % a.wpx;
@@ -244,6 +253,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino4_kernel(Wino4Args a) {
         const unsigned a_base = ((unsigned)(rowbase + p.w0 * a.dil + p.pw) * (unsigned)a.x_cs + (unsigned)(a.x_co + q * 4)) * 4u;    // column j = 1
 #pragma unroll
         for (int j = 0; j < 6; ++j) a_off[j] = (row_ok && (unsigned)((p.w0 - 1 + j) * a.dil + p.pw) < (unsigned)W) ? a_base : OOB;
+        // the tile table of the output pass: the 32 lanes of wave 0 that hold a distinct tile.  (SK: the previous segment's output pass has read its records -- the
+        // barrier that ends a segment lies between.)
+        if (tid < 64 && q == 0) {
+            tab[2 * lt] = make_int4((p.ok ? 1 : 0) | (p.s << 1), p.n, p.h0 * a.dil + p.ph, p.w0 * a.dil + p.pw);
+            tab[2 * lt + 1] = make_int4(H, W, a.m0[p.s] + p.n * H * W, __float_as_int(a.seg_param[p.s]));
+        }
     }
 
     // ---- MFMA role ----
@@ -397,6 +412,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino4_kernel(Wino4Args a) {
         }
     }
     float* Ms = reinterpret_cast<float*>(smem);                          // [2 ch][36 f][16 tiles][32 cout]
+    // The output pass addresses its stores and residual loads like the loader its patch rows: one 32-bit byte offset per thread and row (OOB for a pixel outside the
+    // image) plus a scalar offset per column.  y_bytes = 0: a view too large for that -- 64-bit pointers and branches around the pixels outside.
+    const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.y + (size_t)blockIdx.y * a.slice_stride), (short)0, (int)a.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, (short)0, (int)a.res_bytes, 0x00020000);
     // output role: thread = (channel block, row pair of the 4 x 4 outputs, tile of the half, cout quad)
     int te = tid;
     asm volatile("" : "+v"(te));                                         // (opaque: nothing of the output role is computed, and kept in registers, ahead of the main loop)
@@ -414,10 +433,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino4_kernel(Wino4Args a) {
             for (int e = 0; e < 8; ++e) d[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32] = acc[fi][8 * h + e];
         }
         __syncthreads();
-        const Tile4 ep = wino4_decode(a, tile0 + 16 * h + et);
-        const int eH = a.H[ep.s], eW = a.W[ep.s];
-        const float eprm = a.seg_param[ep.s];
-        if (ep.ok && nn < a.Cout && !(W4_DBG(a) & 16)) {       // (timing builds, 16: dump + barriers only)
+        // the tile's record from the set-up's table: no level search, division or per-lane read of the argument block here (such a read is a vector-memory load whose
+        // wait also waits for every output store of half 0)
+        const int4 er0 = tab[2 * (16 * h + et)], er1 = tab[2 * (16 * h + et) + 1];
+        const int eH = er1.x, eW = er1.y;
+        const float eprm = __int_as_float(er1.w);
+        if ((er0.x & 1) && nn < a.Cout && !(W4_DBG(a) & 16)) {       // (timing builds, 16: dump + barriers only)
             // Y = A^T M A, A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]: per frequency row i the column pass r_i[y], then
             // Y[x][y] += A^T[x][i] * r_i[y] for this thread's two rows x = 2 eh, 2 eh + 1 (eh is wave-uniform; the zero entries of A^T cost nothing)
             float4 Y[2][4];
@@ -483,21 +504,32 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino4_kernel(Wino4Args a) {
             // The eight stores of this thread as TWO copies of the loop: FAST = no activation or ReLU / SiLU on every channel of the tile -- a dozen instructions
             // per store, contiguous; the general copy carries the residual fetch and fd_act's whole switch (ScaleExp, SiLU, sigmoid) per channel.  As ONE loop the
             // ReLU layers hopped through ~8 000 instructions of mostly skipped code per output pass (the finding of DESIGN 4.3c on the AMP kernel: 40 % there).
+            // buf (every view but the largest): the addresses as 32-bit byte offsets into the output / residual resources -- one per thread for (row 2 eh, column 0), the second row one add away, the
+            // columns a scalar offset each; a pixel outside the image gets the offset OOB (its store is dropped, its residual load returns zeros) instead of a branch.
             auto store_sites = [&](auto fast_c) {
                 constexpr bool FAST = decltype(fast_c)::value;
+                const bool buf = a.y_bytes != 0;                         // (uniform)
+                const int hq = er0.z + 2 * eh * a.dil, wq = er0.w;       // this thread's first output pixel
+                const unsigned pix0 = (unsigned)(er1.z + hq * eW + wq);
+                unsigned y_off = (pix0 * (unsigned)a.y_cs + (unsigned)(a.y_co + nn)) * 4u, r_off = (pix0 * (unsigned)a.res_cs + (unsigned)(a.res_co + nn)) * 4u;
+                const unsigned y_row = (unsigned)(a.dil * eW * a.y_cs) * 4u, r_row = (unsigned)(a.dil * eW * a.res_cs) * 4u;
+                const int y_px = a.dil * a.y_cs * 4, r_px = a.dil * a.res_cs * 4;      // (uniform)
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
-                    const int hh = (ep.h0 + 2 * eh + x) * a.dil + ep.ph;
-                    if (hh >= eH) continue;
+                    const int hh = hq + x * a.dil;
 #pragma unroll
                     for (int y = 0; y < 4; ++y) {
-                        const int w = (ep.w0 + y) * a.dil + ep.pw;
-                        if (w >= eW) continue;
-                        const size_t m_ = (size_t)(a.m0[ep.s] + (ep.n * eH + hh) * eW + w);
+                        const int w = wq + y * a.dil;
+                        const bool in = hh < eH && w < eW;
+                        auto load_res = [&]() -> float4 {
+                            if (buf) return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rrsrc, (int)(in ? r_off + x * r_row : OOB), y * r_px, 0));
+                            const size_t m_ = (size_t)(er1.z + hh * eW + w);
+                            return in ? *reinterpret_cast<const float4*>(a.res + m_ * a.res_cs + a.res_co + nn) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        };
                         float4 v = make_float4(Y[x][y].x * sc.x + sf.x, Y[x][y].y * sc.y + sf.y, Y[x][y].z * sc.z + sf.z, Y[x][y].w * sc.w + sf.w);
                         if constexpr (FAST) {
                             if (a.res) {                       // (uniform) the training step's data gradients: ReLU mask of the layer below, or an addend
-                                const float4 rr = *reinterpret_cast<const float4*>(a.res + m_ * a.res_cs + a.res_co + nn);
+                                const float4 rr = load_res();
                                 if (a.res_mask) {
                                     v.x = rr.x > 0.f ? v.x : 0.f; v.y = rr.y > 0.f ? v.y : 0.f; v.z = rr.z > 0.f ? v.z : 0.f; v.w = rr.w > 0.f ? v.w : 0.f;
                                 } else {
@@ -511,7 +543,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino4_kernel(Wino4Args a) {
                             }
                         } else {
                             if (a.res) {
-                                const float4 rr = *reinterpret_cast<const float4*>(a.res + m_ * a.res_cs + a.res_co + nn);
+                                const float4 rr = load_res();
                                 if (a.res_mask) {
                                     v.x = rr.x > 0.f ? v.x : 0.f; v.y = rr.y > 0.f ? v.y : 0.f; v.z = rr.z > 0.f ? v.z : 0.f; v.w = rr.w > 0.f ? v.w : 0.f;
                                 } else {
@@ -526,12 +558,18 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino4_kernel(Wino4Args a) {
                             }
                         }
                         if ((W4_DBG(a) & 8) && v.x != 12345.678f) continue;          // (timing builds: the epilogue without its global stores)
-                        *reinterpret_cast<float4*>(a.y + (size_t)blockIdx.y * a.slice_stride + m_ * a.y_cs + a.y_co + nn) = v;
+                        if (buf) {
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((__vector_size__(4 * sizeof(unsigned)))) unsigned, v), yrsrc,
+                                                                   (int)(in ? y_off + x * y_row : OOB), y * y_px, 0);
+                        } else if (in) {
+                            const size_t m_ = (size_t)(er1.z + hh * eW + w);
+                            *reinterpret_cast<float4*>(a.y + (size_t)blockIdx.y * a.slice_stride + m_ * a.y_cs + a.y_co + nn) = v;
+                        }
                     }
                 }
             };
-            if (a.act == FD_ACT_NONE || ((a.act == FD_ACT_RELU || a.act == FD_ACT_SILU) && a.act_c0 <= n0)) store_sites(std::integral_constant<bool, true>{});       // (uniform)
-            else store_sites(std::integral_constant<bool, false>{});
+            if (a.act == FD_ACT_NONE || ((a.act == FD_ACT_RELU || a.act == FD_ACT_SILU) && a.act_c0 <= n0)) store_sites(std::true_type{});       // (uniform)
+            else store_sites(std::false_type{});
         }
     }
     if constexpr (!SK) break;
@@ -661,7 +699,7 @@ int fd_launch_conv_wino4(const fd_conv_params* p, hipStream_t stream) {
     a.mtiles = (a.T + W4_TB - 1) / W4_TB;
     a.ntiles = (p->Cout + 63) / 64;
     a.mt_per = (a.mtiles + 7) / 8;
-    constexpr int lds = (2 * W4_STAGE + 2 * W4_SSTAGE) * 4 + 16;   // 146 KB + the SK form's claim word
+    constexpr int lds = W4_LDS_BYTES;                              // 146 KB + the SK form's claim word + the tile table (1 KB)
     a.nc_per = a.NC; a.slice_stride = 0;
     const int ksplit = p->ksplit > 1 ? p->ksplit : 1;
     ConvArgs o = {};
@@ -685,6 +723,12 @@ int fd_launch_conv_wino4(const fd_conv_params* p, hipStream_t stream) {
         o.sc_on = 0;
         a.y = (float*)p->workspace; a.y_cs = ldw; a.y_co = 0; a.slice_stride = slab;
         a.scale = a.shift = a.res = nullptr; a.act = FD_ACT_NONE; a.res_mask = 0;
+    }
+    {   // the output pass's buffer resources: the extent of the view the kernel stores to (split-K: one slice's slab) and of the residual view
+        const long yb = ((rows - 1) * a.y_cs + a.y_co + p->Cout) * 4, rb = a.res ? ((rows - 1) * a.res_cs + a.res_co + p->Cout) * 4 : 0;
+        // (and the scalar column offsets, at most 3 * dil pixels, stay far from wrapping an offset that is OOB)
+        const bool fits = yb < 0xC0000000L && rb < 0xC0000000L && (long)a.y_cs * 24 < 0x40000000L && (!a.res || (long)a.res_cs * 24 < 0x40000000L);
+        a.y_bytes = fits ? (unsigned)yb : 0u; a.res_bytes = fits ? (unsigned)rb : 0u;
     }
     const int nslice = (a.NC + a.nc_per - 1) / a.nc_per;
     dim3 grid((unsigned)(8 * a.mt_per * a.ntiles), (unsigned)nslice);
