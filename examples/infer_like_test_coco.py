@@ -6,6 +6,11 @@
 Per image (batch 1, as the reference evaluates): uint8 HWC image resized on the host to (min side 800, max side 1333)
 and zero padded to a multiple of 32 (dataset/coco.py preprocess) -> model -> FCOSHead(0.05, 0.6, 1000) -> ClipBoxes ->
 boxes /= scale, xyxy -> xywh.  Only the host-side resize is numpy; everything from the padded uint8 image on is HIP.
+
+With a real data set the same loop plus COCOeval is Test_coco.evaluate_coco(generator, model).  Across GPUs, start one process
+per GPU (python -m torch.distributed.run --nproc_per_node 8 your_script.py), init_process_group("nccl") in each, and call
+evaluate_coco(generator, model, gather=True) on EVERY rank: rank r runs images r, r + 8, ..., the detections are merged, every
+rank returns the same 12 stats and rank 0 prints them.
 """
 import argparse
 import os

@@ -10,11 +10,13 @@ The kernels are in csrc/fd_eval.hip.
 from __future__ import annotations
 
 import json
+import zlib
 from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import dist as _dist
 from . import ops
 from ._lib import FdError
 from .model.modules.head import ClipBoxes, FCOSHead
@@ -197,6 +199,32 @@ class COCOEvaluator:
         self._seen.update(ids)
         self._n = n + B
 
+    def gather(self, group=None, force: bool = False) -> "COCOEvaluator":
+        """The union of every rank's evaluator, as a new evaluator on this rank's device; every rank must call it, and every
+        rank gets the same rows: each distinct image id once (of an id two ranks hold, the lowest rank's row), ids ascending.
+        Only detections and ids travel -- every rank holds the GT already (two collectives, dist.gather_rows); ranks whose GT
+        differ in their categories or images raise FdError, all of them.  No process group, or world size 1 without
+        `force`: returns self."""
+        if _dist._no_group(group, force):
+            return self
+        dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        n = self._n
+        bufs = self._bufs if self._bufs is not None else self._alloc(0, 0, dev)
+        ids = torch.tensor(self._ids, dtype=torch.int64).to(dev)
+        header = (self.gt.num_cats, len(self.gt.image_ids),
+                  zlib.crc32(np.ascontiguousarray(self.gt.category_ids, np.int64).tobytes() + np.ascontiguousarray(self.gt.image_ids, np.int64).tobytes()))
+        got, _, _ = _dist._gather_rows(list(bufs) + [ids], n, group, None, header)
+        out = COCOEvaluator(self.gt, device=dev)
+        out._gt_dev = self._gt_dev
+        all_ids = got.pop().cpu()
+        order = _dist.merge_order(all_ids)
+        if order.numel():
+            out._ids = all_ids[order].tolist()
+            out._seen = set(out._ids)
+            out._bufs = tuple(t.index_select(0, order.to(dev)) for t in got)
+            out._n = order.numel()
+        return out
+
     def _gt_on(self, dev):
         if self._gt_dev is None or self._gt_dev[0].device != dev:
             g = self.gt
@@ -236,13 +264,19 @@ class COCOEvaluator:
         return self.result["stats"]
 
 
-def evaluate_coco(generator, model, threshold=0.05):
+def evaluate_coco(generator, model, threshold=0.05, gather=False):
     """The reference's evaluate_coco (Test_coco.py:120-190): per image FCOSHead(0.05, 0.6, 1000, [8, 16, 32, 64]) -> ClipBoxes ->
     boxes / scale -> xywh, detections from the first with score < threshold on dropped, labels mapped through
     generator.id2category; then COCOeval against generator.coco (crowd annotations included) over the processed images, and the
     summary printed.  The generator is duck-typed: len, [index] -> (img, boxes, classes, scale), .ids, .id2category, .coco.
-    Detections stay on the device (COCOEvaluator).  Differences: no coco_bbox_results.json is written; each rank evaluates what
-    it saw (no cross-rank gather).  -> stats (12 numbers), or None when there is no detection at all."""
+    Detections stay on the device (COCOEvaluator).  Difference: no coco_bbox_results.json is written.
+    gather=False: this process runs every image of the generator, computes and prints.  gather=True: EVERY rank must call; rank
+    r of W runs the generator's indices r, r + W, r + 2W, ..., the evaluators are merged (COCOEvaluator.gather: two collectives),
+    every rank computes the same stats and rank 0 prints them; whether there is a detection at all is read off the merged rows
+    (a detection whose category the GT does not list takes no part there, as in the evaluation itself).  Without a process
+    group gather=True runs every image here.  -> stats (12 numbers), or None when there is no detection at all."""
+    grouped = gather and torch.distributed.is_available() and torch.distributed.is_initialized()
+    rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if grouped else (0, 1)
     head = FCOSHead(0.05, 0.6, 1000, [8, 16, 32, 64])
     clip = ClipBoxes()
     ev = COCOEvaluator(generator.coco)
@@ -254,7 +288,7 @@ def evaluate_coco(generator, model, threshold=0.05):
     lut = lut.to(dev)
     any_det = torch.zeros((), dtype=torch.int64, device=dev)
     with torch.no_grad():
-        for index in range(len(generator)):
+        for index in range(rank, len(generator), world):
             img, _, _, scale = generator[index]
             x = (img if torch.is_tensor(img) else torch.from_numpy(np.asarray(img))).unsqueeze(dim=0).to(dev)
             out = model(x)
@@ -269,7 +303,13 @@ def evaluate_coco(generator, model, threshold=0.05):
             lab = lut[labels.clamp(0, lut.shape[0] - 1)] * (labels < lut.shape[0]).to(torch.int64)
             any_det += n.sum()
             ev.add([generator.ids[index]], scores.float().contiguous(), lab, boxes.float().contiguous(), n.to(torch.int32))
-    if int(any_det) == 0:
+    if gather:
+        ev = ev.gather()
+        if ev.num_images == 0 or not bool((ev._bufs[1][:ev.num_images] != 0).any()):
+            return None
+    elif int(any_det) == 0:
         return None
-    ev.compute()
-    return ev.summarize()
+    stats = ev.compute()["stats"]
+    if rank == 0:
+        print(format_stats(stats))
+    return stats

@@ -1,12 +1,17 @@
 """Image-sharded multi-GPU inference: one process per GPU (torch.distributed, backend 'nccl' = RCCL over xGMI),
 batch split in contiguous slices, weights replicated, and ONE collective — an all-gather of the fixed-size padded
-detections.  The network itself exchanges nothing (frozen BN, per-sample GN / SE)."""
+detections.  The network itself exchanges nothing (frozen BN, per-sample GN / SE).
+
+Sharded evaluation adds a ragged row gather, `gather_rows` (two collectives: the ranks' sizes, then one
+uint8 payload), and `merge_order`, the row order of the union of what the ranks evaluated."""
 from __future__ import annotations
 
-from typing import Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
+
+from ._lib import FdError
 
 
 def shard_batch(global_batch: int, rank: int, world: int) -> Tuple[int, int]:
@@ -63,3 +68,104 @@ def unpad_gathered(gathered, global_batch: int, world: int):
     pad = max(sizes)
     idx = torch.cat([torch.arange(r * pad, r * pad + n) for r, n in enumerate(sizes)]).to(gathered[0].device)
     return tuple(t.index_select(0, idx) for t in gathered)
+
+
+# ---------------------------------------------------------------------------------------------- sharded evaluation
+def _no_group(group, force: bool) -> bool:
+    return not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size(group) == 1 and not force)
+
+
+def _pad_block(t: torch.Tensor, n: int, rows: int, width: int, fill) -> torch.Tensor:
+    """The first n rows of t in a [rows, width, ...] block (a [rows] block for a 1-D tensor), the rest holding `fill`."""
+    if t.dim() == 1:
+        out = torch.full((rows,), fill, dtype=t.dtype, device=t.device)
+        out[:n] = t[:n]
+        return out
+    out = torch.full((rows, width) + tuple(t.shape[2:]), fill, dtype=t.dtype, device=t.device)
+    out[:n, :t.shape[1]] = t[:n]
+    return out
+
+
+def _gather_rows(tensors: Sequence[torch.Tensor], n: int, group, fills: Optional[Sequence], header: Sequence[int]):
+    """gather_rows' protocol, which also hands back every rank's header: -> (tensors, rows_per_rank, headers [W, len(header)])."""
+    world = dist.get_world_size(group)
+    tensors = list(tensors)
+    fills = [0] * len(tensors) if fills is None else list(fills)
+    n = int(n)
+    if not tensors or len(fills) != len(tensors):
+        raise FdError("gather_rows: needs at least one tensor and one fill value per tensor")
+    dev = tensors[0].device
+    for t in tensors:
+        if t.dtype not in (torch.float32, torch.int32, torch.int64) or t.dim() < 1 or t.shape[0] < n or t.device != dev:
+            raise FdError("gather_rows: f32 / i32 / i64 tensors on one device with at least n rows each")
+    # collective 1: n, the dimension-1 widths, the header -- a fixed-size message
+    msg = torch.tensor([n] + [t.shape[1] if t.dim() > 1 else 0 for t in tensors] + [int(h) for h in header], dtype=torch.int64, device=dev)
+    sizes = torch.empty(world * msg.numel(), dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(sizes, msg, group=group)
+    sizes = sizes.cpu().view(world, msg.numel())
+    rows = [int(v) for v in sizes[:, 0]]
+    headers = sizes[:, 1 + len(tensors):]
+    for k in range(headers.shape[1]):           # every rank sees the same table: all of them raise, none waits in collective 2
+        vals = sorted({int(v) for v in headers[:, k] if int(v) >= 0})
+        if len(vals) > 1:
+            raise FdError(f"gather_rows: the ranks disagree on header value {k}: {[int(v) for v in headers[:, k]]}")
+    widths = [int(v) for v in sizes[:, 1:1 + len(tensors)].max(dim=0).values]
+    pad = max(rows)
+    if pad == 0:                                # no rank has a row, and every rank knows: nothing to send
+        return [_pad_block(t, 0, 0, w, f) for t, w, f in zip(tensors, widths, fills)], rows, headers
+    # collective 2: every tensor padded to [pad, width, ...], as bytes, each block on an 8-byte boundary
+    blocks = [_pad_block(t, n, pad, w, f) for t, w, f in zip(tensors, widths, fills)]
+    nbytes = [(b.numel() * b.element_size() + 7) // 8 * 8 for b in blocks]
+    send = torch.zeros(sum(nbytes), dtype=torch.uint8, device=dev)
+    off = 0
+    for b, nb in zip(blocks, nbytes):
+        send[off:off + b.numel() * b.element_size()] = b.view(-1).view(torch.uint8)
+        off += nb
+    recv = torch.empty(world * send.numel(), dtype=torch.uint8, device=dev)
+    dist.all_gather_into_tensor(recv, send, group=group)
+    recv = recv.view(world, send.numel())
+    out, off = [], 0
+    for b, nb in zip(blocks, nbytes):
+        live = b.numel() * b.element_size()
+        parts = [recv[r, off:off + live].view(b.dtype).view(b.shape)[:rows[r]] for r in range(world)]
+        out.append(torch.cat(parts, 0))
+        off += nb
+    return out, rows, headers
+
+
+def gather_rows(tensors: Sequence[torch.Tensor], n: int, group=None, force: bool = False, fills: Optional[Sequence] = None,
+                header: Sequence[int] = ()) -> Tuple[List[torch.Tensor], List[int]]:
+    """Ragged all-gather of rows: every rank contributes the first `n` rows of each of `tensors` (f32 / i32 / i64, one device,
+    the same trailing shapes on every rank except dimension 1 -- a K or G width -- which may differ from rank to rank).
+    -> ([rank 0's rows, then rank 1's, ...] per tensor, rows_per_rank); dimension 1 is the widest rank's, the columns a
+    narrower rank did not have hold that tensor's `fills` value (default 0).
+
+    TWO collectives: an all_gather_into_tensor of the sizes (n, the widths and `header`), then one of a uint8 payload in which
+    every rank has padded its columns to the widest and its rows to the largest n (the padding rows are dropped on arrival).
+    When no rank has a row the sizes say so on every rank and the payload is skipped.  `header`: ints that must be equal on
+    every rank (a negative value agrees with anything); a disagreement raises FdError on every rank before the payload, so no
+    rank is left waiting.  CUDA tensors travel as they are (RCCL); CPU tensors take the same protocol over gloo.
+    No initialised process group, or world size 1 without `force`: the inputs' first n rows (views) and no collective."""
+    if _no_group(group, force):
+        return [t[:int(n)] for t in tensors], [int(n)]
+    out, rows, _ = _gather_rows(tensors, n, group, fills, header)
+    return out, rows
+
+
+def merge_order(ids_per_rank) -> torch.Tensor:
+    """Row order of a merged evaluation.  `ids_per_rank`: the image id of every gathered row, rank 0's rows first, as one flat
+    sequence or as one sequence per rank.  -> int64 index that visits each distinct id once, ids ascending; of equal ids it
+    keeps the first row, i.e. the lowest rank's earliest arrival.  Host arithmetic only."""
+    flat: List[int] = []
+    for x in (ids_per_rank.tolist() if torch.is_tensor(ids_per_rank) else ids_per_rank):
+        if isinstance(x, (list, tuple)) or torch.is_tensor(x) or hasattr(x, "tolist"):
+            flat.extend(int(i) for i in (x.tolist() if hasattr(x, "tolist") else x))
+        else:
+            flat.append(int(x))
+    ids = torch.tensor(flat, dtype=torch.int64)
+    if ids.numel() == 0:
+        return ids
+    srt, order = torch.sort(ids, stable=True)
+    keep = torch.ones(ids.numel(), dtype=torch.bool)
+    keep[1:] = srt[1:] != srt[:-1]
+    return order[keep]

@@ -11,11 +11,13 @@ csrc/fd_eval.hip (fd_eval_ap, include/fcosdet.h).
 from __future__ import annotations
 
 import time
+import zlib
 from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
+from . import dist as _dist
 from . import ops
 from ._lib import FdError
 from .model.modules.head import ClipBoxes, FCOSHead
@@ -40,7 +42,11 @@ class VOCEvaluator:
 
     add() takes what FCOSHead.detect_padded + ClipBoxes produce and what the VOC collate yields, and only enqueues device copies
     (no host synchronisation); batches may differ in K (detections per image) and G (GT rows per image).  compute() runs
-    fd_eval_ap once and copies one packed result to the host."""
+    fd_eval_ap once and copies one packed result to the host.
+
+    Under sharded evaluation every rank fills its own evaluator and gather() returns the union on every rank.
+    Image ids (add(image_ids=...)) let the union drop the images a padding sampler handed to two ranks and put the rest in id
+    order, which fixes the order among equal scores; without ids the union is every row in (rank, arrival) order."""
 
     def __init__(self, num_cls: int = 21, iou_thresholds: Sequence[float] = (0.5,), device=None):
         if not 2 <= num_cls <= 128 or not 1 <= len(iou_thresholds) <= 16:
@@ -50,10 +56,30 @@ class VOCEvaluator:
         self.device = torch.device(device) if device is not None else None
         self._n = 0
         self._bufs = None       # scores [cap, K] f32, classes [cap, K] int64 (0 = not taking part), boxes [cap, K, 4], gt boxes [cap, G, 4], gt classes [cap, G] (-1 = padding)
+        self._ids = None        # image id of each added row; None: add() was given no ids (or nothing was added yet)
 
     def reset(self) -> None:
         """Forget every image added; the device buffers are kept for reuse (add() overwrites the rows it appends in full)."""
         self._n = 0
+        self._ids = None
+
+    def _take_ids(self, image_ids, B: int) -> None:
+        """One evaluator takes ids on every add() or on none; an id is added once."""
+        if image_ids is None:
+            if self._ids is not None:
+                raise FdError("VOCEvaluator.add: earlier batches came with image_ids, this one without")
+            return
+        ids = [int(i) for i in image_ids]
+        if self._ids is None and self._n:
+            raise FdError("VOCEvaluator.add: earlier batches came without image_ids, this one with")
+        if len(ids) != B:
+            raise FdError(f"VOCEvaluator.add: {len(ids)} image_ids for {B} images")
+        seen = set(self._ids or ())
+        for i in ids:
+            if i in seen:
+                raise FdError(f"VOCEvaluator.add: image id {i} added twice")
+            seen.add(i)
+        self._ids = (self._ids or []) + ids
 
     @property
     def num_images(self) -> int:
@@ -82,9 +108,9 @@ class VOCEvaluator:
         self._bufs = new
 
     def add(self, scores: torch.Tensor, classes: torch.Tensor, boxes: torch.Tensor, counts: Optional[torch.Tensor],
-            gt_boxes: torch.Tensor, gt_classes: torch.Tensor) -> None:
+            gt_boxes: torch.Tensor, gt_classes: torch.Tensor, *, image_ids: Optional[Sequence[int]] = None) -> None:
         """scores [B,K], classes [B,K] (1-based), boxes [B,K,4], counts [B] (rows >= counts[b] ignored; None = all rows), gt_boxes
-        [B,G,4], gt_classes [B,G] (-1 = padding).  Device tensors only."""
+        [B,G,4], gt_classes [B,G] (-1 = padding).  Device tensors only.  image_ids: B host ints, on every add() or on none."""
         ops._need_gpu(scores, classes, boxes, counts, gt_boxes, gt_classes)
         B, K = scores.shape
         G = gt_classes.shape[1]
@@ -92,6 +118,7 @@ class VOCEvaluator:
             raise FdError("VOCEvaluator.add: shapes do not agree")
         if K > MAX_DETECTIONS or G > MAX_GT:
             raise FdError(f"VOCEvaluator.add: at most {MAX_DETECTIONS} detections and {MAX_GT} GT rows per image (got K={K}, G={G})")
+        self._take_ids(image_ids, B)
         dev = scores.device
         if self.device is None:
             self.device = dev
@@ -111,6 +138,40 @@ class VOCEvaluator:
         gc[n:n + B, :G] = gt_classes
         gc[n:n + B, G:] = -1
         self._n = n + B
+
+    def _assign_ids(self, image_ids) -> None:
+        """Name the rows added so far (all of them without ids) after the fact: evaluate() learns its sampler's ids this way."""
+        ids = [int(i) for i in image_ids]
+        if self._ids is not None or len(ids) != self._n:
+            raise FdError(f"VOCEvaluator: {len(ids)} image ids for {self._n} rows, or the rows carry ids already")
+        if len(set(ids)) != len(ids):
+            raise FdError("VOCEvaluator: an image id added twice")
+        self._ids = ids
+
+    def gather(self, group=None, force: bool = False) -> "VOCEvaluator":
+        """The union of every rank's evaluator, as a new evaluator on this rank's device; every rank must call it, and every
+        rank gets the same rows.  With image ids: each distinct id once (of an id two ranks hold, the lowest rank's row), ids
+        ascending.  Without: every row, rank 0's first, in arrival order.  Two collectives (dist.gather_rows); num_cls, the
+        thresholds and the with / without ids choice travel in the first and a disagreement raises FdError on every rank.
+        No process group, or world size 1 without `force`: returns self."""
+        if _dist._no_group(group, force):
+            return self
+        dev = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        n = self._n
+        bufs = self._bufs if self._bufs is not None else self._alloc(0, 0, 0, dev)
+        ids = torch.tensor(self._ids if (n and self._ids is not None) else [0] * n, dtype=torch.int64).to(dev)
+        header = (self.num_cls, len(self.iou_thresholds), zlib.crc32(np.asarray(self.iou_thresholds, np.float64).tobytes()),
+                  -1 if n == 0 else int(self._ids is not None))
+        got, _, headers = _dist._gather_rows(list(bufs) + [ids], n, group, (0, 0, 0, 0, -1, 0), header)
+        out = VOCEvaluator(self.num_cls, self.iou_thresholds, device=dev)
+        all_ids = got.pop()
+        if int(headers[:, 3].max()) == 1:
+            order = _dist.merge_order(all_ids.cpu())
+            out._ids = all_ids.cpu()[order].tolist()
+            got = [t.index_select(0, order.to(dev)) for t in got]
+        if got[0].shape[0]:
+            out._bufs, out._n = tuple(got), got[0].shape[0]
+        return out
 
     def compute(self) -> Dict[str, np.ndarray]:
         """-> {"ap": [T, num_cls-1] f64 (labels 1 ..), "mAP": [T], "n_gt", "n_pred": [num_cls-1], "n_tp": [T, num_cls-1],
@@ -171,14 +232,23 @@ def eval_ap_2d(gt_boxes, gt_labels, pred_boxes, pred_labels, pred_scores, iou_th
     return {label: np.float64(ap[0, label]) for label in range(1, int(num_cls))}
 
 
-def evaluate(model: torch.nn.Module, val_data_loader, amp_enable: bool, ddp_enable: bool, devices, strides=None):
+def evaluate(model: torch.nn.Module, val_data_loader, amp_enable: bool, ddp_enable: bool, devices, strides=None, gather: bool = False):
     """The reference's evaluate (test.py:165-238): FCOSHead(0.05, 0.6, 1000, [8, 16, 32, 64]) -- four strides, reproducing the
     reference's dropped P7; `strides=` overrides -- then ClipBoxes, autocast flag, per-class / mAP / fps prints.
     Detections stay on the device (VOCEvaluator).  Every image of a batch is evaluated (the reference takes index 0 only; the
-    two agree at its batch size of 1).  Each rank evaluates what it saw: there is no cross-rank gather.
-    -> {"ap": {label: AP at IoU 0.5}, "mAP": float, "fps": float, "result": VOCEvaluator.compute()}."""
+    two agree at its batch size of 1).
+
+    gather=False: the result covers what this rank's loader yielded, and a call on one rank alone is fine; `ddp_enable` only
+    says that the printing rank is the process group's rank 0.  gather=True: EVERY rank must call; after the loop the ranks'
+    evaluators are merged (VOCEvaluator.gather: two collectives) and every rank computes the same, global, result, which rank 0
+    prints.  The images are named by list(val_data_loader.sampler) when the loader has a sampler that long -- what a
+    DistributedSampler gives, padding included, so an image two ranks were handed counts once and the merged order is the data
+    set's; otherwise the rows merge unnamed, in (rank, arrival) order.  Without a process group gather=True changes nothing.
+    -> {"ap": {label: AP at IoU 0.5}, "mAP": float, "fps": float (this rank's), "result": VOCEvaluator.compute(), "images":
+    distinct images evaluated, "world": ranks the result covers}."""
     model.eval()
-    local_rank = torch.distributed.get_rank() if ddp_enable else 0
+    grouped = gather and torch.distributed.is_available() and torch.distributed.is_initialized()
+    local_rank = torch.distributed.get_rank() if (ddp_enable or grouped) else 0
     head = FCOSHead(0.05, 0.6, 1000, list(strides) if strides is not None else [8, 16, 32, 64])
     clip = ClipBoxes()
     num_cls = len(VOC_CLASSES)
@@ -199,6 +269,13 @@ def evaluate(model: torch.nn.Module, val_data_loader, amp_enable: bool, ddp_enab
             inference_time += time.time() - start_time
         nb += 1
     fps = 1.0 / (inference_time / nb) if nb and inference_time > 0 else float("nan")
+    world = 1
+    if gather and not _dist._no_group(None, False):     # more than one rank: name the rows, merge
+        sampler = getattr(val_data_loader, "sampler", None)
+        if sampler is not None and hasattr(sampler, "__len__") and hasattr(sampler, "__iter__") and len(sampler) == ev.num_images:
+            ev._assign_ids(list(sampler))
+        ev = ev.gather()
+        world = torch.distributed.get_world_size()
     res = ev.compute()
     all_ap = {label: np.float64(res["ap"][0, label - 1]) for label in range(1, num_cls)}
     m_ap = float(res["mAP"][0])
@@ -207,4 +284,4 @@ def evaluate(model: torch.nn.Module, val_data_loader, amp_enable: bool, ddp_enab
         for key, value in all_ap.items():
             print(f'{VOC_CLASSES[int(key)]}: {value}')
         print(f'mAP: {m_ap:.3f}\n fps: {fps}')
-    return {"ap": all_ap, "mAP": m_ap, "fps": fps, "result": res}
+    return {"ap": all_ap, "mAP": m_ap, "fps": fps, "result": res, "images": ev.num_images, "world": world}
