@@ -794,6 +794,22 @@ int32_t fd_batchnorm_train_sync_bwd_nhwc(const float* x, int32_t x_cs, int32_t x
                                          float eps, int32_t act, int32_t phase, double* sums, double total_rows, const void* fwd_workspace, void* workspace,
                                          int64_t workspace_bytes, fd_stream_t stream);
 
+/* The residual form of the two forwards above (the ResNet bottleneck's output relu(bn3(conv3(y2)) + identity) in one apply pass):
+ *   y = act((x - mean) * rstd * gamma + beta + res),  act in {NONE, RELU}  (SILU: FD_E_UNSUPPORTED -- the backward takes its mask from y)
+ * `res` is a fourth fp32 channel view under the same view rules; one float4 of it is read per float4 of x.  The statistics are those of x alone, so the
+ * partition, the fp64 sums and their order, the statistics block, the running-statistics update, the workspace (fd_batchnorm_train_workspace_bytes /
+ * fd_batchnorm_train_sync_workspace_bytes) and every error code are the plain forms'; phase 1 of the synchronised form does not read res (it may be NULL) and
+ * writes exactly what the plain phase 1 writes.  y must not alias x or res.  There is no backward of its own: with g = dy * [y > 0] (fd_act_bwd_nhwc on the
+ * saved output; g = dy for act NONE), g is the residual's gradient and fd_batchnorm_train_bwd_nhwc / _sync_bwd_nhwc with act NONE on g give dx, dgamma, dbeta. */
+int32_t fd_batchnorm_train_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res, int32_t res_cs,
+                                        int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act,
+                                        float momentum, float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes,
+                                        fd_stream_t stream);
+int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
+                                             int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
+                                             int32_t act, int32_t phase, double* sums, double total_rows, float momentum, float* running_mean,
+                                             float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream);
+
 /* Drop-connect (stochastic depth) on [N][HW][C] fp32 channel views: y = a * s[n] + r, s = N floats on the device, r may be NULL; y may alias a.
  * Two roundings, like the torch expression a * s + r. */
 int32_t fd_sample_scale_add_nhwc(const float* a, int32_t a_cs, int32_t a_co, const float* s, const float* r, int32_t r_cs, int32_t r_co, float* y,

@@ -8,6 +8,9 @@
 // -- a function of (rows, C) alone.  Every sum is fp64: per thread over its rows in row order, the RT lanes in lane order (LDS), the chunks in index order by
 // a second launch (4 interleaved chunk lanes, added in lane order).  No atomics: two runs are bit-identical.  Statistics and apply are separate launches.
 //   forward    partial (sum x, sum x^2) -> final (mean, rstd, running statistics) -> apply y = act((x - mean) * rstd * gamma + beta)
+//              residual form (fd_batchnorm_train_res_fwd_nhwc, the ResNet bottleneck's output): apply y = act((x - mean) * rstd * gamma + beta + res), act in
+//              {NONE, RELU}; statistics of x alone, so everything but the apply launch is the plain form's.  Its backward is the plain one with act NONE on
+//              g = dy * [y > 0] (g is the residual's gradient too): no kernel of its own.
 //   backward   partial (sum dz, sum dz * xhat; dz = dy * act'(z), z recomputed from x exactly as the forward computed it) -> final (dgamma, dbeta and the two
 //              per-channel constants c1 = rstd * gamma * mean(dz), c2 = rstd * gamma * mean(dz * xhat)) -> apply dx = rstd * gamma * dz - c1 - xhat * c2
 // workspace (both directions, fd_batchnorm_train_workspace_bytes): double [2][C] then double [nchunk][2][C].  The forward leaves mean[C], rstd[C] in the first
@@ -42,7 +45,7 @@ __device__ __forceinline__ float bn_act_grad(float z, int act) {
     return 1.f;
 }
 
-struct BnArgs {
+struct BnArgs {                                         // (dy: the incoming gradient of the backward; the residual of the forward's residual form)
     const float* x; const float* dy; const float* gamma; const float* beta; float* out;
     int x_cs, x_co, dy_cs, dy_co, out_cs, out_co, C, QT, RT, act;
     long rows, rows_per;
@@ -158,8 +161,9 @@ __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const double* __restr
     bn_bwd_coef(c, C, A, B, count, gamma, stat, coef);
 }
 
-// forward: y = act(xhat * gamma + beta); backward: dx = rstd * gamma * dz - c1 - xhat * c2.  Same (tile, chunk) ownership as the partial kernel.
-template <bool BWD>
+// forward: y = act(xhat * gamma + beta), RES: y = act(xhat * gamma + beta + res), one float4 of res (a.dy) per float4 of x; backward: dx = rstd * gamma * dz
+// - c1 - xhat * c2.  Same (tile, chunk) ownership as the partial kernel.
+template <bool BWD, bool RES = false>
 __global__ __launch_bounds__(256) void bn_apply_kernel(BnArgs a, const double* __restrict__ stat, const double* __restrict__ coef) {
     const int tid = threadIdx.x, ql = tid % a.QT, rt = tid / a.QT;
     const int q = blockIdx.x * a.QT + ql, chunk = blockIdx.y;
@@ -185,6 +189,11 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BnArgs a, const double* _
                 const float dz = g[e] * bn_act_grad(xh * gm[e] + bt[e], a.act);
                 o[e] = (k1[e] * dz - c1[e]) - xh * c2[e];
             }
+        } else if constexpr (RES) {
+            const float4 u4 = *reinterpret_cast<const float4*>(a.dy + r * a.dy_cs + a.dy_co + 4 * q);
+            const float u[4] = {u4.x, u4.y, u4.z, u4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = fd_act1(((v[e] - mean[e]) * rstd[e] * gm[e] + bt[e]) + u[e], a.act, 0.f);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = fd_act1((v[e] - mean[e]) * rstd[e] * gm[e] + bt[e], a.act, 0.f);
@@ -201,23 +210,25 @@ extern "C" int64_t fd_batchnorm_train_workspace_bytes(int64_t rows, int32_t C) {
     return ((int64_t)2 * C + (int64_t)p.nchunk * 2 * C) * (int64_t)sizeof(double);
 }
 
-extern "C" int32_t fd_batchnorm_train_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
-                                               int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, float momentum, float* running_mean,
-                                               float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
-    FD_REQUIRE(bn_shape_ok(rows, C), FD_E_UNSUPPORTED, "fd_batchnorm_train_fwd: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 2 <= rows < 2^31)",
+// the plain forward and its residual form (RES: `res` is a fourth channel view, act in {NONE, RELU}); `who` names the entry point in the messages
+template <bool RES>
+static int32_t bn_train_fwd(const char* who, const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res, int32_t res_cs,
+                            int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, float momentum,
+                            float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    FD_REQUIRE(bn_shape_ok(rows, C), FD_E_UNSUPPORTED, "%s: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 2 <= rows < 2^31)", who,
                (long long)rows, C, BN_MAXC);
-    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || act == FD_ACT_SILU, FD_E_UNSUPPORTED, "fd_batchnorm_train_fwd: activation %d unsupported", act);
-    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && bn_view_ok(y, y_cs, y_co, C) && gamma && beta, FD_E_INVAL,
-               "fd_batchnorm_train_fwd: bad pointer / channel view (C=%d)", C);
-    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "fd_batchnorm_train_fwd: running_mean and running_var go together");
-    FD_REQUIRE(eps >= 0.f, FD_E_INVAL, "fd_batchnorm_train_fwd: eps must not be negative");
+    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || (!RES && act == FD_ACT_SILU), FD_E_UNSUPPORTED, "%s: activation %d unsupported", who, act);
+    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && bn_view_ok(y, y_cs, y_co, C) && gamma && beta && (!RES || bn_view_ok(res, res_cs, res_co, C)), FD_E_INVAL,
+               "%s: bad pointer / channel view (C=%d)", who, C);
+    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "%s: running_mean and running_var go together", who);
+    FD_REQUIRE(eps >= 0.f, FD_E_INVAL, "%s: eps must not be negative", who);
     const int64_t need = fd_batchnorm_train_workspace_bytes(rows, C);
     FD_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
-               "fd_batchnorm_train_fwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes, (long long)need);
+               "%s: workspace of %lld bytes, %lld needed (8-byte aligned)", who, (long long)workspace_bytes, (long long)need);
     const BnPart p = bn_partition(rows, C);
     BnArgs a;
-    a.x = x; a.dy = nullptr; a.gamma = gamma; a.beta = beta; a.out = y;
-    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = 0; a.dy_co = 0; a.out_cs = y_cs; a.out_co = y_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
+    a.x = x; a.dy = res; a.gamma = gamma; a.beta = beta; a.out = y;
+    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = res_cs; a.dy_co = res_co; a.out_cs = y_cs; a.out_co = y_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
     a.rows = (long)rows; a.rows_per = p.rows_per;
     double* stat = (double*)workspace;
     double* part = stat + 2 * (long)C;
@@ -227,9 +238,24 @@ extern "C" int32_t fd_batchnorm_train_fwd_nhwc(const float* x, int32_t x_cs, int
     hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)part, p.nchunk, C, (double)rows, eps, momentum, stat,
                        running_mean, running_var);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (statistics)");
-    hipLaunchKernelGGL((bn_apply_kernel<false>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, (const double*)nullptr);
+    hipLaunchKernelGGL((bn_apply_kernel<false, RES>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, (const double*)nullptr);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (apply)");
     return FD_OK;
+}
+
+extern "C" int32_t fd_batchnorm_train_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
+                                               int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, float momentum, float* running_mean,
+                                               float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    return bn_train_fwd<false>("fd_batchnorm_train_fwd", x, x_cs, x_co, gamma, beta, nullptr, 0, 0, y, y_cs, y_co, rows, C, eps, act, momentum, running_mean,
+                               running_var, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t fd_batchnorm_train_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
+                                                   int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
+                                                   int32_t act, float momentum, float* running_mean, float* running_var, void* workspace,
+                                                   int64_t workspace_bytes, fd_stream_t stream) {
+    return bn_train_fwd<true>("fd_batchnorm_train_res_fwd", x, x_cs, x_co, gamma, beta, res, res_cs, res_co, y, y_cs, y_co, rows, C, eps, act, momentum,
+                              running_mean, running_var, workspace, workspace_bytes, stream);
 }
 
 extern "C" int32_t fd_batchnorm_train_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
@@ -310,29 +336,32 @@ extern "C" int64_t fd_batchnorm_train_sync_workspace_bytes(int64_t rows, int32_t
     return ((int64_t)2 * C + (int64_t)p.nchunk * 2 * C) * (int64_t)sizeof(double);
 }
 
-extern "C" int32_t fd_batchnorm_train_sync_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
-                                                    int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums,
-                                                    double total_rows, float momentum, float* running_mean, float* running_var, void* workspace,
-                                                    int64_t workspace_bytes, fd_stream_t stream) {
+// the synchronised forward and its residual form (RES: phase 2 adds the `res` view before the activation, act in {NONE, RELU}; phase 1 never reads it)
+template <bool RES>
+static int32_t bn_train_sync_fwd(const char* who, const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
+                                 int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act,
+                                 int32_t phase, double* sums, double total_rows, float momentum, float* running_mean, float* running_var, void* workspace,
+                                 int64_t workspace_bytes, fd_stream_t stream) {
     FD_REQUIRE(bn_sync_shape_ok(rows, C), FD_E_UNSUPPORTED,
-               "fd_batchnorm_train_sync_fwd: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 1 <= rows < 2^31)", (long long)rows, C, BN_MAXC);
-    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || act == FD_ACT_SILU, FD_E_UNSUPPORTED, "fd_batchnorm_train_sync_fwd: activation %d unsupported", act);
-    FD_REQUIRE(phase == 1 || phase == 2, FD_E_UNSUPPORTED, "fd_batchnorm_train_sync_fwd: phase %d (1: this rank's sums, 2: statistics + apply)", phase);
+               "%s: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 1 <= rows < 2^31)", who, (long long)rows, C, BN_MAXC);
+    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || (!RES && act == FD_ACT_SILU), FD_E_UNSUPPORTED, "%s: activation %d unsupported", who, act);
+    FD_REQUIRE(phase == 1 || phase == 2, FD_E_UNSUPPORTED, "%s: phase %d (1: this rank's sums, 2: statistics + apply)", who, phase);
     FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && sums && ((uintptr_t)sums & 7) == 0, FD_E_INVAL,
-               "fd_batchnorm_train_sync_fwd: bad pointer / channel view (C=%d; sums: [2C + 1] doubles)", C);
-    FD_REQUIRE(phase == 1 || (bn_view_ok(y, y_cs, y_co, C) && gamma && beta), FD_E_INVAL, "fd_batchnorm_train_sync_fwd: phase 2 needs y, gamma and beta (C=%d)", C);
+               "%s: bad pointer / channel view (C=%d; sums: [2C + 1] doubles)", who, C);
+    FD_REQUIRE(phase == 1 || (bn_view_ok(y, y_cs, y_co, C) && gamma && beta && (!RES || bn_view_ok(res, res_cs, res_co, C))), FD_E_INVAL,
+               "%s: phase 2 needs y, gamma and beta%s (C=%d)", who, RES ? " and res" : "", C);
     FD_REQUIRE(bn_sync_count_ok(total_rows, rows), FD_E_INVAL,
-               "fd_batchnorm_train_sync_fwd: total_rows=%g: the global row count (>= this rank's %lld rows, >= 2), or -1: read from sums[2C] on the device",
+               "%s: total_rows=%g: the global row count (>= this rank's %lld rows, >= 2), or -1: read from sums[2C] on the device", who,
                total_rows, (long long)rows);
-    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "fd_batchnorm_train_sync_fwd: running_mean and running_var go together");
-    FD_REQUIRE(eps >= 0.f, FD_E_INVAL, "fd_batchnorm_train_sync_fwd: eps must not be negative");
+    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "%s: running_mean and running_var go together", who);
+    FD_REQUIRE(eps >= 0.f, FD_E_INVAL, "%s: eps must not be negative", who);
     const int64_t need = fd_batchnorm_train_sync_workspace_bytes(rows, C);
     FD_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
-               "fd_batchnorm_train_sync_fwd: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes, (long long)need);
+               "%s: workspace of %lld bytes, %lld needed (8-byte aligned)", who, (long long)workspace_bytes, (long long)need);
     const BnPart p = bn_partition(rows, C);
     BnArgs a;
-    a.x = x; a.dy = nullptr; a.gamma = gamma; a.beta = beta; a.out = y;
-    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = 0; a.dy_co = 0; a.out_cs = y_cs; a.out_co = y_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
+    a.x = x; a.dy = res; a.gamma = gamma; a.beta = beta; a.out = y;
+    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = res_cs; a.dy_co = res_co; a.out_cs = y_cs; a.out_co = y_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
     a.rows = (long)rows; a.rows_per = p.rows_per;
     double* stat = (double*)workspace;
     double* part = stat + 2 * (long)C;
@@ -347,9 +376,26 @@ extern "C" int32_t fd_batchnorm_train_sync_fwd_nhwc(const float* x, int32_t x_cs
     hipLaunchKernelGGL(bn_wide_sync_fwd_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const double*)sums, C, total_rows, eps, momentum, stat, running_mean,
                        running_var);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (statistics)");
-    hipLaunchKernelGGL((bn_apply_kernel<false>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, (const double*)nullptr);
+    hipLaunchKernelGGL((bn_apply_kernel<false, RES>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, (const double*)nullptr);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (apply)");
     return FD_OK;
+}
+
+extern "C" int32_t fd_batchnorm_train_sync_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
+                                                    int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums,
+                                                    double total_rows, float momentum, float* running_mean, float* running_var, void* workspace,
+                                                    int64_t workspace_bytes, fd_stream_t stream) {
+    return bn_train_sync_fwd<false>("fd_batchnorm_train_sync_fwd", x, x_cs, x_co, gamma, beta, nullptr, 0, 0, y, y_cs, y_co, rows, C, eps, act, phase, sums,
+                                    total_rows, momentum, running_mean, running_var, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
+                                                        int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C,
+                                                        float eps, int32_t act, int32_t phase, double* sums, double total_rows, float momentum,
+                                                        float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes,
+                                                        fd_stream_t stream) {
+    return bn_train_sync_fwd<true>("fd_batchnorm_train_sync_res_fwd", x, x_cs, x_co, gamma, beta, res, res_cs, res_co, y, y_cs, y_co, rows, C, eps, act, phase,
+                                   sums, total_rows, momentum, running_mean, running_var, workspace, workspace_bytes, stream);
 }
 
 extern "C" int32_t fd_batchnorm_train_sync_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co,

@@ -39,6 +39,7 @@ class _Trunk(nn.Module):
     """conv1, bn1, layer1..layer4 (no avgpool/fc: the fx feature extractor of the reference prunes them)."""
 
     hip_stem_train = False       # opt-in: a trainable stem on the HIP node (train_ops.stem_rows) instead of stock ops
+    hip_bn_train = False         # opt-in: bottlenecks whose BatchNorms are in training mode run on the batch-statistics HIP nodes instead of stock BatchNorm
 
     def __init__(self):
         super().__init__()
@@ -80,7 +81,8 @@ def trunk_train_forward(trunk: nn.Module, x: torch.Tensor):
     """Autograd-capable trunk forward (training only; inference runs the HIP plan).  Every bottleneck conv is one fused
     HIP launch (conv + frozen BN + residual + ReLU, train_ops.conv_bn_act) differentiated by the HIP data- / weight-
     gradient kernels; a frozen stem (freeze_stages(1)) runs on the inference kernels; a trainable one runs on train_ops.stem_rows (the stem kernel +
-    fd_stem7x7_bwd_weight_nhwc4) when `trunk.hip_stem_train` is set, else on stock ops.  Returns (C3, C4, C5)."""
+    fd_stem7x7_bwd_weight_nhwc4) when `trunk.hip_stem_train` is set, else on stock ops.  With `trunk.hip_bn_train` set, a block whose BatchNorms are in
+    training mode runs on the batch-statistics nodes (train_ops._bottleneck_bn_rows) instead of conv on HIP + stock BatchNorm.  Returns (C3, C4, C5)."""
     import torch.nn.functional as F
 
     from ...train_ops import bottleneck, stem_frozen, stem_is_frozen, stem_rows, stem_rows_ok
@@ -93,9 +95,11 @@ def trunk_train_forward(trunk: nn.Module, x: torch.Tensor):
         stock_fallback("a trainable / un-frozen 7x7 stem (Cin = 3)")
         x = F.max_pool2d(F.relu(trunk.bn1(trunk.conv1(x))), 3, 2, 1)
     feats = []
+    batch_stats = bool(getattr(trunk, "hip_bn_train", False))
     for li in (1, 2, 3, 4):
         for blk in getattr(trunk, f"layer{li}"):
-            x = bottleneck(blk, x)          # one autograd node per block (train_ops._BottleneckRows)
+            # frozen BatchNorm: one autograd node per block (train_ops._BottleneckRows); the switch adds the per-block choice of the batch-statistics path
+            x = bottleneck(blk, x, batch_stats=True) if batch_stats else bottleneck(blk, x)
         feats.append(x)
     return feats[1], feats[2], feats[3]
 
@@ -126,6 +130,15 @@ class ResNet50v2(nn.Module):
     def hip_stem_train(self, on: bool) -> None:
         self.extract_feature.hip_stem_train = bool(on)
 
+    @property
+    def hip_bn_train(self) -> bool:
+        """Opt-in (default False): BatchNorms in training mode run on the batch-statistics HIP nodes.  Lives on the trunk that trunk_train_forward sees."""
+        return self.extract_feature.hip_bn_train
+
+    @hip_bn_train.setter
+    def hip_bn_train(self, on: bool) -> None:
+        self.extract_feature.hip_bn_train = bool(on)
+
     forward = _no_torch_forward
     freeze_bn, freeze_stages = _freeze_bn, _freeze_stages
 
@@ -134,6 +147,7 @@ class ResNet50(nn.Module):
     """Reference model/backbone/resnet50.py:9-57 (FCOS baseline backbone): keys conv1, bn1, layer1..layer4."""
 
     hip_stem_train = False       # opt-in: a trainable stem on the HIP node (train_ops.stem_rows) instead of stock ops
+    hip_bn_train = False         # opt-in: BatchNorms in training mode on the batch-statistics HIP nodes (PlannedModule.enable_trunk_batch_stats)
 
     def __init__(self, re_layer: int = 1):
         super().__init__()

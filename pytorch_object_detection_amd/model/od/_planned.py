@@ -87,6 +87,23 @@ class PlannedModule(nn.Module):
                 for p in m.parameters():
                     p.requires_grad = False
 
+    def enable_trunk_batch_stats(self):
+        """Opt in to training the ResNet-50 trunk on BATCH statistics on the HIP nodes (backbone.trunk.hip_bn_train): every bottleneck whose BatchNorms are in
+        training mode runs conv -> batch-statistics BatchNorm -> ReLU on rows (train_ops.conv_norm_act_rows) and its output relu(bn3(conv3(.)) + identity) as
+        one residual apply pass (fd_batchnorm_train_res_fwd_nhwc), also as nn.SyncBatchNorm across ranks; frozen blocks keep their fused node.  Needs a model
+        whose constructor left the BatchNorms trainable (bn_freeze=False / freeze_bn=False).  Without this call such a model trains with the convs on HIP
+        and stock BatchNorm.  The sibling of enable_stem_training().  Returns self."""
+        if getattr(self, "efficientnet", False):
+            raise FdError("enable_trunk_batch_stats() is for the ResNet-50 trunk; FCOS(efficientnet=True) trains on batch statistics through "
+                          "enable_training(batch_stats=True)")
+        trunk = getattr(getattr(self, "backbone", None), "trunk", None)
+        if trunk is None or not all(hasattr(trunk, f"layer{i}") for i in (1, 2, 3, 4)):
+            raise FdError(f"enable_trunk_batch_stats(): {type(self).__name__} has no ResNet-50 trunk")
+        if getattr(self, "backbone_freeze", False):
+            raise FdError("enable_trunk_batch_stats() needs a model constructed with bn_freeze=False / freeze_bn=False (this one froze its BatchNorm layers)")
+        trunk.hip_bn_train = True
+        return self
+
     # ---- what a detector (backbone + FPN + head) supplies, and what it gets for it ----
     def _parts(self):
         """(the FPN module, its engine.build_*_fpn, the head's engine.build_*_head) of a detector; the head is `self.head`."""

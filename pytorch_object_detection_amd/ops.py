@@ -1666,6 +1666,33 @@ def batchnorm_train_fwd(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, y: Row
     return ws
 
 
+def _bn_res_check(who: str, x: Rows, res: Optional[Rows], act_id: int) -> None:
+    """The residual forms' own contract: act in {NONE, RELU} (the backward takes its mask from y) and an fp32 residual view of x's shape."""
+    if act_id not in (ACT_NONE, ACT_RELU):
+        raise FdError(f"{who}: act must be ACT_NONE or ACT_RELU (the backward takes its mask from the output)", rc=_lib.E_UNSUPPORTED)
+    if res is not None and (res.f16 or res.C != x.C or res.rows != x.rows):
+        raise FdError(f"{who}: the residual must be an fp32 view of x's shape")
+
+
+def batchnorm_train_res_fwd(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, res: Rows, y: Rows, eps: float, act_id: int = ACT_NONE,
+                            momentum: Optional[float] = None, running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
+                            ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = act(BatchNorm(x) + res) on the batch statistics of x (fd_batchnorm_train_res_fwd_nhwc), act in {NONE, RELU}: batchnorm_train_fwd with the residual
+    added in the apply pass.  y must not alias x or res.  Returns the workspace: batchnorm_train_bwd with ACT_NONE on the (ReLU-masked) gradient needs it."""
+    _need_gpu(x.buf, y.buf, res.buf, gamma, beta, running_mean, running_var, ws)
+    if x.f16 or y.f16 or x.C != y.C or x.rows != y.rows or gamma.numel() != x.C or beta.numel() != x.C:
+        raise FdError("batchnorm_train_res_fwd: fp32 views of the same shape and C-element gamma / beta expected")
+    _bn_res_check("batchnorm_train_res_fwd", x, res, act_id)
+    if ws is None:
+        ws = batchnorm_train_workspace(x.rows, x.C, x.buf.device)
+    upd = momentum is not None and running_mean is not None and running_var is not None
+    check(_lib.lib().fd_batchnorm_train_res_fwd_nhwc(x.ptr, x.cs, x.co, gamma.data_ptr(), beta.data_ptr(), res.ptr, res.cs, res.co, y.ptr, y.cs, y.co, x.rows,
+                                                     x.C, float(eps), act_id, float(momentum) if upd else 0.0, running_mean.data_ptr() if upd else None,
+                                                     running_var.data_ptr() if upd else None, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+          "fd_batchnorm_train_res_fwd_nhwc")
+    return ws
+
+
 def batchnorm_train_bwd(x: Rows, dy: Rows, gamma: torch.Tensor, beta: torch.Tensor, dx: Rows, eps: float, act_id: int, fwd_ws: torch.Tensor,
                         ws: Optional[torch.Tensor] = None):
     """The backward of batchnorm_train_fwd (fd_batchnorm_train_bwd_nhwc): writes dx, returns (dgamma, dbeta)."""
@@ -1713,6 +1740,32 @@ def batchnorm_train_sync_fwd(phase: int, x: Rows, sums: torch.Tensor, gamma: Opt
                                                       sums.data_ptr(), float(total_rows), float(momentum) if upd else 0.0,
                                                       running_mean.data_ptr() if upd else None, running_var.data_ptr() if upd else None, ws.data_ptr(),
                                                       ws.numel() * ws.element_size(), _stream()), f"fd_batchnorm_train_sync_fwd_nhwc (phase {phase})")
+    return ws
+
+
+def batchnorm_train_sync_res_fwd(phase: int, x: Rows, sums: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                                 res: Optional[Rows] = None, y: Optional[Rows] = None, eps: float = 1e-5, act_id: int = ACT_NONE, total_rows: float = -1.0,
+                                 momentum: Optional[float] = None, running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
+                                 ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One phase of batchnorm_train_sync_fwd's residual form (fd_batchnorm_train_sync_res_fwd_nhwc): phase 2 gives y = act(BatchNorm(x) + res), act in
+    {NONE, RELU}; phase 1 is the plain phase 1 and needs no `res`.  Everything else as batchnorm_train_sync_fwd."""
+    _need_gpu(x.buf, sums, gamma, beta, res.buf if res is not None else None, y.buf if y is not None else None, running_mean, running_var, ws)
+    if x.f16 or (y is not None and (y.f16 or y.C != x.C or y.rows != x.rows)) or any(t is not None and t.numel() != x.C for t in (gamma, beta)):
+        raise FdError("batchnorm_train_sync_res_fwd: fp32 views of the same shape and C-element gamma / beta expected")
+    _bn_res_check("batchnorm_train_sync_res_fwd", x, res, act_id)
+    if sums.dtype != torch.float64 or sums.numel() != 2 * x.C + 1 or not sums.is_contiguous():
+        raise FdError(f"batchnorm_train_sync_res_fwd: sums must be {2 * x.C + 1} contiguous float64 elements")
+    if ws is None:
+        ws = batchnorm_train_sync_workspace(x.rows, x.C, x.buf.device)
+    upd = momentum is not None and running_mean is not None and running_var is not None
+    check(_lib.lib().fd_batchnorm_train_sync_res_fwd_nhwc(x.ptr, x.cs, x.co, gamma.data_ptr() if gamma is not None else None,
+                                                          beta.data_ptr() if beta is not None else None, res.ptr if res is not None else None,
+                                                          res.cs if res is not None else 0, res.co if res is not None else 0,
+                                                          y.ptr if y is not None else None, y.cs if y is not None else 0, y.co if y is not None else 0,
+                                                          x.rows, x.C, float(eps), act_id, phase, sums.data_ptr(), float(total_rows),
+                                                          float(momentum) if upd else 0.0, running_mean.data_ptr() if upd else None,
+                                                          running_var.data_ptr() if upd else None, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+          f"fd_batchnorm_train_sync_res_fwd_nhwc (phase {phase})")
     return ws
 
 

@@ -18,11 +18,14 @@ over the whole pyramid exactly as at inference.
                             conv_rows' node is the GEMM over them; deformable_conv2d = the layer with its two side convs as one launch.
   groupnorm_rows            GroupNorm + ReLU / SiLU: fd_groupnorm_act_nhwc / fd_groupnorm_act_bwd_nhwc.
   stem_rows                 the trainable 7x7 stem (Cin = 3), opt-in (trunk.hip_stem_train): fd_stem7x7_nhwc4 forward, fd_stem7x7_bwd_weight_nhwc4 backward.
+  batchnorm_train_res_rows  act(bn(x) + res) on batch statistics, the output of a ResNet bottleneck: fd_batchnorm_train_res_fwd_nhwc forward (the add and the ReLU in the
+                            apply pass), ReLU-mask pass + fd_batchnorm_train_bwd_nhwc backward; bottleneck(blk, x, batch_stats=True) = the whole block with its
+                            BatchNorms in training mode, opt-in (trunk.hip_bn_train), nn.SyncBatchNorm across ranks included.
 
 What the kernels do not cover falls back to stock PyTorch-ROCm ops on the GPU: the data gradient of strided layers other than the
 parity-class geometries and of layers padded by more than dil * (k - 1) (the rungs of _dense_dgrad), a padding='same' that torch pads asymmetrically,
 dense layers with Cin % 32 != 0 (the 7x7 stem when it is trainable and its node is not switched on), BatchNorm in training mode or with trainable
-affine parameters, and SiLU after a BatchNorm (its derivative needs the pre-activation, which the fused epilogue does
+affine parameters behind a conv of the ResNet trunk while trunk.hip_bn_train is off (conv_bn_act: the conv on HIP, the statistics stock), and SiLU after a BatchNorm (its derivative needs the pre-activation, which the fused epilogue does
 not keep).  Narrow outputs (class / centre-ness / box logits) are padded to 32 channels by `conv_rows(pad_out=True)`.
 """
 from __future__ import annotations
@@ -572,18 +575,41 @@ class _BottleneckRows(torch.autograd.Function):
         return gx, gw1, gw2, gw3, gwd, None, None, None, None, None, None, None
 
 
-def bottleneck(blk: nn.Module, x: torch.Tensor) -> torch.Tensor:
+def _bottleneck_bn_rows(blk: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    """A bottleneck whose BatchNorms run on batch statistics (any of them may also be frozen), every layer a HIP node on rows: conv1/bn1/ReLU, conv2/bn2/ReLU
+    and the downsample conv/BN through conv_norm_act_rows' dispatch, then the raw conv3 and act(bn3(.) + identity) as one node (batchnorm_train_res_rows).
+    Across ranks the downsample BatchNorm's statistics all-reduce is issued before conv1 and waited for where the residual is needed."""
+    B, _, H, W = x.shape
+    ds, s = blk.downsample, blk.conv2.stride[0]
+    segs = Segs.make(B, [(H, W)])
+    so = ops.conv_out_segs(segs, 3, s, 1, 1)
+    xr = to_rows(x)
+    hd = conv_norm_begin(ds[0], ds[1], xr, segs, ACT_NONE) if ds is not None else None
+    y = conv_norm_act_rows(blk.conv1, blk.bn1, xr, segs, ACT_RELU)
+    y = conv_norm_act_rows(blk.conv2, blk.bn2, y, segs, ACT_RELU)
+    idt = xr if ds is None else conv_norm_finish(hd)
+    if bn_is_frozen(blk.bn3):
+        out = conv_rows(blk.conv3, y, so, blk.bn3, ACT_RELU, residual=idt.float())      # (fp32 maps on this path, whatever the block before stored)
+    else:
+        out = batchnorm_train_res_rows(blk.bn3, conv_rows(blk.conv3, y, so, None, ACT_NONE), idt, ACT_RELU)
+    return from_rows(out, B, so.H[0], so.W[0])
+
+
+def bottleneck(blk: nn.Module, x: torch.Tensor, batch_stats: bool = False) -> torch.Tensor:
     """torchvision-style Bottleneck (conv1/bn1, conv2/bn2, conv3/bn3, optional downsample) on an NCHW-shaped tensor: one
-    fused autograd node when every BatchNorm is frozen and the shapes are covered, else layer by layer (conv_bn_act)."""
+    fused autograd node when every BatchNorm is frozen and the shapes are covered, else layer by layer (conv_bn_act).  batch_stats (the trunk's opt-in
+    hip_bn_train): a covered block with BatchNorms in training mode runs on the batch-statistics nodes instead (_bottleneck_bn_rows)."""
     _need_cuda(x)
     ds = blk.downsample
     bns = [blk.bn1, blk.bn2, blk.bn3] + ([ds[1]] if ds is not None else [])
     convs = [blk.conv1, blk.conv2, blk.conv3] + ([ds[0]] if ds is not None else [])
-    ok = (not _STOCK and all(bn_is_frozen(b) for b in bns) and all(c.bias is None and _dense_ok(c, x) and c.out_channels % 32 == 0
-                                                                   for c in convs)
-          and blk.conv1.kernel_size == (1, 1) and blk.conv3.kernel_size == (1, 1) and blk.conv2.kernel_size == (3, 3)
-          and blk.conv2.padding == (1, 1) and blk.conv2.dilation == (1, 1) and blk.conv1.stride == (1, 1) and blk.conv3.stride == (1, 1)
-          and (ds is None or (ds[0].kernel_size == (1, 1) and ds[0].stride == blk.conv2.stride)))
+    shapes_ok = (not _STOCK and all(c.bias is None and _dense_ok(c, x) and c.out_channels % 32 == 0 for c in convs)
+                 and blk.conv1.kernel_size == (1, 1) and blk.conv3.kernel_size == (1, 1) and blk.conv2.kernel_size == (3, 3)
+                 and blk.conv2.padding == (1, 1) and blk.conv2.dilation == (1, 1) and blk.conv1.stride == (1, 1) and blk.conv3.stride == (1, 1)
+                 and (ds is None or (ds[0].kernel_size == (1, 1) and ds[0].stride == blk.conv2.stride)))
+    ok = shapes_ok and all(bn_is_frozen(b) for b in bns)
+    if batch_stats and shapes_ok and not ok and all(bn_is_frozen(b) or _bn_train_ok(b, x) or _bn_train_wide_ok(b, x) for b in bns):
+        return _bottleneck_bn_rows(blk, x)
     if not ok:
         idt = x if ds is None else conv_bn_act(ds[0], ds[1], x, ACT_NONE)
         y = conv_bn_act(blk.conv1, blk.bn1, x, ACT_RELU)
@@ -1197,11 +1223,61 @@ def syncbn_begin(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE, defer_back
     return h
 
 
-def syncbn_finish(h: "_SyncHandle") -> torch.Tensor:
+def syncbn_finish(h: "_SyncHandle", res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Phase 2.  res (wide handles, act NONE / ReLU): act(bn(x) + res) in the apply pass, the residual form."""
     bn = h.bn
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
+    if res is not None:
+        if not h.wide or h.defer:
+            raise FdError("syncbn_finish(res=...): the residual form exists for the any-width kernels (wide=True) without a deferred backward")
+        return _SyncBatchNormResApply.apply(h.x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, bn.momentum, bn.eps, h.act, h)
     return _SyncBatchNormApply.apply(h.x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, h.act, h)
+
+
+def _syncbn_backward(x, g, gm, bt, ws, buf, eps, act, group, defer, wide):
+    """The backward of a SyncBatchNorm node on the contiguous incoming gradient g: phase 1 (this rank's sums, dgamma, dbeta), the asynchronous all-reduce,
+    and phase 2 -- run here, or left pending for the consuming conv node when `defer`.  Returns (gx, dgamma, dbeta)."""
+    import ctypes as C
+    import torch.distributed as dist
+    rows, Cc = x.shape[0], gm.numel()
+    gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
+    dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    sums = torch.empty(2 * Cc + 1, dtype=torch.float64, device=x.device)       # [sum dz | sum dz * xhat | global row count]
+    if wide:
+        bws = ops.batchnorm_train_sync_bwd(1, Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, sums, ws, None, dgamma, dbeta, eps, act)
+    else:
+        segs = Segs.make(1, [(rows, 1)])
+        nb = _lib.lib().fd_groupnorm_bwd_workspace_bytes(C.byref(segs), Cc)
+        bws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
+        fn = _lib.lib().fd_batchnorm_sync_bwd_nhwc
+        ops.check(fn(x.data_ptr(), Cc, 0, g.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), None, 0, 0, dgamma.data_ptr(), dbeta.data_ptr(),
+                     rows, Cc, eps, act, 1, sums.data_ptr(), 0.0, ws.data_ptr(), bws.data_ptr(), ops._stream()), "fd_batchnorm_sync_bwd_nhwc (sums)")
+    sums[2 * Cc:].copy_(buf[2 * Cc:])                       # the forward's all-reduced row count, device to device (its own slot: not all-reduced again)
+    work = dist.all_reduce(sums[:2 * Cc], group=group, async_op=True)     # THE backward collective of this layer
+    at_issue = ops.LAUNCHES[0]
+
+    def finish(x=x, g=g, gm=gm, bt=bt, gx=gx, sums=sums, ws=ws, bws=bws, work=work):
+        SYNC_TRACE.append(("bwd", ops.LAUNCHES[0] - at_issue))
+        work.wait()
+        if wide:
+            ops.batchnorm_train_sync_bwd(2, Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, sums, ws, Rows(gx, 0, Cc), None, None, eps, act, -1.0, ws=bws)
+            return
+        ops.check(fn(x.data_ptr(), Cc, 0, g.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), gx.data_ptr(), Cc, 0, None, None,
+                     rows, Cc, eps, act, 2, sums.data_ptr(), C.c_double(-1.0), ws.data_ptr(), None, ops._stream()), "fd_batchnorm_sync_bwd_nhwc (apply)")
+
+    if defer:
+        # the ONLY consumer of gx is one of this module's conv nodes (conv_norm_begin built the chain): it finishes gx on entry (resolve_pending);
+        # the nodes autograd runs before it are enqueued under the collective.  flush_pending at the end of the pass is the safety net.
+        tid = _task_id()
+        for k in [k for k, e in _PENDING.items() if e[0] != tid]:      # leftovers of a pass that raised before its flush
+            del _PENDING[k]
+        torch.autograd.Variable._execution_engine.queue_callback(flush_pending)      # always: a stale entry must not suppress this pass's flush
+        _PENDING[gx.data_ptr()] = (tid, finish)
+    else:
+        finish()
+    return gx, dgamma, dbeta
 
 
 class _SyncBatchNormApply(torch.autograd.Function):
@@ -1235,48 +1311,8 @@ class _SyncBatchNormApply(torch.autograd.Function):
     @staticmethod
     @_bwd
     def backward(ctx, gy):
-        import ctypes as C
-        import torch.distributed as dist
         x, gm, bt, ws, buf = ctx.saved_tensors
-        eps, act, group, defer, wide = ctx.geom
-        rows, Cc = x.shape[0], gm.numel()
-        g = gy.contiguous()
-        gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
-        dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device)
-        sums = torch.empty(2 * Cc + 1, dtype=torch.float64, device=x.device)       # [sum dz | sum dz * xhat | global row count]
-        if wide:
-            bws = ops.batchnorm_train_sync_bwd(1, Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, sums, ws, None, dgamma, dbeta, eps, act)
-        else:
-            segs = Segs.make(1, [(rows, 1)])
-            nb = _lib.lib().fd_groupnorm_bwd_workspace_bytes(C.byref(segs), Cc)
-            bws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
-            fn = _lib.lib().fd_batchnorm_sync_bwd_nhwc
-            ops.check(fn(x.data_ptr(), Cc, 0, g.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), None, 0, 0, dgamma.data_ptr(), dbeta.data_ptr(),
-                         rows, Cc, eps, act, 1, sums.data_ptr(), 0.0, ws.data_ptr(), bws.data_ptr(), ops._stream()), "fd_batchnorm_sync_bwd_nhwc (sums)")
-        sums[2 * Cc:].copy_(buf[2 * Cc:])                       # the forward's all-reduced row count, device to device (its own slot: not all-reduced again)
-        work = dist.all_reduce(sums[:2 * Cc], group=group, async_op=True)     # THE backward collective of this layer
-        at_issue = ops.LAUNCHES[0]
-
-        def finish(x=x, g=g, gm=gm, bt=bt, gx=gx, sums=sums, ws=ws, bws=bws, work=work):
-            SYNC_TRACE.append(("bwd", ops.LAUNCHES[0] - at_issue))
-            work.wait()
-            if wide:
-                ops.batchnorm_train_sync_bwd(2, Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, sums, ws, Rows(gx, 0, Cc), None, None, eps, act, -1.0, ws=bws)
-                return
-            ops.check(fn(x.data_ptr(), Cc, 0, g.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), gx.data_ptr(), Cc, 0, None, None,
-                         rows, Cc, eps, act, 2, sums.data_ptr(), C.c_double(-1.0), ws.data_ptr(), None, ops._stream()), "fd_batchnorm_sync_bwd_nhwc (apply)")
-
-        if defer:
-            # the ONLY consumer of gx is one of this module's conv nodes (conv_norm_begin built the chain): it finishes gx on entry (resolve_pending);
-            # the nodes autograd runs before it are enqueued under the collective.  flush_pending at the end of the pass is the safety net.
-            tid = _task_id()
-            for k in [k for k, e in _PENDING.items() if e[0] != tid]:      # leftovers of a pass that raised before its flush
-                del _PENDING[k]
-            torch.autograd.Variable._execution_engine.queue_callback(flush_pending)      # always: a stale entry must not suppress this pass's flush
-            _PENDING[gx.data_ptr()] = (tid, finish)
-        else:
-            finish()
+        gx, dgamma, dbeta = _syncbn_backward(x, gy.contiguous(), gm, bt, ws, buf, *ctx.geom)
         return gx, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -1365,6 +1401,86 @@ def _bn_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) -> torch.
     if _is_sync(bn):
         return syncbn_finish(syncbn_begin(bn, x, act, wide=True))
     return batchnorm_train_wide_rows(bn, x, act)
+
+
+class _BatchNormResRows(torch.autograd.Function):
+    """act(bn(x) + res) with nn.BatchNorm2d in TRAINING mode, act NONE / ReLU, at any width C % 4 == 0 up to 4096 on [rows, C] maps: the output of a ResNet
+    bottleneck, relu(bn3(conv3(y2)) + identity), with the add and the ReLU in the apply pass (fd_batchnorm_train_res_fwd_nhwc).  Backward: g = gy * [y > 0]
+    (one mask pass over the saved output) is the residual's gradient AND the dz of a BatchNorm without activation, so fd_batchnorm_train_bwd_nhwc with ACT_NONE
+    on g gives dx, dgamma, dbeta.  fp32 under autocast, like the other normalisation nodes."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act):
+        x, res = x.contiguous(), res.contiguous()
+        y = torch.empty_like(x)
+        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
+        ws = ops.batchnorm_train_res_fwd(_r(x), gm, bt, _r(res), _r(y), eps, act, momentum, rmean, rvar)
+        ctx.save_for_backward(x, gm, bt, ws, y if act == ACT_RELU else None)
+        ctx.eps = eps
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        x, gm, bt, ws, y = ctx.saved_tensors
+        g = resolve_pending(gy).contiguous()
+        if y is not None:
+            g = relu_mask(g, y)
+        gx = torch.empty_like(x)
+        dgamma, dbeta = ops.batchnorm_train_bwd(_r(x), _r(g), gm, bt, _r(gx), ctx.eps, ACT_NONE, ws)
+        return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None
+
+
+class _SyncBatchNormResApply(torch.autograd.Function):
+    """_BatchNormResRows for an nn.SyncBatchNorm that spans ranks: the second half behind syncbn_begin(..., wide=True), whose phase 1 never reads the residual
+    (fd_batchnorm_train_sync_res_fwd_nhwc phase 2).  Backward: the mask pass, then _SyncBatchNormApply's backward with ACT_NONE."""
+
+    @staticmethod
+    @_fwd32
+    def forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act, h):
+        x, res = x.contiguous(), res.contiguous()
+        y = torch.empty_like(x)
+        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
+        SYNC_TRACE.append(("fwd", ops.LAUNCHES[0] - h.launches_at_issue))
+        h.work.wait()
+        ops.batchnorm_train_sync_res_fwd(2, _r(x), h.buf, gm, bt, _r(res), _r(y), eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
+        ctx.save_for_backward(x, gm, bt, h.ws, h.buf, y if act == ACT_RELU else None)
+        ctx.geom = (eps, h.group)
+        return y
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        x, gm, bt, ws, buf, y = ctx.saved_tensors
+        eps, group = ctx.geom
+        g = resolve_pending(gy).contiguous()
+        if y is not None:
+            g = relu_mask(g, y)
+        gx, dgamma, dbeta = _syncbn_backward(x, g, gm, bt, ws, buf, eps, ACT_NONE, group, False, True)
+        return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None, None
+
+
+def batchnorm_train_res_rows(bn: nn.Module, x: torch.Tensor, res: torch.Tensor, act: int = ACT_RELU) -> torch.Tensor:
+    """act(bn(x) + res) with batch statistics on [rows, C] maps, act NONE / ReLU, any width C % 4 == 0 up to 4096 (check with _bn_train_wide_ok): one-shot,
+    and for an nn.SyncBatchNorm spanning ranks through its synchronised form.  Gradients for x, gamma, beta and res; running statistics and
+    num_batches_tracked move like nn.BatchNorm2d's."""
+    Cc = getattr(bn, "num_features", 0)
+    if act not in (ACT_NONE, ACT_RELU):
+        raise FdError("batchnorm_train_res_rows differentiates ACT_NONE / ACT_RELU only (the backward takes its mask from the output)")
+    if not _bn_train_wide_ok(bn, x):
+        raise FdError(f"batchnorm_train_res_rows: {type(bn).__name__}({Cc}) must be a BatchNorm in training mode with affine parameters, running statistics "
+                      "and a momentum, C % 4 == 0, 4 <= C <= 4096, on floating-point rows")
+    if x.dim() != 2 or x.shape[1] != Cc or tuple(res.shape) != tuple(x.shape):
+        raise FdError(f"batchnorm_train_res_rows: BatchNorm({Cc}) on rows of shape {tuple(x.shape)} with a residual of shape {tuple(res.shape)}: "
+                      f"two [rows, {Cc}] maps expected")
+    if _is_sync(bn):
+        return syncbn_finish(syncbn_begin(bn, x, act, wide=True), res)
+    if x.shape[0] < 2:
+        raise FdError(f"batchnorm_train_res_rows: batch statistics need at least 2 rows (got {x.shape[0]})")
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return _BatchNormResRows.apply(x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act)
 
 
 class _SampleScaleAddRows(torch.autograd.Function):
@@ -1603,11 +1719,12 @@ class _StemRows(torch.autograd.Function):
 
 def stem_rows_ok(trunk: nn.Module, x: torch.Tensor) -> bool:
     """What stem_rows covers: the [64, 3, 7, 7] fp32 filter bank without bias, an fp32 image batch of even size that needs no gradient, and bn1 either
-    frozen or a BatchNorm in training mode that batchnorm_train_rows takes (not a SyncBatchNorm spanning ranks: that keeps the stock path)."""
+    frozen or a BatchNorm in training mode that batchnorm_train_rows takes (a SyncBatchNorm spanning ranks only with the trunk's hip_bn_train switch on:
+    without it that keeps the stock path)."""
     m, bn = trunk.conv1, trunk.bn1
     return (not _STOCK and tuple(m.weight.shape) == (64, 3, 7, 7) and m.bias is None and m.weight.dtype == torch.float32 and x.dtype == torch.float32
             and not x.requires_grad and x.dim() == 4 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.shape[2] >= 2 and x.shape[3] >= 2
-            and (bn_is_frozen(bn) or (_bn_train_ok(bn, x) and not _is_sync(bn))))
+            and (bn_is_frozen(bn) or (_bn_train_ok(bn, x) and (not _is_sync(bn) or getattr(trunk, "hip_bn_train", False)))))
 
 
 def stem_rows(trunk: nn.Module, x: torch.Tensor) -> torch.Tensor:
