@@ -75,10 +75,12 @@ __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs a) {
 //   2. one lane per location scans its row in LDS: L = max logit (compare-only), then sigmoid only for the classes whose
 //      computed sigmoid could tie with or exceed the computed sigmoid(L).  sigmoid is monotonic and fd_sigmoid good to a few
 //      ulp, so those are the logits within ~1e-6 (1 + e^L) of L: normally just the maximum itself (1 sigmoid per location
-//      instead of C); equal or nearly equal logits, or a saturating L, widen the set -- up to every class -- and the first
-//      maximal SIGMOID value wins exactly as in the plain kernel (torch.max semantics, head.py:61-62).
+//      instead of C); equal or nearly equal logits, a saturating L, or an L whose sigmoid underflows (L < DEC_SIG_MIN) widen
+//      the set -- up to every class -- and the first maximal SIGMOID value wins exactly as in the plain kernel (torch.max
+//      semantics, head.py:61-62).
 #define DEC_MAXQ 64
 #define DEC_LPW 16     /* locations per wave: 64 / DEC_LPW lanes share one location in the scan */
+#define DEC_SIG_MIN (-87.3f) /* below this largest logit fd_sigmoid's result is denormal or 0: no fast path (see `cut`) */
 __global__ __launch_bounds__(256) void decode_coalesced_kernel(DecodeArgs a) {
     extern __shared__ __attribute__((aligned(16))) char dec_smem[];
     const int Q = a.C >> 2, QP = Q | 1;             // row stride in float4 (odd: conflict-free ds_read_b128 across lanes)
@@ -175,8 +177,12 @@ __global__ __launch_bounds__(256) void decode_coalesced_kernel(DecodeArgs a) {
             if (take_other) { L = oL; li = oli; }
         }
         // classes whose COMPUTED sigmoid could reach the computed sigmoid(L): fd_sigmoid is good to a few ulp, so only logits
-        // within ~8 ulp(s) / s'(L) = 9.5e-7 (1 + e^L) of L (doubled below) -- just the maximum unless logits are (nearly) equal
-        const float cut = (L < 80.0f) ? L - 2.0e-6f * (1.0f + expf(L)) : -INFINITY;   // (e^L overflows: every class is a candidate)
+        // within ~8 ulp(s) / s'(L) = 9.5e-7 (1 + e^L) of L (doubled below) -- just the maximum unless logits are (nearly) equal.
+        // That bound counts ulps of a NORMAL sigmoid(L).  On gfx950 fd_sigmoid(v) is a normal float for v >= -87.33654f, a
+        // denormal down to v = -88.72283f and exactly 0 below (expf(-v) overflows): under DEC_SIG_MIN sigmoid(L) can no longer be
+        // told from its neighbours -- a row whose logits all underflow is C equal sigmoids, and the FIRST index wins, not the
+        // largest logit -- so every class is a candidate there, as it is where e^L overflows.
+        const float cut = (L >= DEC_SIG_MIN && L < 80.0f) ? L - 2.0e-6f * (1.0f + expf(L)) : -INFINITY;
         float best = -1.0f;
         int besti = 0;
         if (L2 < cut) {
