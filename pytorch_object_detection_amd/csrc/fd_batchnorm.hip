@@ -202,43 +202,101 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BnArgs a, const double* _
     }
 }
 
-static bool bn_shape_ok(int64_t rows, int32_t C) { return C >= 4 && C <= BN_MAXC && C % 4 == 0 && rows >= 2 && rows < (1LL << 31); }
+// a rank of the synchronised form may hold ONE row: only the global count must reach 2
+static bool bn_shape_ok(int64_t rows, int32_t C, int64_t min_rows) { return C >= 4 && C <= BN_MAXC && C % 4 == 0 && rows >= min_rows && rows < (1LL << 31); }
+// the global count: a host value >= this rank's rows (and >= 2), or <= 0 = "read sums[2C] on the device"
+static bool bn_sync_count_ok(double total_rows, int64_t rows) { return total_rows <= 0.0 || (total_rows >= (double)rows && total_rows >= 2.0); }
 
-extern "C" int64_t fd_batchnorm_train_workspace_bytes(int64_t rows, int32_t C) {
-    if (!bn_shape_ok(rows, C)) return -1;
+static int64_t bn_workspace_bytes(int64_t rows, int32_t C, int64_t min_rows) {
+    if (!bn_shape_ok(rows, C, min_rows)) return -1;
     const BnPart p = bn_partition(rows, C);
     return ((int64_t)2 * C + (int64_t)p.nchunk * 2 * C) * (int64_t)sizeof(double);
 }
 
-// the plain forward and its residual form (RES: `res` is a fourth channel view, act in {NONE, RELU}); `who` names the entry point in the messages
-template <bool RES>
-static int32_t bn_train_fwd(const char* who, const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res, int32_t res_cs,
-                            int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, float momentum,
-                            float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
-    FD_REQUIRE(bn_shape_ok(rows, C), FD_E_UNSUPPORTED, "%s: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 2 <= rows < 2^31)", who,
-               (long long)rows, C, BN_MAXC);
-    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || (!RES && act == FD_ACT_SILU), FD_E_UNSUPPORTED, "%s: activation %d unsupported", who, act);
-    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && bn_view_ok(y, y_cs, y_co, C) && gamma && beta && (!RES || bn_view_ok(res, res_cs, res_co, C)), FD_E_INVAL,
-               "%s: bad pointer / channel view (C=%d)", who, C);
-    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "%s: running_mean and running_var go together", who);
-    FD_REQUIRE(eps >= 0.f, FD_E_INVAL, "%s: eps must not be negative", who);
-    const int64_t need = fd_batchnorm_train_workspace_bytes(rows, C);
-    FD_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
-               "%s: workspace of %lld bytes, %lld needed (8-byte aligned)", who, (long long)workspace_bytes, (long long)need);
-    const BnPart p = bn_partition(rows, C);
+extern "C" int64_t fd_batchnorm_train_workspace_bytes(int64_t rows, int32_t C) { return bn_workspace_bytes(rows, C, 2); }
+extern "C" int64_t fd_batchnorm_train_sync_workspace_bytes(int64_t rows, int32_t C) { return bn_workspace_bytes(rows, C, 1); }
+
+// What every entry point below starts with: the argument checks, the partition, the kernels' arguments and the workspace split.  rc != FD_OK: rejected
+// (fd_last_error is set), nothing else is valid.  stat: mean[C], rstd[C] -- the head of the forward's own workspace, the forward's workspace in the backward.
+struct BnLaunch {
+    int32_t rc;
     BnArgs a;
-    a.x = x; a.dy = res; a.gamma = gamma; a.beta = beta; a.out = y;
-    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = res_cs; a.dy_co = res_co; a.out_cs = y_cs; a.out_co = y_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
-    a.rows = (long)rows; a.rows_per = p.rows_per;
-    double* stat = (double*)workspace;
-    double* part = stat + 2 * (long)C;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, part);
+    BnPart p;
+    const double* stat;
+    double* head;                                       // [2][C] in front of the workspace: the forward's statistics, the backward's c1, c2
+    double* part;                                       // [nchunk][2][C] behind it
+    hipStream_t st;
+};
+
+#define BN_REQUIRE(cond, code, ...)                                          \
+    do {                                                                     \
+        if (!(cond)) { fd_set_error(__VA_ARGS__); L.rc = (code); return L; } \
+    } while (0)
+
+// bwd: the backward (g = dy, out = dx; else out = y and g = the residual view of the residual form `res`, otherwise unused).  sync: one phase of the
+// synchronised form -- rows from 1, and a call needs only what its phase touches (phase 1: the sums, and dgamma / dbeta in the backward; phase 2: out, and
+// gamma / beta / res in the forward), where the unsynchronised call runs both halves and needs all of it.  `who` names the entry point in the messages.
+static BnLaunch bn_prologue(const char* who, bool bwd, bool sync, bool res, const float* x, int32_t x_cs, int32_t x_co, const float* g, int32_t g_cs,
+                            int32_t g_co, const float* gamma, const float* beta, float* out, int32_t out_cs, int32_t out_co, const float* dgamma,
+                            const float* dbeta, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, const double* sums, double total_rows,
+                            const float* running_mean, const float* running_var, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
+                            fd_stream_t stream) {
+    BnLaunch L;
+    L.rc = FD_OK;
+    BN_REQUIRE(bn_shape_ok(rows, C, sync ? 1 : 2), FD_E_UNSUPPORTED, "%s: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, %d <= rows < 2^31)", who,
+               (long long)rows, C, BN_MAXC, sync ? 1 : 2);
+    BN_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || (!res && act == FD_ACT_SILU), FD_E_UNSUPPORTED,
+               bwd ? "%s: activation %d has no backward" : "%s: activation %d unsupported", who, act);
+    BN_REQUIRE(!sync || phase == 1 || phase == 2, FD_E_UNSUPPORTED,
+               bwd ? "%s: phase %d (1: this rank's sums, dgamma, dbeta; 2: dx)" : "%s: phase %d (1: this rank's sums, 2: statistics + apply)", who, phase);
+    const bool first = !sync || phase == 1, second = !sync || phase == 2;
+    const bool in_ok = bn_view_ok(x, x_cs, x_co, C) && (!bwd || (bn_view_ok(g, g_cs, g_co, C) && gamma && beta));
+    const bool phase_ok = (!second || (bn_view_ok(out, out_cs, out_co, C) && gamma && beta && (!res || bn_view_ok(g, g_cs, g_co, C)))) &&
+                          (!(bwd && first) || (dgamma && dbeta));
+    if (!sync) {
+        BN_REQUIRE(in_ok && phase_ok, FD_E_INVAL, "%s: bad pointer / channel view (C=%d)", who, C);
+    } else {
+        BN_REQUIRE(in_ok && sums && ((uintptr_t)sums & 7) == 0, FD_E_INVAL, "%s: bad pointer / channel view (C=%d; sums: [2C + 1] doubles)", who, C);
+        if (bwd) BN_REQUIRE(phase_ok, FD_E_INVAL, "%s: phase 1 needs dgamma and dbeta, phase 2 needs dx (C=%d)", who, C);
+        else BN_REQUIRE(phase_ok, FD_E_INVAL, "%s: phase 2 needs y, gamma and beta%s (C=%d)", who, res ? " and res" : "", C);
+        BN_REQUIRE(bn_sync_count_ok(total_rows, rows), FD_E_INVAL,
+                   "%s: total_rows=%g: the global row count (>= this rank's %lld rows, >= 2), or -1: read from sums[2C] on the device", who, total_rows,
+                   (long long)rows);
+    }
+    const int64_t need = bn_workspace_bytes(rows, C, 1);
+    if (!bwd) {                                         // (the backward takes no running tensors, and its rstd comes from the forward's workspace)
+        BN_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "%s: running_mean and running_var go together", who);
+        BN_REQUIRE(eps >= 0.f, FD_E_INVAL, "%s: eps must not be negative", who);
+        BN_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
+                   "%s: workspace of %lld bytes, %lld needed (8-byte aligned)", who, (long long)workspace_bytes, (long long)need);
+    } else {
+        BN_REQUIRE(fwd_workspace && ((uintptr_t)fwd_workspace & 7) == 0 && workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need,
+                   FD_E_INVAL, "%s: the forward's workspace and a workspace of %lld bytes needed (got %lld; 8-byte aligned)", who, (long long)need,
+                   (long long)workspace_bytes);
+    }
+    L.p = bn_partition(rows, C);
+    BnArgs& a = L.a;
+    a.x = x; a.dy = g; a.gamma = gamma; a.beta = beta; a.out = out;
+    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = g_cs; a.dy_co = g_co; a.out_cs = out_cs; a.out_co = out_co; a.C = C; a.QT = L.p.QT; a.RT = L.p.RT; a.act = act;
+    a.rows = (long)rows; a.rows_per = L.p.rows_per;
+    L.head = (double*)workspace;
+    L.part = L.head + 2 * (long)C;
+    L.stat = bwd ? (const double*)fwd_workspace : L.head;
+    L.st = (hipStream_t)stream;
+    return L;
+}
+#undef BN_REQUIRE
+
+// the forward's launches; the residual form (`res` a fourth channel view, act in {NONE, RELU}) differs in the apply kernel alone
+static int32_t bn_fwd_launches(const BnLaunch& L, bool res, float eps, float momentum, float* running_mean, float* running_var) {
+    const int C = L.a.C;
+    hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (partial)");
-    hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)part, p.nchunk, C, (double)rows, eps, momentum, stat,
-                       running_mean, running_var);
+    hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, L.st, (const double*)L.part, L.p.nchunk, C, (double)L.a.rows, eps, momentum,
+                       L.head, running_mean, running_var);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (statistics)");
-    hipLaunchKernelGGL((bn_apply_kernel<false, RES>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, (const double*)nullptr);
+    if (!res) hipLaunchKernelGGL((bn_apply_kernel<false, false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
+    else hipLaunchKernelGGL((bn_apply_kernel<false, true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (apply)");
     return FD_OK;
 }
@@ -246,47 +304,33 @@ static int32_t bn_train_fwd(const char* who, const float* x, int32_t x_cs, int32
 extern "C" int32_t fd_batchnorm_train_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
                                                int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, float momentum, float* running_mean,
                                                float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
-    return bn_train_fwd<false>("fd_batchnorm_train_fwd", x, x_cs, x_co, gamma, beta, nullptr, 0, 0, y, y_cs, y_co, rows, C, eps, act, momentum, running_mean,
-                               running_var, workspace, workspace_bytes, stream);
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_fwd", false, false, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr, nullptr,
+                                   rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
+    return L.rc != FD_OK ? L.rc : bn_fwd_launches(L, false, eps, momentum, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
                                                    int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
                                                    int32_t act, float momentum, float* running_mean, float* running_var, void* workspace,
                                                    int64_t workspace_bytes, fd_stream_t stream) {
-    return bn_train_fwd<true>("fd_batchnorm_train_res_fwd", x, x_cs, x_co, gamma, beta, res, res_cs, res_co, y, y_cs, y_co, rows, C, eps, act, momentum,
-                              running_mean, running_var, workspace, workspace_bytes, stream);
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_res_fwd", false, false, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co, nullptr,
+                                   nullptr, rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
+    return L.rc != FD_OK ? L.rc : bn_fwd_launches(L, true, eps, momentum, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
                                                const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows,
                                                int32_t C, float eps, int32_t act, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
                                                fd_stream_t stream) {
-    (void)eps;                                          // (rstd comes from the forward's workspace)
-    FD_REQUIRE(bn_shape_ok(rows, C), FD_E_UNSUPPORTED, "fd_batchnorm_train_bwd: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 2 <= rows < 2^31)",
-               (long long)rows, C, BN_MAXC);
-    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || act == FD_ACT_SILU, FD_E_UNSUPPORTED, "fd_batchnorm_train_bwd: activation %d has no backward", act);
-    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && bn_view_ok(dy, dy_cs, dy_co, C) && bn_view_ok(dx, dx_cs, dx_co, C) && gamma && beta && dgamma && dbeta,
-               FD_E_INVAL, "fd_batchnorm_train_bwd: bad pointer / channel view (C=%d)", C);
-    const int64_t need = fd_batchnorm_train_workspace_bytes(rows, C);
-    FD_REQUIRE(fwd_workspace && ((uintptr_t)fwd_workspace & 7) == 0 && workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
-               "fd_batchnorm_train_bwd: the forward's workspace and a workspace of %lld bytes needed (got %lld; 8-byte aligned)", (long long)need,
-               (long long)workspace_bytes);
-    const BnPart p = bn_partition(rows, C);
-    BnArgs a;
-    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.out = dx;
-    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = dy_cs; a.dy_co = dy_co; a.out_cs = dx_cs; a.out_co = dx_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
-    a.rows = (long)rows; a.rows_per = p.rows_per;
-    const double* stat = (const double*)fwd_workspace;
-    double* coef = (double*)workspace;
-    double* part = coef + 2 * (long)C;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL((bn_partial_kernel<true>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, stat, part);
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_bwd", true, false, false, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta,
+                                   rows, C, eps, act, 0, nullptr, 0.0, nullptr, nullptr, fwd_workspace, workspace, workspace_bytes, stream);
+    if (L.rc != FD_OK) return L.rc;
+    hipLaunchKernelGGL((bn_partial_kernel<true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
     FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (partial)");
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)part, p.nchunk, C, (double)rows, gamma, stat, coef, dgamma,
-                       dbeta);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, L.st, (const double*)L.part, L.p.nchunk, C, (double)rows, gamma, L.stat, L.head,
+                       dgamma, dbeta);
     FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (sums)");
-    hipLaunchKernelGGL((bn_apply_kernel<true>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, stat, (const double*)coef);
+    hipLaunchKernelGGL((bn_apply_kernel<true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)L.head);
     FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (apply)");
     return FD_OK;
 }
@@ -325,58 +369,23 @@ __global__ __launch_bounds__(256) void bn_wide_sync_bwd_coef_kernel(const double
     bn_bwd_coef(c, C, sums[c], sums[C + c], count, gamma, stat, coef);
 }
 
-// a rank may hold ONE row: only the global count must reach 2
-static bool bn_sync_shape_ok(int64_t rows, int32_t C) { return C >= 4 && C <= BN_MAXC && C % 4 == 0 && rows >= 1 && rows < (1LL << 31); }
-// the global count: a host value >= this rank's rows (and >= 2), or <= 0 = "read sums[2C] on the device"
-static bool bn_sync_count_ok(double total_rows, int64_t rows) { return total_rows <= 0.0 || (total_rows >= (double)rows && total_rows >= 2.0); }
-
-extern "C" int64_t fd_batchnorm_train_sync_workspace_bytes(int64_t rows, int32_t C) {
-    if (!bn_sync_shape_ok(rows, C)) return -1;
-    const BnPart p = bn_partition(rows, C);
-    return ((int64_t)2 * C + (int64_t)p.nchunk * 2 * C) * (int64_t)sizeof(double);
-}
-
-// the synchronised forward and its residual form (RES: phase 2 adds the `res` view before the activation, act in {NONE, RELU}; phase 1 never reads it)
-template <bool RES>
-static int32_t bn_train_sync_fwd(const char* who, const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
-                                 int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act,
-                                 int32_t phase, double* sums, double total_rows, float momentum, float* running_mean, float* running_var, void* workspace,
-                                 int64_t workspace_bytes, fd_stream_t stream) {
-    FD_REQUIRE(bn_sync_shape_ok(rows, C), FD_E_UNSUPPORTED,
-               "%s: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 1 <= rows < 2^31)", who, (long long)rows, C, BN_MAXC);
-    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || (!RES && act == FD_ACT_SILU), FD_E_UNSUPPORTED, "%s: activation %d unsupported", who, act);
-    FD_REQUIRE(phase == 1 || phase == 2, FD_E_UNSUPPORTED, "%s: phase %d (1: this rank's sums, 2: statistics + apply)", who, phase);
-    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && sums && ((uintptr_t)sums & 7) == 0, FD_E_INVAL,
-               "%s: bad pointer / channel view (C=%d; sums: [2C + 1] doubles)", who, C);
-    FD_REQUIRE(phase == 1 || (bn_view_ok(y, y_cs, y_co, C) && gamma && beta && (!RES || bn_view_ok(res, res_cs, res_co, C))), FD_E_INVAL,
-               "%s: phase 2 needs y, gamma and beta%s (C=%d)", who, RES ? " and res" : "", C);
-    FD_REQUIRE(bn_sync_count_ok(total_rows, rows), FD_E_INVAL,
-               "%s: total_rows=%g: the global row count (>= this rank's %lld rows, >= 2), or -1: read from sums[2C] on the device", who,
-               total_rows, (long long)rows);
-    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "%s: running_mean and running_var go together", who);
-    FD_REQUIRE(eps >= 0.f, FD_E_INVAL, "%s: eps must not be negative", who);
-    const int64_t need = fd_batchnorm_train_sync_workspace_bytes(rows, C);
-    FD_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
-               "%s: workspace of %lld bytes, %lld needed (8-byte aligned)", who, (long long)workspace_bytes, (long long)need);
-    const BnPart p = bn_partition(rows, C);
-    BnArgs a;
-    a.x = x; a.dy = res; a.gamma = gamma; a.beta = beta; a.out = y;
-    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = res_cs; a.dy_co = res_co; a.out_cs = y_cs; a.out_co = y_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
-    a.rows = (long)rows; a.rows_per = p.rows_per;
-    double* stat = (double*)workspace;
-    double* part = stat + 2 * (long)C;
-    hipStream_t st = (hipStream_t)stream;
+// one phase of the synchronised forward; the residual form adds the `res` view in phase 2's apply kernel (act in {NONE, RELU}), phase 1 never reads it
+static int32_t bn_sync_fwd_launches(const BnLaunch& L, bool res, int32_t phase, double* sums, double total_rows, float eps, float momentum,
+                                    float* running_mean, float* running_var) {
+    const int C = L.a.C;
     if (phase == 1) {
-        hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, part);
+        hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
         FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (partial)");
-        hipLaunchKernelGGL(bn_wide_sync_sums_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)part, p.nchunk, C, sums, (float*)nullptr, (float*)nullptr);
+        hipLaunchKernelGGL(bn_wide_sync_sums_kernel, dim3((C + 63) / 64), dim3(256), 0, L.st, (const double*)L.part, L.p.nchunk, C, sums, (float*)nullptr,
+                           (float*)nullptr);
         FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (sums)");
         return FD_OK;
     }
-    hipLaunchKernelGGL(bn_wide_sync_fwd_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const double*)sums, C, total_rows, eps, momentum, stat, running_mean,
-                       running_var);
+    hipLaunchKernelGGL(bn_wide_sync_fwd_final_kernel, dim3((C + 255) / 256), dim3(256), 0, L.st, (const double*)sums, C, total_rows, eps, momentum, L.head,
+                       running_mean, running_var);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (statistics)");
-    hipLaunchKernelGGL((bn_apply_kernel<false, RES>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, (const double*)stat, (const double*)nullptr);
+    if (!res) hipLaunchKernelGGL((bn_apply_kernel<false, false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
+    else hipLaunchKernelGGL((bn_apply_kernel<false, true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (apply)");
     return FD_OK;
 }
@@ -385,8 +394,9 @@ extern "C" int32_t fd_batchnorm_train_sync_fwd_nhwc(const float* x, int32_t x_cs
                                                     int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums,
                                                     double total_rows, float momentum, float* running_mean, float* running_var, void* workspace,
                                                     int64_t workspace_bytes, fd_stream_t stream) {
-    return bn_train_sync_fwd<false>("fd_batchnorm_train_sync_fwd", x, x_cs, x_co, gamma, beta, nullptr, 0, 0, y, y_cs, y_co, rows, C, eps, act, phase, sums,
-                                    total_rows, momentum, running_mean, running_var, workspace, workspace_bytes, stream);
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_fwd", false, true, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr, nullptr,
+                                   rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
+    return L.rc != FD_OK ? L.rc : bn_sync_fwd_launches(L, false, phase, sums, total_rows, eps, momentum, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
@@ -394,49 +404,28 @@ extern "C" int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t 
                                                         float eps, int32_t act, int32_t phase, double* sums, double total_rows, float momentum,
                                                         float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes,
                                                         fd_stream_t stream) {
-    return bn_train_sync_fwd<true>("fd_batchnorm_train_sync_res_fwd", x, x_cs, x_co, gamma, beta, res, res_cs, res_co, y, y_cs, y_co, rows, C, eps, act, phase,
-                                   sums, total_rows, momentum, running_mean, running_var, workspace, workspace_bytes, stream);
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_res_fwd", false, true, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co, nullptr,
+                                   nullptr, rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
+    return L.rc != FD_OK ? L.rc : bn_sync_fwd_launches(L, true, phase, sums, total_rows, eps, momentum, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_sync_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co,
                                                     const float* gamma, const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta,
                                                     int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums, double total_rows,
                                                     const void* fwd_workspace, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
-    (void)eps;                                          // (rstd comes from the forward's workspace)
-    FD_REQUIRE(bn_sync_shape_ok(rows, C), FD_E_UNSUPPORTED,
-               "fd_batchnorm_train_sync_bwd: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, 1 <= rows < 2^31)", (long long)rows, C, BN_MAXC);
-    FD_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || act == FD_ACT_SILU, FD_E_UNSUPPORTED, "fd_batchnorm_train_sync_bwd: activation %d has no backward", act);
-    FD_REQUIRE(phase == 1 || phase == 2, FD_E_UNSUPPORTED, "fd_batchnorm_train_sync_bwd: phase %d (1: this rank's sums, dgamma, dbeta; 2: dx)", phase);
-    FD_REQUIRE(bn_view_ok(x, x_cs, x_co, C) && bn_view_ok(dy, dy_cs, dy_co, C) && gamma && beta && sums && ((uintptr_t)sums & 7) == 0, FD_E_INVAL,
-               "fd_batchnorm_train_sync_bwd: bad pointer / channel view (C=%d; sums: [2C + 1] doubles)", C);
-    FD_REQUIRE(phase == 1 ? (dgamma && dbeta) : bn_view_ok(dx, dx_cs, dx_co, C), FD_E_INVAL,
-               "fd_batchnorm_train_sync_bwd: phase 1 needs dgamma and dbeta, phase 2 needs dx (C=%d)", C);
-    FD_REQUIRE(bn_sync_count_ok(total_rows, rows), FD_E_INVAL,
-               "fd_batchnorm_train_sync_bwd: total_rows=%g: the global row count (>= this rank's %lld rows, >= 2), or -1: read from sums[2C] on the device",
-               total_rows, (long long)rows);
-    const int64_t need = fd_batchnorm_train_sync_workspace_bytes(rows, C);
-    FD_REQUIRE(fwd_workspace && ((uintptr_t)fwd_workspace & 7) == 0 && workspace && ((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, FD_E_INVAL,
-               "fd_batchnorm_train_sync_bwd: the forward's workspace and a workspace of %lld bytes needed (got %lld; 8-byte aligned)", (long long)need,
-               (long long)workspace_bytes);
-    const BnPart p = bn_partition(rows, C);
-    BnArgs a;
-    a.x = x; a.dy = dy; a.gamma = gamma; a.beta = beta; a.out = dx;
-    a.x_cs = x_cs; a.x_co = x_co; a.dy_cs = dy_cs; a.dy_co = dy_co; a.out_cs = dx_cs; a.out_co = dx_co; a.C = C; a.QT = p.QT; a.RT = p.RT; a.act = act;
-    a.rows = (long)rows; a.rows_per = p.rows_per;
-    const double* stat = (const double*)fwd_workspace;
-    double* coef = (double*)workspace;
-    double* part = coef + 2 * (long)C;
-    hipStream_t st = (hipStream_t)stream;
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_bwd", true, true, false, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta,
+                                   rows, C, eps, act, phase, sums, total_rows, nullptr, nullptr, fwd_workspace, workspace, workspace_bytes, stream);
+    if (L.rc != FD_OK) return L.rc;
     if (phase == 1) {
-        hipLaunchKernelGGL((bn_partial_kernel<true>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, stat, part);
+        hipLaunchKernelGGL((bn_partial_kernel<true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
         FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (partial)");
-        hipLaunchKernelGGL(bn_wide_sync_sums_kernel, dim3((C + 63) / 64), dim3(256), 0, st, (const double*)part, p.nchunk, C, sums, dgamma, dbeta);
+        hipLaunchKernelGGL(bn_wide_sync_sums_kernel, dim3((C + 63) / 64), dim3(256), 0, L.st, (const double*)L.part, L.p.nchunk, C, sums, dgamma, dbeta);
         FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (sums)");
         return FD_OK;
     }
-    hipLaunchKernelGGL(bn_wide_sync_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, (const double*)sums, C, total_rows, gamma, stat, coef);
+    hipLaunchKernelGGL(bn_wide_sync_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, L.st, (const double*)sums, C, total_rows, gamma, L.stat, L.head);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (coefficients)");
-    hipLaunchKernelGGL((bn_apply_kernel<true>), dim3(p.ntile, p.nchunk), dim3(256), 0, st, a, stat, (const double*)coef);
+    hipLaunchKernelGGL((bn_apply_kernel<true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)L.head);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (apply)");
     return FD_OK;
 }

@@ -1649,23 +1649,6 @@ def batchnorm_train_workspace(rows: int, Cc: int, device) -> torch.Tensor:
     return torch.empty(nb // 8, dtype=torch.float64, device=device)
 
 
-def batchnorm_train_fwd(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, y: Rows, eps: float, act_id: int = ACT_NONE, momentum: Optional[float] = None,
-                        running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = act(BatchNorm(x)) on the batch statistics of the fp32 channel view x (fd_batchnorm_train_fwd_nhwc: any C % 4 == 0 up to 4096).  With `momentum`
-    and the running tensors given they are updated in place like nn.BatchNorm2d's.  Returns the workspace batchnorm_train_bwd needs."""
-    _need_gpu(x.buf, y.buf, gamma, beta, running_mean, running_var, ws)
-    if x.f16 or y.f16 or x.C != y.C or x.rows != y.rows or gamma.numel() != x.C or beta.numel() != x.C:
-        raise FdError("batchnorm_train_fwd: fp32 views of the same shape and C-element gamma / beta expected")
-    if ws is None:
-        ws = batchnorm_train_workspace(x.rows, x.C, x.buf.device)
-    upd = momentum is not None and running_mean is not None and running_var is not None
-    check(_lib.lib().fd_batchnorm_train_fwd_nhwc(x.ptr, x.cs, x.co, gamma.data_ptr(), beta.data_ptr(), y.ptr, y.cs, y.co, x.rows, x.C, float(eps), act_id,
-                                                 float(momentum) if upd else 0.0, running_mean.data_ptr() if upd else None,
-                                                 running_var.data_ptr() if upd else None, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
-          "fd_batchnorm_train_fwd_nhwc")
-    return ws
-
-
 def _bn_res_check(who: str, x: Rows, res: Optional[Rows], act_id: int) -> None:
     """The residual forms' own contract: act in {NONE, RELU} (the backward takes its mask from y) and an fp32 residual view of x's shape."""
     if act_id not in (ACT_NONE, ACT_RELU):
@@ -1674,39 +1657,61 @@ def _bn_res_check(who: str, x: Rows, res: Optional[Rows], act_id: int) -> None:
         raise FdError(f"{who}: the residual must be an fp32 view of x's shape")
 
 
+def _bn_sums_check(who: str, sums: torch.Tensor, Cc: int) -> None:
+    if sums.dtype != torch.float64 or sums.numel() != 2 * Cc + 1 or not sums.is_contiguous():
+        raise FdError(f"{who}: sums must be {2 * Cc + 1} contiguous float64 elements")
+
+
+def _bn_running(momentum, running_mean, running_var) -> bool:
+    """The running statistics move when the momentum and both tensors are given."""
+    return momentum is not None and running_mean is not None and running_var is not None
+
+
+def _bn_running_args(momentum, running_mean, running_var):
+    if not _bn_running(momentum, running_mean, running_var):
+        return 0.0, None, None
+    return float(momentum), running_mean.data_ptr(), running_var.data_ptr()
+
+
+def _dptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _bn_train_fwd(who: str, res_form: bool, phase: Optional[int], x, sums, gamma, beta, res, y, eps, act_id, total_rows, momentum, running_mean, running_var,
+                  ws) -> torch.Tensor:
+    """The one body of the four any-width forward wrappers, fd_<who>_nhwc: phase None = the unsynchronised entry point (no phase, sums, total_rows
+    operands), res_form = the entry point that takes a residual view behind beta."""
+    _need_gpu(x.buf, sums, gamma, beta, res.buf if res is not None else None, y.buf if y is not None else None, running_mean, running_var, ws)
+    if x.f16 or (y is not None and (y.f16 or y.C != x.C or y.rows != x.rows)) or any(t is not None and t.numel() != x.C for t in (gamma, beta)):
+        raise FdError(f"{who}: fp32 views of the same shape and C-element gamma / beta expected")
+    if res_form:
+        _bn_res_check(who, x, res, act_id)
+    if phase is None:
+        sync, sym = (), f"fd_{who}_nhwc"
+    else:
+        _bn_sums_check(who, sums, x.C)
+        sync, sym = (phase, sums.data_ptr(), float(total_rows)), f"fd_{who}_nhwc (phase {phase})"
+    if ws is None:
+        ws = (batchnorm_train_workspace if phase is None else batchnorm_train_sync_workspace)(x.rows, x.C, x.buf.device)
+    check(getattr(_lib.lib(), f"fd_{who}_nhwc")(x.ptr, x.cs, x.co, _dptr(gamma), _dptr(beta), *(_view3(res) if res_form else ()), *_view3(y), x.rows, x.C,
+                                                float(eps), act_id, *sync, *_bn_running_args(momentum, running_mean, running_var), ws.data_ptr(),
+                                                ws.numel() * ws.element_size(), _stream()), sym)
+    return ws
+
+
+def batchnorm_train_fwd(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, y: Rows, eps: float, act_id: int = ACT_NONE, momentum: Optional[float] = None,
+                        running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = act(BatchNorm(x)) on the batch statistics of the fp32 channel view x (fd_batchnorm_train_fwd_nhwc: any C % 4 == 0 up to 4096).  With `momentum`
+    and the running tensors given they are updated in place like nn.BatchNorm2d's.  Returns the workspace batchnorm_train_bwd needs."""
+    return _bn_train_fwd("batchnorm_train_fwd", False, None, x, None, gamma, beta, None, y, eps, act_id, 0.0, momentum, running_mean, running_var, ws)
+
+
 def batchnorm_train_res_fwd(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, res: Rows, y: Rows, eps: float, act_id: int = ACT_NONE,
                             momentum: Optional[float] = None, running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
                             ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = act(BatchNorm(x) + res) on the batch statistics of x (fd_batchnorm_train_res_fwd_nhwc), act in {NONE, RELU}: batchnorm_train_fwd with the residual
     added in the apply pass.  y must not alias x or res.  Returns the workspace: batchnorm_train_bwd with ACT_NONE on the (ReLU-masked) gradient needs it."""
-    _need_gpu(x.buf, y.buf, res.buf, gamma, beta, running_mean, running_var, ws)
-    if x.f16 or y.f16 or x.C != y.C or x.rows != y.rows or gamma.numel() != x.C or beta.numel() != x.C:
-        raise FdError("batchnorm_train_res_fwd: fp32 views of the same shape and C-element gamma / beta expected")
-    _bn_res_check("batchnorm_train_res_fwd", x, res, act_id)
-    if ws is None:
-        ws = batchnorm_train_workspace(x.rows, x.C, x.buf.device)
-    upd = momentum is not None and running_mean is not None and running_var is not None
-    check(_lib.lib().fd_batchnorm_train_res_fwd_nhwc(x.ptr, x.cs, x.co, gamma.data_ptr(), beta.data_ptr(), res.ptr, res.cs, res.co, y.ptr, y.cs, y.co, x.rows,
-                                                     x.C, float(eps), act_id, float(momentum) if upd else 0.0, running_mean.data_ptr() if upd else None,
-                                                     running_var.data_ptr() if upd else None, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
-          "fd_batchnorm_train_res_fwd_nhwc")
-    return ws
-
-
-def batchnorm_train_bwd(x: Rows, dy: Rows, gamma: torch.Tensor, beta: torch.Tensor, dx: Rows, eps: float, act_id: int, fwd_ws: torch.Tensor,
-                        ws: Optional[torch.Tensor] = None):
-    """The backward of batchnorm_train_fwd (fd_batchnorm_train_bwd_nhwc): writes dx, returns (dgamma, dbeta)."""
-    _need_gpu(x.buf, dy.buf, dx.buf, gamma, beta, fwd_ws, ws)
-    if x.f16 or dy.f16 or dx.f16 or not (x.C == dy.C == dx.C) or not (x.rows == dy.rows == dx.rows):
-        raise FdError("batchnorm_train_bwd: fp32 views of the same shape expected")
-    if ws is None:
-        ws = batchnorm_train_workspace(x.rows, x.C, x.buf.device)
-    dgamma = torch.empty(x.C, dtype=torch.float32, device=x.buf.device)
-    dbeta = torch.empty(x.C, dtype=torch.float32, device=x.buf.device)
-    check(_lib.lib().fd_batchnorm_train_bwd_nhwc(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gamma.data_ptr(), beta.data_ptr(), dx.ptr, dx.cs, dx.co,
-                                                 dgamma.data_ptr(), dbeta.data_ptr(), x.rows, x.C, float(eps), act_id, fwd_ws.data_ptr(), ws.data_ptr(),
-                                                 ws.numel() * ws.element_size(), _stream()), "fd_batchnorm_train_bwd_nhwc")
-    return dgamma, dbeta
+    return _bn_train_fwd("batchnorm_train_res_fwd", True, None, x, None, gamma, beta, res, y, eps, act_id, 0.0, momentum, running_mean, running_var, ws)
 
 
 def batchnorm_train_sync_workspace(rows: int, Cc: int, device) -> torch.Tensor:
@@ -1717,7 +1722,6 @@ def batchnorm_train_sync_workspace(rows: int, Cc: int, device) -> torch.Tensor:
                       "1 <= rows < 2^31", rc=_lib.E_UNSUPPORTED)
     return torch.empty(nb // 8, dtype=torch.float64, device=device)
 
-
 def batchnorm_train_sync_fwd(phase: int, x: Rows, sums: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
                              y: Optional[Rows] = None, eps: float = 1e-5, act_id: int = ACT_NONE, total_rows: float = -1.0, momentum: Optional[float] = None,
                              running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
@@ -1726,21 +1730,8 @@ def batchnorm_train_sync_fwd(phase: int, x: Rows, sums: torch.Tensor, gamma: Opt
     [2C + 1] float64; the caller puts its row count in sums[2C] and all-reduces); phase 2 normalises x into y with the global statistics, `total_rows` the
     global count or -1 = sums[2C] on the device, and updates the running tensors when `momentum` and both are given.  Returns the workspace: hand phase 1's
     to phase 2, and phase 2's to batchnorm_train_sync_bwd."""
-    _need_gpu(x.buf, sums, gamma, beta, y.buf if y is not None else None, running_mean, running_var, ws)
-    if x.f16 or (y is not None and (y.f16 or y.C != x.C or y.rows != x.rows)) or any(t is not None and t.numel() != x.C for t in (gamma, beta)):
-        raise FdError("batchnorm_train_sync_fwd: fp32 views of the same shape and C-element gamma / beta expected")
-    if sums.dtype != torch.float64 or sums.numel() != 2 * x.C + 1 or not sums.is_contiguous():
-        raise FdError(f"batchnorm_train_sync_fwd: sums must be {2 * x.C + 1} contiguous float64 elements")
-    if ws is None:
-        ws = batchnorm_train_sync_workspace(x.rows, x.C, x.buf.device)
-    upd = momentum is not None and running_mean is not None and running_var is not None
-    check(_lib.lib().fd_batchnorm_train_sync_fwd_nhwc(x.ptr, x.cs, x.co, gamma.data_ptr() if gamma is not None else None,
-                                                      beta.data_ptr() if beta is not None else None, y.ptr if y is not None else None,
-                                                      y.cs if y is not None else 0, y.co if y is not None else 0, x.rows, x.C, float(eps), act_id, phase,
-                                                      sums.data_ptr(), float(total_rows), float(momentum) if upd else 0.0,
-                                                      running_mean.data_ptr() if upd else None, running_var.data_ptr() if upd else None, ws.data_ptr(),
-                                                      ws.numel() * ws.element_size(), _stream()), f"fd_batchnorm_train_sync_fwd_nhwc (phase {phase})")
-    return ws
+    return _bn_train_fwd("batchnorm_train_sync_fwd", False, phase, x, sums, gamma, beta, None, y, eps, act_id, total_rows, momentum, running_mean, running_var,
+                         ws)
 
 
 def batchnorm_train_sync_res_fwd(phase: int, x: Rows, sums: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
@@ -1749,24 +1740,35 @@ def batchnorm_train_sync_res_fwd(phase: int, x: Rows, sums: torch.Tensor, gamma:
                                  ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One phase of batchnorm_train_sync_fwd's residual form (fd_batchnorm_train_sync_res_fwd_nhwc): phase 2 gives y = act(BatchNorm(x) + res), act in
     {NONE, RELU}; phase 1 is the plain phase 1 and needs no `res`.  Everything else as batchnorm_train_sync_fwd."""
-    _need_gpu(x.buf, sums, gamma, beta, res.buf if res is not None else None, y.buf if y is not None else None, running_mean, running_var, ws)
-    if x.f16 or (y is not None and (y.f16 or y.C != x.C or y.rows != x.rows)) or any(t is not None and t.numel() != x.C for t in (gamma, beta)):
-        raise FdError("batchnorm_train_sync_res_fwd: fp32 views of the same shape and C-element gamma / beta expected")
-    _bn_res_check("batchnorm_train_sync_res_fwd", x, res, act_id)
-    if sums.dtype != torch.float64 or sums.numel() != 2 * x.C + 1 or not sums.is_contiguous():
-        raise FdError(f"batchnorm_train_sync_res_fwd: sums must be {2 * x.C + 1} contiguous float64 elements")
+    return _bn_train_fwd("batchnorm_train_sync_res_fwd", True, phase, x, sums, gamma, beta, res, y, eps, act_id, total_rows, momentum, running_mean,
+                         running_var, ws)
+
+
+def _bn_train_bwd(who: str, phase: Optional[int], x, dy, gamma, beta, sums, fwd_ws, dx, dgamma, dbeta, eps, act_id, total_rows, ws) -> torch.Tensor:
+    """The one body of the two any-width backward wrappers, fd_<who>_nhwc (phase None: the unsynchronised entry point)."""
+    _need_gpu(x.buf, dy.buf, dx.buf if dx is not None else None, gamma, beta, sums, fwd_ws, dgamma, dbeta, ws)
+    if x.f16 or dy.f16 or x.C != dy.C or x.rows != dy.rows or (dx is not None and (dx.f16 or dx.C != x.C or dx.rows != x.rows)):
+        raise FdError(f"{who}: fp32 views of the same shape expected")
+    if phase is None:
+        sync, sym = (), f"fd_{who}_nhwc"
+    else:
+        _bn_sums_check(who, sums, x.C)
+        sync, sym = (phase, sums.data_ptr(), float(total_rows)), f"fd_{who}_nhwc (phase {phase})"
     if ws is None:
-        ws = batchnorm_train_sync_workspace(x.rows, x.C, x.buf.device)
-    upd = momentum is not None and running_mean is not None and running_var is not None
-    check(_lib.lib().fd_batchnorm_train_sync_res_fwd_nhwc(x.ptr, x.cs, x.co, gamma.data_ptr() if gamma is not None else None,
-                                                          beta.data_ptr() if beta is not None else None, res.ptr if res is not None else None,
-                                                          res.cs if res is not None else 0, res.co if res is not None else 0,
-                                                          y.ptr if y is not None else None, y.cs if y is not None else 0, y.co if y is not None else 0,
-                                                          x.rows, x.C, float(eps), act_id, phase, sums.data_ptr(), float(total_rows),
-                                                          float(momentum) if upd else 0.0, running_mean.data_ptr() if upd else None,
-                                                          running_var.data_ptr() if upd else None, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
-          f"fd_batchnorm_train_sync_res_fwd_nhwc (phase {phase})")
+        ws = (batchnorm_train_workspace if phase is None else batchnorm_train_sync_workspace)(x.rows, x.C, x.buf.device)
+    check(getattr(_lib.lib(), f"fd_{who}_nhwc")(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gamma.data_ptr(), beta.data_ptr(), *_view3(dx), _dptr(dgamma),
+                                                _dptr(dbeta), x.rows, x.C, float(eps), act_id, *sync, fwd_ws.data_ptr(), ws.data_ptr(),
+                                                ws.numel() * ws.element_size(), _stream()), sym)
     return ws
+
+
+def batchnorm_train_bwd(x: Rows, dy: Rows, gamma: torch.Tensor, beta: torch.Tensor, dx: Rows, eps: float, act_id: int, fwd_ws: torch.Tensor,
+                        ws: Optional[torch.Tensor] = None):
+    """The backward of batchnorm_train_fwd (fd_batchnorm_train_bwd_nhwc): writes dx, returns (dgamma, dbeta)."""
+    dgamma = torch.empty(x.C, dtype=torch.float32, device=x.buf.device)
+    dbeta = torch.empty(x.C, dtype=torch.float32, device=x.buf.device)
+    _bn_train_bwd("batchnorm_train_bwd", None, x, dy, gamma, beta, None, fwd_ws, dx, dgamma, dbeta, eps, act_id, 0.0, ws)
+    return dgamma, dbeta
 
 
 def batchnorm_train_sync_bwd(phase: int, x: Rows, dy: Rows, gamma: torch.Tensor, beta: torch.Tensor, sums: torch.Tensor, fwd_ws: torch.Tensor,
@@ -1775,19 +1777,46 @@ def batchnorm_train_sync_bwd(phase: int, x: Rows, dy: Rows, gamma: torch.Tensor,
     """One phase of SyncBatchNorm's backward at any width (fd_batchnorm_train_sync_bwd_nhwc).  Phase 1 writes this rank's sum dz, sum dz * xhat to sums[:2C]
     and dgamma / dbeta (from those local sums); the caller all-reduces sums[:2C]; phase 2 writes dx, `total_rows` as in the forward.  fwd_ws: the forward's
     phase-2 workspace.  Returns the workspace: hand phase 1's to phase 2."""
+    return _bn_train_bwd("batchnorm_train_sync_bwd", phase, x, dy, gamma, beta, sums, fwd_ws, dx, dgamma, dbeta, eps, act_id, total_rows, ws)
+
+
+def batchnorm_sync_fwd(phase: int, x: Rows, sums: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+                       y: Optional[Rows] = None, eps: float = 1e-5, act_id: int = ACT_NONE, total_rows: float = -1.0, momentum: Optional[float] = None,
+                       running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """batchnorm_train_sync_fwd on the narrow kernel family (fd_batchnorm_sync_fwd_nhwc, the GroupNorm route: C / 4 divides 256, C <= 1024), same parameters
+    and protocol.  `sums` is [2C + 1] float64 and OPAQUE to the caller, who only fills sums[2C] with the row count and all-reduces: the forward's sums lie
+    interleaved here (sum x, sum x^2 per channel) and planar in the any-width family.  The workspace is a groupnorm_workspace of one image of rows x 1 pixels
+    with G = C; phase 2 with `momentum` and both running tensors enqueues fd_batchnorm_update_running_dev on sums[2C:] behind the apply launch."""
+    _need_gpu(x.buf, sums, gamma, beta, y.buf if y is not None else None, running_mean, running_var, ws)
+    if x.f16 or (y is not None and (y.f16 or y.C != x.C or y.rows != x.rows)) or any(t is not None and t.numel() != x.C for t in (gamma, beta)):
+        raise FdError("batchnorm_sync_fwd: fp32 views of the same shape and C-element gamma / beta expected")
+    _bn_sums_check("batchnorm_sync_fwd", sums, x.C)
+    if ws is None:
+        ws = groupnorm_workspace(Segs.make(1, [(x.rows, 1)]), x.C, x.buf.device)
+    check(_lib.lib().fd_batchnorm_sync_fwd_nhwc(x.ptr, x.cs, x.co, _dptr(gamma), _dptr(beta), *_view3(y), x.rows, x.C, float(eps), act_id, phase,
+                                                sums.data_ptr(), float(total_rows), ws.data_ptr(), _stream()), f"fd_batchnorm_sync_fwd_nhwc (phase {phase})")
+    if phase == 2 and _bn_running(momentum, running_mean, running_var):
+        batchnorm_update_running_dev(ws, sums[2 * x.C:], x.C, momentum, eps, running_mean, running_var)
+    return ws
+
+
+def batchnorm_sync_bwd(phase: int, x: Rows, dy: Rows, gamma: torch.Tensor, beta: torch.Tensor, sums: torch.Tensor, fwd_ws: torch.Tensor,
+                       dx: Optional[Rows] = None, dgamma: Optional[torch.Tensor] = None, dbeta: Optional[torch.Tensor] = None, eps: float = 1e-5,
+                       act_id: int = ACT_NONE, total_rows: float = -1.0, ws: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """batchnorm_train_sync_bwd on the narrow kernel family (fd_batchnorm_sync_bwd_nhwc), same parameters and protocol; `sums` as in batchnorm_sync_fwd.
+    The workspace is fd_groupnorm_bwd_workspace_bytes of the forward's segment table: phase 1 allocates it when none is given, phase 2 reads none."""
     _need_gpu(x.buf, dy.buf, dx.buf if dx is not None else None, gamma, beta, sums, fwd_ws, dgamma, dbeta, ws)
     if x.f16 or dy.f16 or x.C != dy.C or x.rows != dy.rows or (dx is not None and (dx.f16 or dx.C != x.C or dx.rows != x.rows)):
-        raise FdError("batchnorm_train_sync_bwd: fp32 views of the same shape expected")
-    if sums.dtype != torch.float64 or sums.numel() != 2 * x.C + 1 or not sums.is_contiguous():
-        raise FdError(f"batchnorm_train_sync_bwd: sums must be {2 * x.C + 1} contiguous float64 elements")
-    if ws is None:
-        ws = batchnorm_train_sync_workspace(x.rows, x.C, x.buf.device)
-    check(_lib.lib().fd_batchnorm_train_sync_bwd_nhwc(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gamma.data_ptr(), beta.data_ptr(),
-                                                      dx.ptr if dx is not None else None, dx.cs if dx is not None else 0, dx.co if dx is not None else 0,
-                                                      dgamma.data_ptr() if dgamma is not None else None, dbeta.data_ptr() if dbeta is not None else None,
-                                                      x.rows, x.C, float(eps), act_id, phase, sums.data_ptr(), float(total_rows), fwd_ws.data_ptr(),
-                                                      ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
-          f"fd_batchnorm_train_sync_bwd_nhwc (phase {phase})")
+        raise FdError("batchnorm_sync_bwd: fp32 views of the same shape expected")
+    _bn_sums_check("batchnorm_sync_bwd", sums, x.C)
+    if ws is None and phase == 1:
+        nb = _lib.lib().fd_groupnorm_bwd_workspace_bytes(C.byref(Segs.make(1, [(x.rows, 1)])), x.C)
+        if nb < 0:
+            raise FdError("fd_groupnorm_bwd_workspace_bytes: bad arguments")
+        ws = torch.empty(nb // 8, dtype=torch.float64, device=x.buf.device)
+    check(_lib.lib().fd_batchnorm_sync_bwd_nhwc(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gamma.data_ptr(), beta.data_ptr(), *_view3(dx), _dptr(dgamma),
+                                                _dptr(dbeta), x.rows, x.C, float(eps), act_id, phase, sums.data_ptr(), float(total_rows), fwd_ws.data_ptr(),
+                                                _dptr(ws), _stream()), f"fd_batchnorm_sync_bwd_nhwc (phase {phase})")
     return ws
 
 

@@ -608,7 +608,7 @@ def bottleneck(blk: nn.Module, x: torch.Tensor, batch_stats: bool = False) -> to
                  and blk.conv2.padding == (1, 1) and blk.conv2.dilation == (1, 1) and blk.conv1.stride == (1, 1) and blk.conv3.stride == (1, 1)
                  and (ds is None or (ds[0].kernel_size == (1, 1) and ds[0].stride == blk.conv2.stride)))
     ok = shapes_ok and all(bn_is_frozen(b) for b in bns)
-    if batch_stats and shapes_ok and not ok and all(bn_is_frozen(b) or _bn_train_ok(b, x) or _bn_train_wide_ok(b, x) for b in bns):
+    if batch_stats and shapes_ok and not ok and all(bn_is_frozen(b) or _bn_family(b, x) is not None for b in bns):
         return _bottleneck_bn_rows(blk, x)
     if not ok:
         idt = x if ds is None else conv_bn_act(ds[0], ds[1], x, ACT_NONE)
@@ -1188,34 +1188,32 @@ def flush_pending() -> None:
 
 
 class _SyncHandle:
-    __slots__ = ("bn", "x", "act", "group", "buf", "ws", "work", "launches_at_issue", "defer", "wide")
+    __slots__ = ("bn", "x", "act", "group", "buf", "ws", "work", "launches_at_issue", "defer", "wide", "fwd", "bwd", "res_fwd")
+
+
+# THE place the synchronised code looks at the kernel family, keyed by syncbn_begin's `wide`: the family's two-phase forward and backward wrappers (both
+# pairs take the same arguments) and the forward's residual form where the family has one
+_SYNC_KERNELS = {False: (ops.batchnorm_sync_fwd, ops.batchnorm_sync_bwd, None),
+                 True: (ops.batchnorm_train_sync_fwd, ops.batchnorm_train_sync_bwd, ops.batchnorm_train_sync_res_fwd)}
 
 
 def syncbn_begin(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE, defer_backward: bool = False, wide: bool = False) -> "_SyncHandle":
     """Phase 1 of nn.SyncBatchNorm's forward on rows + the asynchronous all-reduce of the [2C + 1] fp64 buffer (sums and row count).  wide: the any-width
     kernel family (fd_batchnorm_train_sync_*; check with _bn_train_wide_ok) on the C-channel view of x [rows, Cw >= C] -- the MBConv trunk's round32(C) maps
-    with zero pad channels, which the output and the input gradient keep; otherwise the GroupNorm-route family (fd_batchnorm_sync_*; _bn_train_ok) on
-    x [rows, C].  Everything behind phase 1 -- the collective, the handle, SYNC_TRACE, the deferred backward -- is the same."""
+    with zero pad channels, which the output and the input gradient keep; otherwise the GroupNorm-route family (fd_batchnorm_sync_*; _bn_train_ok), whose
+    callers pass x [rows, C].  Everything behind the choice of the wrappers -- the collective, the handle, SYNC_TRACE, the deferred backward -- is the same."""
     import torch.distributed as dist
     h = _SyncHandle()
     h.bn, h.act, h.defer, h.wide = bn, act, defer_backward, wide
+    h.fwd, h.bwd, h.res_fwd = _SYNC_KERNELS[wide]          # (everything below calls these: `wide` itself is read nowhere else)
     h.group = bn.process_group if bn.process_group is not None else dist.group.WORLD
     with torch.no_grad():
         xd = x.detach().float().contiguous()
-        rows, Cc = xd.shape
-        if wide:
-            Cc = bn.num_features
-            if xd.shape[1] < Cc or xd.shape[1] % 4:
-                raise FdError(f"SyncBatchNorm({Cc}) on rows of shape {tuple(x.shape)}: rows of at least {Cc} channels (a multiple of 4) expected")
-            h.buf = torch.empty(2 * Cc + 1, dtype=torch.float64, device=xd.device)
-            h.ws = ops.batchnorm_train_sync_fwd(1, Rows(xd, 0, Cc), h.buf, act_id=act)
-        else:
-            segs = Segs.make(1, [(rows, 1)])
-            h.ws = ops.groupnorm_workspace(segs, Cc, xd.device)
-            h.buf = torch.empty(2 * Cc + 1, dtype=torch.float64, device=xd.device)
-            fn = _lib.lib().fd_batchnorm_sync_fwd_nhwc
-            ops.check(fn(xd.data_ptr(), Cc, 0, None, None, None, 0, 0, rows, Cc, bn.eps, act, 1, h.buf.data_ptr(), 0.0, h.ws.data_ptr(), ops._stream()),
-                      "fd_batchnorm_sync_fwd_nhwc (stats)")
+        rows, Cc = xd.shape[0], bn.num_features
+        if xd.shape[1] < Cc or xd.shape[1] % 4:
+            raise FdError(f"SyncBatchNorm({Cc}) on rows of shape {tuple(x.shape)}: rows of at least {Cc} channels (a multiple of 4) expected")
+        h.buf = torch.empty(2 * Cc + 1, dtype=torch.float64, device=xd.device)
+        h.ws = h.fwd(1, Rows(xd, 0, Cc), h.buf, act_id=act)
         h.buf[2 * Cc] = float(rows)                               # this rank's row count rides behind the 2C sums (a device-side fill, no sync)
         h.work = dist.all_reduce(h.buf, group=h.group, async_op=True)       # THE forward collective of this layer (C3), not waited for here
     h.x = x
@@ -1228,44 +1226,30 @@ def syncbn_finish(h: "_SyncHandle", res: Optional[torch.Tensor] = None) -> torch
     bn = h.bn
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    if res is not None:
-        if not h.wide or h.defer:
-            raise FdError("syncbn_finish(res=...): the residual form exists for the any-width kernels (wide=True) without a deferred backward")
-        return _SyncBatchNormResApply.apply(h.x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, bn.momentum, bn.eps, h.act, h)
-    return _SyncBatchNormApply.apply(h.x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, h.act, h)
+    if res is not None and (h.res_fwd is None or h.defer):
+        raise FdError("syncbn_finish(res=...): the residual form exists for the any-width kernels (wide=True) without a deferred backward")
+    return _SyncBatchNormApply.apply(h.x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, bn.momentum, bn.eps, h.act, h)
 
 
-def _syncbn_backward(x, g, gm, bt, ws, buf, eps, act, group, defer, wide):
+def _syncbn_backward(x, g, gm, bt, ws, buf, eps, act, group, defer, bwd):
     """The backward of a SyncBatchNorm node on the contiguous incoming gradient g: phase 1 (this rank's sums, dgamma, dbeta), the asynchronous all-reduce,
-    and phase 2 -- run here, or left pending for the consuming conv node when `defer`.  Returns (gx, dgamma, dbeta)."""
-    import ctypes as C
+    and phase 2 -- run here, or left pending for the consuming conv node when `defer`.  bwd: the family's wrapper.  Returns (gx, dgamma, dbeta)."""
     import torch.distributed as dist
-    rows, Cc = x.shape[0], gm.numel()
+    Cc = gm.numel()
     gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
     dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device)
     dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device)
     sums = torch.empty(2 * Cc + 1, dtype=torch.float64, device=x.device)       # [sum dz | sum dz * xhat | global row count]
-    if wide:
-        bws = ops.batchnorm_train_sync_bwd(1, Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, sums, ws, None, dgamma, dbeta, eps, act)
-    else:
-        segs = Segs.make(1, [(rows, 1)])
-        nb = _lib.lib().fd_groupnorm_bwd_workspace_bytes(C.byref(segs), Cc)
-        bws = torch.empty(nb // 8, dtype=torch.float64, device=x.device)
-        fn = _lib.lib().fd_batchnorm_sync_bwd_nhwc
-        ops.check(fn(x.data_ptr(), Cc, 0, g.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), None, 0, 0, dgamma.data_ptr(), dbeta.data_ptr(),
-                     rows, Cc, eps, act, 1, sums.data_ptr(), 0.0, ws.data_ptr(), bws.data_ptr(), ops._stream()), "fd_batchnorm_sync_bwd_nhwc (sums)")
+    xr, gr = Rows(x, 0, Cc), Rows(g, 0, Cc)
+    bws = bwd(1, xr, gr, gm, bt, sums, ws, None, dgamma, dbeta, eps, act)
     sums[2 * Cc:].copy_(buf[2 * Cc:])                       # the forward's all-reduced row count, device to device (its own slot: not all-reduced again)
     work = dist.all_reduce(sums[:2 * Cc], group=group, async_op=True)     # THE backward collective of this layer
     at_issue = ops.LAUNCHES[0]
 
-    def finish(x=x, g=g, gm=gm, bt=bt, gx=gx, sums=sums, ws=ws, bws=bws, work=work):
+    def finish(xr=xr, gr=gr, gm=gm, bt=bt, gx=gx, sums=sums, ws=ws, bws=bws, work=work):
         SYNC_TRACE.append(("bwd", ops.LAUNCHES[0] - at_issue))
         work.wait()
-        if wide:
-            ops.batchnorm_train_sync_bwd(2, Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, sums, ws, Rows(gx, 0, Cc), None, None, eps, act, -1.0, ws=bws)
-            return
-        ops.check(fn(x.data_ptr(), Cc, 0, g.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), gx.data_ptr(), Cc, 0, None, None,
-                     rows, Cc, eps, act, 2, sums.data_ptr(), C.c_double(-1.0), ws.data_ptr(), None, ops._stream()), "fd_batchnorm_sync_bwd_nhwc (apply)")
+        bwd(2, xr, gr, gm, bt, sums, ws, Rows(gx, 0, Cc), None, None, eps, act, -1.0, ws=bws)
 
     if defer:
         # the ONLY consumer of gx is one of this module's conv nodes (conv_norm_begin built the chain): it finishes gx on entry (resolve_pending);
@@ -1280,46 +1264,72 @@ def _syncbn_backward(x, g, gm, bt, ws, buf, eps, act, group, defer, wide):
     return gx, dgamma, dbeta
 
 
+def _bn_node_begin(x, gamma, beta, res):
+    """What the batch-statistics nodes' forwards start with: contiguous inputs, the C-channel views of x and of an output of x's width (a map held wider than
+    C keeps exactly-zero pad channels), detached affine parameters."""
+    x = x.contiguous()
+    Cc = gamma.numel()
+    y = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
+    return x, y, Rows(x, 0, Cc), Rows(y, 0, Cc), (_r(res.contiguous()) if res is not None else None), gamma.detach().contiguous(), beta.detach().contiguous()
+
+
+def _bn_node_grad(gy, y):
+    """The incoming gradient of a batch-statistics node, finished and contiguous; y (the saved output of a residual form with ReLU): times [y > 0], which is
+    the residual's gradient AND the dz of a BatchNorm without activation."""
+    g = resolve_pending(gy).contiguous()
+    return g if y is None else relu_mask(g, y)
+
+
 class _SyncBatchNormApply(torch.autograd.Function):
     """Second half of nn.SyncBatchNorm in TRAINING mode + ReLU / SiLU on rows (train.py:101-103 converts the model after the DDP wrap): waits for the
     all-reduce syncbn_begin issued, normalises with the GLOBAL statistics, updates the running statistics with the global row count -- read ON THE
     DEVICE from the all-reduced buffer: ranks whose batches are padded to different H x W hold different row counts (dataset/voc.py:141-171).  Like
-    torch's SyncBatchNorm the affine gradients come from the local sums (DDP averages them)."""
+    torch's SyncBatchNorm the affine gradients come from the local sums (DDP averages them).  res (or None): the residual form act(bn(x) + res), act NONE /
+    ReLU, _BatchNormResRows across ranks -- phase 1 never read the residual; its backward is the mask pass, then the plain backward with ACT_NONE."""
 
     @staticmethod
     @_fwd32
-    def forward(ctx, x, gamma, beta, rmean, rvar, momentum, eps, act, h):
-        import ctypes as C
-        x = x.contiguous()
-        rows, Cc = x.shape[0], gamma.numel()
-        y = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)      # (wide: the pad channels stay exactly 0)
-        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
+    def forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act, h):
+        x, y, xr, yr, rr, gm, bt = _bn_node_begin(x, gamma, beta, res)
         SYNC_TRACE.append(("fwd", ops.LAUNCHES[0] - h.launches_at_issue))
         h.work.wait()
-        if h.wide:          # statistics, running statistics (global count from buf[2C] on the device) and apply in one call
-            ops.batchnorm_train_sync_fwd(2, Rows(x, 0, Cc), h.buf, gm, bt, Rows(y, 0, Cc), eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
+        # statistics, running statistics (global count from buf[2C] on the device) and apply in one call
+        if rr is None:
+            h.fwd(2, xr, h.buf, gm, bt, yr, eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
         else:
-            fn, st = _lib.lib().fd_batchnorm_sync_fwd_nhwc, ops._stream()
-            ops.check(fn(x.data_ptr(), Cc, 0, gm.data_ptr(), bt.data_ptr(), y.data_ptr(), Cc, 0, rows, Cc, eps, act, 2, h.buf.data_ptr(),
-                         C.c_double(-1.0), h.ws.data_ptr(), st), "fd_batchnorm_sync_fwd_nhwc (apply)")
-            if rmean is not None and momentum is not None:
-                ops.batchnorm_update_running_dev(h.ws, h.buf[2 * Cc:], Cc, momentum, eps, rmean, rvar)
-        ctx.save_for_backward(x, gm, bt, h.ws, h.buf)
-        ctx.geom = (eps, act, h.group, h.defer, h.wide)
+            h.res_fwd(2, xr, h.buf, gm, bt, rr, yr, eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
+        ctx.save_for_backward(x, gm, bt, h.ws, h.buf, y if rr is not None and act == ACT_RELU else None)
+        ctx.geom = (eps, act if rr is None else ACT_NONE, h.group, h.defer, h.bwd)
         return y
 
     @staticmethod
     @_bwd
     def backward(ctx, gy):
-        x, gm, bt, ws, buf = ctx.saved_tensors
-        gx, dgamma, dbeta = _syncbn_backward(x, gy.contiguous(), gm, bt, ws, buf, *ctx.geom)
-        return gx, dgamma, dbeta, None, None, None, None, None, None
+        x, gm, bt, ws, buf, y = ctx.saved_tensors
+        g = _bn_node_grad(gy, y)
+        gx, dgamma, dbeta = _syncbn_backward(x, g, gm, bt, ws, buf, *ctx.geom)
+        return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None, None
+
+
+def _bn_train_wide_ok(bn: nn.Module, x: torch.Tensor) -> bool:
+    """A BatchNorm in training mode that batchnorm_train_wide_rows takes: any width C % 4 == 0 up to 4096 (x may be held wider)."""
+    Cc = getattr(bn, "num_features", 0)
+    return (not _STOCK and isinstance(bn, BN_TYPES) and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and Cc % 4 == 0 and 4 <= Cc <= 4096 and _f32(x))
 
 
 def _bn_train_ok(bn: nn.Module, x: torch.Tensor) -> bool:
-    Cc = getattr(bn, "num_features", 0)
-    return (not _STOCK and isinstance(bn, BN_TYPES) and bn.training and bn.affine and bn.track_running_stats
-            and bn.momentum is not None and Cc % 4 == 0 and Cc <= 1024 and 256 % (Cc // 4) == 0 and _f32(x))
+    """One that batchnorm_train_rows takes: the widths of the GroupNorm-route kernels, C / 4 dividing 256 (so C <= 1024)."""
+    return _bn_train_wide_ok(bn, x) and 256 % (bn.num_features // 4) == 0
+
+
+BN_NARROW, BN_WIDE = "narrow", "wide"
+
+
+def _bn_family(bn: nn.Module, x: torch.Tensor) -> Optional[str]:
+    """The kernel family that runs `bn` on batch statistics: BN_NARROW (the GroupNorm route, batchnorm_train_rows) where its widths allow, else BN_WIDE (the
+    any-width kernels, _bn_wide_rows), None: not covered.  THE place this is decided."""
+    return BN_NARROW if _bn_train_ok(bn, x) else BN_WIDE if _bn_train_wide_ok(bn, x) else None
 
 
 def batchnorm_train_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) -> torch.Tensor:
@@ -1342,6 +1352,30 @@ def _is_sync(bn: nn.Module) -> bool:
     return False
 
 
+def _bn_wide_forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act):
+    """The forward of _BatchNormWideRows (res None) and _BatchNormResRows; the backward below is the plain one, in the residual form with ACT_NONE on the
+    gradient that the saved output masked."""
+    x, y, xr, yr, rr, gm, bt = _bn_node_begin(x, gamma, beta, res)
+    if rr is None:
+        ws = ops.batchnorm_train_fwd(xr, gm, bt, yr, eps, act, momentum, rmean, rvar)
+    else:
+        ws = ops.batchnorm_train_res_fwd(xr, gm, bt, rr, yr, eps, act, momentum, rmean, rvar)
+    ctx.save_for_backward(x, gm, bt, ws, y if rr is not None and act == ACT_RELU else None)
+    ctx.geom = (eps, act if rr is None else ACT_NONE)
+    return y
+
+
+def _bn_wide_backward(ctx, gy):
+    """Returns (g, gx, dgamma, dbeta): g is the residual's gradient too."""
+    x, gm, bt, ws, y = ctx.saved_tensors
+    eps, act = ctx.geom
+    Cc = gm.numel()
+    g = _bn_node_grad(gy, y)
+    gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
+    dgamma, dbeta = ops.batchnorm_train_bwd(Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, Rows(gx, 0, Cc), eps, act, ws)
+    return g, gx, dgamma, dbeta
+
+
 class _BatchNormWideRows(torch.autograd.Function):
     """nn.BatchNorm2d in TRAINING mode + ReLU / SiLU at ANY width C % 4 == 0 up to 4096 (fd_batchnorm_train_fwd_nhwc / _bwd_nhwc), on the real-width view of a
     map that may be held wider (the MBConv trunk: round32(C) with zero pad channels): x [rows, Cw >= C], gamma / beta [C].  The output and the input gradient
@@ -1350,33 +1384,13 @@ class _BatchNormWideRows(torch.autograd.Function):
     @staticmethod
     @_fwd32
     def forward(ctx, x, gamma, beta, rmean, rvar, momentum, eps, act):
-        x = x.contiguous()
-        rows, Cw = x.shape
-        Cc = gamma.numel()
-        y = (torch.zeros if Cw != Cc else torch.empty)(rows, Cw, dtype=torch.float32, device=x.device)
-        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
-        ws = ops.batchnorm_train_fwd(Rows(x, 0, Cc), gm, bt, Rows(y, 0, Cc), eps, act, momentum, rmean, rvar)
-        ctx.save_for_backward(x, gm, bt, ws)
-        ctx.geom = (eps, act)
-        return y
+        return _bn_wide_forward(ctx, x, gamma, beta, None, rmean, rvar, momentum, eps, act)
 
     @staticmethod
     @_bwd
     def backward(ctx, gy):
-        x, gm, bt, ws = ctx.saved_tensors
-        eps, act = ctx.geom
-        Cc = gm.numel()
-        g = resolve_pending(gy).contiguous()
-        gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
-        dgamma, dbeta = ops.batchnorm_train_bwd(Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, Rows(gx, 0, Cc), eps, act, ws)
+        _, gx, dgamma, dbeta = _bn_wide_backward(ctx, gy)
         return gx, dgamma, dbeta, None, None, None, None, None
-
-
-def _bn_train_wide_ok(bn: nn.Module, x: torch.Tensor) -> bool:
-    """A BatchNorm in training mode that batchnorm_train_wide_rows takes: any width C % 4 == 0 up to 4096 (x may be held wider)."""
-    Cc = getattr(bn, "num_features", 0)
-    return (not _STOCK and isinstance(bn, BN_TYPES) and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
-            and Cc % 4 == 0 and 4 <= Cc <= 4096 and _f32(x))
 
 
 def batchnorm_train_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) -> torch.Tensor:
@@ -1412,53 +1426,13 @@ class _BatchNormResRows(torch.autograd.Function):
     @staticmethod
     @_fwd32
     def forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act):
-        x, res = x.contiguous(), res.contiguous()
-        y = torch.empty_like(x)
-        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
-        ws = ops.batchnorm_train_res_fwd(_r(x), gm, bt, _r(res), _r(y), eps, act, momentum, rmean, rvar)
-        ctx.save_for_backward(x, gm, bt, ws, y if act == ACT_RELU else None)
-        ctx.eps = eps
-        return y
+        return _bn_wide_forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act)
 
     @staticmethod
     @_bwd
     def backward(ctx, gy):
-        x, gm, bt, ws, y = ctx.saved_tensors
-        g = resolve_pending(gy).contiguous()
-        if y is not None:
-            g = relu_mask(g, y)
-        gx = torch.empty_like(x)
-        dgamma, dbeta = ops.batchnorm_train_bwd(_r(x), _r(g), gm, bt, _r(gx), ctx.eps, ACT_NONE, ws)
+        g, gx, dgamma, dbeta = _bn_wide_backward(ctx, gy)
         return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None
-
-
-class _SyncBatchNormResApply(torch.autograd.Function):
-    """_BatchNormResRows for an nn.SyncBatchNorm that spans ranks: the second half behind syncbn_begin(..., wide=True), whose phase 1 never reads the residual
-    (fd_batchnorm_train_sync_res_fwd_nhwc phase 2).  Backward: the mask pass, then _SyncBatchNormApply's backward with ACT_NONE."""
-
-    @staticmethod
-    @_fwd32
-    def forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act, h):
-        x, res = x.contiguous(), res.contiguous()
-        y = torch.empty_like(x)
-        gm, bt = gamma.detach().contiguous(), beta.detach().contiguous()
-        SYNC_TRACE.append(("fwd", ops.LAUNCHES[0] - h.launches_at_issue))
-        h.work.wait()
-        ops.batchnorm_train_sync_res_fwd(2, _r(x), h.buf, gm, bt, _r(res), _r(y), eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
-        ctx.save_for_backward(x, gm, bt, h.ws, h.buf, y if act == ACT_RELU else None)
-        ctx.geom = (eps, h.group)
-        return y
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, gy):
-        x, gm, bt, ws, buf, y = ctx.saved_tensors
-        eps, group = ctx.geom
-        g = resolve_pending(gy).contiguous()
-        if y is not None:
-            g = relu_mask(g, y)
-        gx, dgamma, dbeta = _syncbn_backward(x, g, gm, bt, ws, buf, eps, ACT_NONE, group, False, True)
-        return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None, None
 
 
 def batchnorm_train_res_rows(bn: nn.Module, x: torch.Tensor, res: torch.Tensor, act: int = ACT_RELU) -> torch.Tensor:
@@ -1579,13 +1553,12 @@ def conv_norm_begin(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, segs
     """conv_norm_act_rows in two halves: everything up to and including the ISSUE of a SyncBatchNorm's statistics all-reduce.  The caller enqueues work
     that does not need the normalised tensor, then calls conv_norm_finish.  (Any other layer kind is simply computed here.)"""
     if bn is not None and not bn_is_frozen(bn) and _is_sync(bn):
-        dense, dw = _dense_ok(m, x), _dw_ok(m, x)
-        narrow = _bn_train_ok(bn, x)
-        if _STOCK or not (dense or dw) or not (narrow or _bn_train_wide_ok(bn, x)) or (dw and m.bias is not None):
+        dense, dw, family = _dense_ok(m, x), _dw_ok(m, x), _bn_family(bn, x)
+        if _STOCK or not (dense or dw) or family is None or (dw and m.bias is not None):
             return None
         pre = conv_rows(m, x, segs, None, ACT_NONE) if dense else dw_rows(m, x, segs, None, ACT_NONE)
         # the conv node just created is the only consumer of the BatchNorm's input gradient: its backward resolves the deferred second phase
-        return NormHandle(sync=syncbn_begin(bn, pre, act, defer_backward=True, wide=not narrow))
+        return NormHandle(sync=syncbn_begin(bn, pre, act, defer_backward=True, wide=family == BN_WIDE))
     y = conv_norm_act_rows(m, bn, x, segs, act)
     return None if y is None else NormHandle(y=y)
 
@@ -1610,12 +1583,10 @@ def conv_norm_act_rows(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, s
         return act_rows(conv(m, x, segs, bn, ACT_NONE), act)
     if dw and m.bias is not None:
         return None
-    if not _bn_train_ok(bn, x):
-        # widths the GroupNorm-route kernels refuse (C / 4 not dividing 256, C > 1024): the any-width kernels, where the result used to be None
-        if not _bn_train_wide_ok(bn, x):
-            return None
-        return _bn_wide_rows(bn, conv(m, x, segs, None, ACT_NONE), act)
-    return batchnorm_train_rows(bn, conv(m, x, segs, None, ACT_NONE), act)
+    family = _bn_family(bn, x)
+    if family is None:
+        return None
+    return (batchnorm_train_rows if family == BN_NARROW else _bn_wide_rows)(bn, conv(m, x, segs, None, ACT_NONE), act)
 
 
 # ------------------------------------------------------------------------------------ NCHW-shaped conveniences
@@ -1724,7 +1695,7 @@ def stem_rows_ok(trunk: nn.Module, x: torch.Tensor) -> bool:
     m, bn = trunk.conv1, trunk.bn1
     return (not _STOCK and tuple(m.weight.shape) == (64, 3, 7, 7) and m.bias is None and m.weight.dtype == torch.float32 and x.dtype == torch.float32
             and not x.requires_grad and x.dim() == 4 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.shape[2] >= 2 and x.shape[3] >= 2
-            and (bn_is_frozen(bn) or (_bn_train_ok(bn, x) and (not _is_sync(bn) or getattr(trunk, "hip_bn_train", False)))))
+            and (bn_is_frozen(bn) or (_bn_family(bn, x) == BN_NARROW and (not _is_sync(bn) or getattr(trunk, "hip_bn_train", False)))))
 
 
 def stem_rows(trunk: nn.Module, x: torch.Tensor) -> torch.Tensor:

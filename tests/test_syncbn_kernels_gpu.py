@@ -1,17 +1,16 @@
-"""fd_batchnorm_sync_fwd_nhwc / fd_batchnorm_sync_bwd_nhwc (two phases each, cut around an all-reduce the caller issues) and
+"""fd_batchnorm_sync_fwd_nhwc / fd_batchnorm_sync_bwd_nhwc (two phases each, cut around an all-reduce the caller issues; through their wrappers
+ops.batchnorm_sync_fwd / _bwd, which the training nodes call) and
 fd_batchnorm_update_running[_dev] at kernel level: R ranks are simulated on ONE device, without torch.distributed -- every rank is a shard of
-rows with its own sums buffer and workspace, the all-reduce is a sum of the ranks' buffers on the device.  The calls go through the C ABI with
-the argument order of train_ops.syncbn_begin / _SyncBatchNormApply; the reference is the float64 rank-set BatchNorm of tests/layer_ref.py:
+rows with its own sums buffer and workspace, the all-reduce is a sum of the ranks' buffers on the device.  The calls follow
+train_ops.syncbn_begin / _SyncBatchNormApply; the reference is the float64 rank-set BatchNorm of tests/layer_ref.py:
 global mean / rstd, dgamma / dbeta from each rank's LOCAL sums, dx from the global means, running statistics with the unbiased variance.
 Tolerances: those of test_batchnorm_train_rows_matches_nn_batchnorm (the same arithmetic)."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import layer_ref as R
-from pytorch_object_detection_amd import _lib, ops
+from pytorch_object_detection_amd import ops
 from pytorch_object_detection_amd._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU, FdError, Segs
 
 pytestmark = pytest.mark.gpu
@@ -25,28 +24,6 @@ GEOMS = [(0, 4), (4, 4), (8, 4), (12, 4)]
 def close(a, b, tol):
     s = float(b.abs().max()) + 1e-12
     np.testing.assert_allclose(a.double().cpu().numpy() / s, b.numpy() / s, atol=tol)
-
-
-def st():
-    return ops._stream()
-
-
-def fwd(x, gm, bt, y, rows, C, act, phase, sums, total, ws):
-    ops.check(_lib.lib().fd_batchnorm_sync_fwd_nhwc(x.ptr, x.cs, x.co, gm.data_ptr() if gm is not None else None, bt.data_ptr() if bt is not None else None,
-                                                    y.ptr if y is not None else None, y.cs if y is not None else 0, y.co if y is not None else 0, rows, C, EPS, act,
-                                                    phase, sums.data_ptr(), ctypes.c_double(total), ws.data_ptr(), st()), "fd_batchnorm_sync_fwd_nhwc")
-
-
-def bwd(x, dy, gm, bt, dx, dgamma, dbeta, rows, C, act, phase, sums, total, ws, bws):
-    ops.check(_lib.lib().fd_batchnorm_sync_bwd_nhwc(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gm.data_ptr(), bt.data_ptr(), dx.ptr if dx is not None else None,
-                                                    dx.cs if dx is not None else 0, dx.co if dx is not None else 0, dgamma.data_ptr() if dgamma is not None else None,
-                                                    dbeta.data_ptr() if dbeta is not None else None, rows, C, EPS, act, phase, sums.data_ptr(), ctypes.c_double(total),
-                                                    ws.data_ptr(), bws.data_ptr() if bws is not None else None, st()), "fd_batchnorm_sync_bwd_nhwc")
-
-
-def bwd_workspace(rows, C):
-    segs = Segs.make(1, [(rows, 1)])
-    return torch.empty(_lib.lib().fd_groupnorm_bwd_workspace_bytes(ctypes.byref(segs), C) // 8, dtype=torch.float64, device=DEV)
 
 
 def data(shards, C, seed=0):
@@ -76,23 +53,23 @@ def protocol(xs, dys, gamma, beta, rmean, rvar, act, host_total, geoms=None):
     wss = [ops.groupnorm_workspace(Segs.make(1, [(x.shape[0], 1)]), C, DEV) for x in xs]
     sums = [torch.empty(2 * C + 1, dtype=torch.float64, device=DEV) for _ in xs]
     for r in range(n):                                                      # forward phase 1 + this rank's row count behind the sums
-        fwd(xv[r], None, None, None, xs[r].shape[0], C, act, 1, sums[r], 0.0, wss[r])
+        ops.batchnorm_sync_fwd(1, xv[r], sums[r], None, None, None, EPS, act, 0.0, ws=wss[r])
         sums[r][2 * C] = float(xs[r].shape[0])
     red = torch.stack(sums).sum(0)                                          # the all-reduce
     for r in range(n):
         sums[r].copy_(red)
-        fwd(xv[r], gm, bt, yv[r], xs[r].shape[0], C, act, 2, sums[r], total, wss[r])
+        ops.batchnorm_sync_fwd(2, xv[r], sums[r], gm, bt, yv[r], EPS, act, total, ws=wss[r])
     ops.batchnorm_update_running_dev(wss[0], sums[0][2 * C:], C, MOM, EPS, rm, rv)
     dgs = [torch.full((C,), NAN, device=DEV) for _ in xs]
     dbs = [torch.full((C,), NAN, device=DEV) for _ in xs]
     bsums = [torch.empty(2 * C + 1, dtype=torch.float64, device=DEV) for _ in xs]
     for r in range(n):                                                      # backward phase 1; the row count is copied, not reduced again
-        bwd(xv[r], dyv[r], gm, bt, None, dgs[r], dbs[r], xs[r].shape[0], C, act, 1, bsums[r], 0.0, wss[r], bwd_workspace(xs[r].shape[0], C))
+        ops.batchnorm_sync_bwd(1, xv[r], dyv[r], gm, bt, bsums[r], wss[r], None, dgs[r], dbs[r], EPS, act, 0.0)
         bsums[r][2 * C:].copy_(sums[r][2 * C:])
     red = torch.stack([s[:2 * C] for s in bsums]).sum(0)                    # the all-reduce of sums[:2C] only
     for r in range(n):
         bsums[r][:2 * C].copy_(red)
-        bwd(xv[r], dyv[r], gm, bt, dxv[r], None, None, xs[r].shape[0], C, act, 2, bsums[r], total, wss[r], None)
+        ops.batchnorm_sync_bwd(2, xv[r], dyv[r], gm, bt, bsums[r], wss[r], dxv[r], None, None, EPS, act, total)
     torch.cuda.synchronize()
     out = dict(y=[v.tensor().clone() for v in yv], dx=[v.tensor().clone() for v in dxv], dgamma=dgs, dbeta=dbs, rmean=rm, rvar=rv, ws=wss, count=sums[0][2 * C:])
     return out, (bufs, before, [xv, yv, dyv, dxv])
@@ -190,16 +167,16 @@ def test_rejections_leave_the_outputs_untouched():
         sums = torch.full((2 * C + 1,), NAN, dtype=torch.float64, device=DEV)
         dg, db = torch.full((C,), NAN, device=DEV), torch.full((C,), NAN, device=DEV)
         ws = ops.groupnorm_workspace(Segs.make(1, [(rows, 1)]), C, DEV)
-        bws = bwd_workspace(rows, C)
+        F, B = ops.batchnorm_sync_fwd, ops.batchnorm_sync_bwd
         calls = {
-            "C48": [lambda: fwd(x, None, None, None, rows, C, ACT_NONE, 1, sums, 0.0, ws), lambda: fwd(x, gm, bt, y, rows, C, ACT_NONE, 2, sums, -1.0, ws),
-                    lambda: bwd(x, dy, gm, bt, None, dg, db, rows, C, ACT_NONE, 1, sums, 0.0, ws, bws),
-                    lambda: bwd(x, dy, gm, bt, dx, None, None, rows, C, ACT_NONE, 2, sums, -1.0, ws, None)],
-            "total_rows": [lambda: fwd(x, gm, bt, y, rows, C, ACT_NONE, 2, sums, 5.0, ws),              # 0 < total_rows < this shard's rows
-                           lambda: bwd(x, dy, gm, bt, dx, None, None, rows, C, ACT_NONE, 2, sums, 36.0, ws, None)],
-            "phase": [lambda: fwd(x, gm, bt, y, rows, C, ACT_NONE, 3, sums, -1.0, ws), lambda: bwd(x, dy, gm, bt, dx, dg, db, rows, C, ACT_NONE, 3, sums, -1.0, ws, bws)],
-            "sigmoid": [lambda: bwd(x, dy, gm, bt, None, dg, db, rows, C, ACT_SIGMOID, 1, sums, 0.0, ws, bws),
-                        lambda: bwd(x, dy, gm, bt, dx, None, None, rows, C, ACT_SIGMOID, 2, sums, -1.0, ws, None)],
+            "C48": [lambda: F(1, x, sums, None, None, None, EPS, ACT_NONE, 0.0, ws=ws), lambda: F(2, x, sums, gm, bt, y, EPS, ACT_NONE, -1.0, ws=ws),
+                    lambda: B(1, x, dy, gm, bt, sums, ws, None, dg, db, EPS, ACT_NONE, 0.0),
+                    lambda: B(2, x, dy, gm, bt, sums, ws, dx, None, None, EPS, ACT_NONE, -1.0)],
+            "total_rows": [lambda: F(2, x, sums, gm, bt, y, EPS, ACT_NONE, 5.0, ws=ws),              # 0 < total_rows < this shard's rows
+                           lambda: B(2, x, dy, gm, bt, sums, ws, dx, None, None, EPS, ACT_NONE, 36.0)],
+            "phase": [lambda: F(3, x, sums, gm, bt, y, EPS, ACT_NONE, -1.0, ws=ws), lambda: B(3, x, dy, gm, bt, sums, ws, dx, dg, db, EPS, ACT_NONE, -1.0)],
+            "sigmoid": [lambda: B(1, x, dy, gm, bt, sums, ws, None, dg, db, EPS, ACT_SIGMOID, 0.0),
+                        lambda: B(2, x, dy, gm, bt, sums, ws, dx, None, None, EPS, ACT_SIGMOID, -1.0)],
         }[what]
         for call in calls:
             with pytest.raises(FdError):
