@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's train.py:97-181 loop on the MI355X path, with synthetic VOC-shaped batches.
 
-    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem]
+    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-optim]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_like_train_py.py   # DDP / RCCL
 
 Same objects and call order as the reference: HalfInvertedStageFCOS([512, 1024, 2048], 20, 256), FCOSGenTargets,
@@ -12,7 +12,9 @@ the reference's AMP arithmetic), normalisation and losses in fp32; under DDP the
 --model MNFCOS (what the reference's config/main.yaml selects) builds MNFCOS([2048, 1024, 512], 20, 256) and opts in to its HIP training nodes
 with model.enable_training() (which also freezes the Cin = 3 stem: the optimizer is built after it).  --hip-stem trains the 7x7 stem on its HIP node
 (fd_stem7x7_bwd_weight_nhwc4) instead: MNFCOS keeps the stem trainable (enable_training(train_stem=True)), HISFCOS un-freezes conv1 and sets
-enable_stem_training() -- without the option a trainable stem runs on stock ops.
+enable_stem_training() -- without the option a trainable stem runs on stock ops.  --hip-optim takes the optimizer from pytorch_object_detection_amd.optim:
+step() on the HIP update kernels, GradScaler without a host read, and the warm-up / drop lines of train.py:160-173 evaluated on the device (optim.TrainPyLR)
+instead of the host lines below.
 """
 import argparse
 import os
@@ -23,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pytorch_object_detection_amd import optim  # noqa: E402
 from pytorch_object_detection_amd.model.loss import FCOSLoss  # noqa: E402
 from pytorch_object_detection_amd.model.modules.head import FCOSGenTargets  # noqa: E402
 from pytorch_object_detection_amd.model.od import MNFCOS, HalfInvertedStageFCOS  # noqa: E402
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--amp", action="store_true")
     ap.add_argument("--model", choices=["HISFCOS", "MNFCOS"], default="HISFCOS")
     ap.add_argument("--hip-stem", action="store_true", help="train the 7x7 stem (conv1) on its HIP forward / weight-gradient node")
+    ap.add_argument("--hip-optim", action="store_true", help="optim.SGD with the learning-rate rule on the device instead of torch.optim.SGD and the host lines")
     args = ap.parse_args()
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
     torch.cuda.set_device(local)
@@ -57,7 +61,11 @@ def main():
         model = torch.nn.parallel.DistributedDataParallel(model, find_unused_parameters=True)       # train.py:101
         model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)                                 # train.py:103
     LR_INIT, WARMUP_STEPS = 1e-3, 501
-    optimizer = torch.optim.SGD([p for p in model.parameters() if p.requires_grad], lr=LR_INIT, momentum=0.9, weight_decay=1e-4)
+    trainable = [p for p in model.parameters() if p.requires_grad]
+    if args.hip_optim:
+        optimizer = optim.SGD(trainable, lr=LR_INIT, momentum=0.9, weight_decay=1e-4, lr_schedule=optim.TrainPyLR(LR_INIT, WARMUP_STEPS))
+    else:
+        optimizer = torch.optim.SGD(trainable, lr=LR_INIT, momentum=0.9, weight_decay=1e-4)
     scaler = torch.amp.GradScaler("cuda", enabled=args.amp)                                         # train.py:133
     criterion = FCOSLoss("giou")
 
@@ -70,7 +78,7 @@ def main():
         s = torch.rand(args.batch, 8, 2, generator=g, device=dev) * 150 + 20
         targets = torch.cat([c - s / 2, c + s / 2], -1).clamp(0, 511)
         classes = torch.randint(1, 21, (args.batch, 8), generator=g, device=dev)
-        if step < WARMUP_STEPS:                                                                     # train.py:161-164
+        if step < WARMUP_STEPS and not args.hip_optim:                                              # train.py:161-164
             for group in optimizer.param_groups:
                 group["lr"] = float(step / WARMUP_STEPS * LR_INIT)
         optimizer.zero_grad()

@@ -1023,6 +1023,100 @@ int32_t fd_anchor_decode(const fd_anchor_params* p, const float* loc, const floa
                          float cls_thresh, float nms_thresh, int32_t max_candidates, float* boxes, int64_t* labels,
                          float* scores, int32_t* counts, int32_t* n_candidates, void* workspace, fd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------- */
+/* Optimizer step (train.py:160-182: the learning-rate lines, scaler.step(optimizer)).
+ *
+ * One step is ONE begin launch followed by one update launch per chunk of tensors.  A chunk is a list of up to
+ * FD_OPTIM_MAX_TENSORS tensors whose pointers travel BY VALUE in the kernel arguments: nothing on the device outlives the
+ * launch, so gradients may move between steps (zero_grad(set_to_none=True), a graph's private pool) and a capture records
+ * the arguments as they are.  The host fills every chunk from the live tensors of the step it launches.
+ *
+ * fd_optim_state is the optimizer's own block of device memory (allocated once, zero-filled: its address must not move
+ * between a capture and its replays).  Only the begin launch writes it; the update launches only read it.
+ *   global_step   pre-incremented by every begin (the reference's GLOBAL_STEPS)
+ *   skip          1 when *found_inf != 0 at begin: the update launches of the step then write nothing
+ *   lr[group]     fp64 rate of the step, written by every begin from the rule, a device scalar or a value
+ *   applied[group]  steps actually applied (not skipped); Adam's t
+ *   bc1 / bc2     1 - beta1^t, 1 - beta2^t in fp64 (Adam) */
+#define FD_OPTIM_MAX_TENSORS 64 /* chunk capacity: 64 * 40 B + 8 B = 2568 B of the 4 KB kernel-argument segment */
+#define FD_OPTIM_MAX_GROUPS 8
+#define FD_OPTIM_MAX_DROPS 4
+#define FD_OPTIM_LR_NONE 0     /* lr[group] = *lr_ptr[group] if given, else lr_value[group] */
+#define FD_OPTIM_LR_TRAIN_PY 1 /* train.py:160-173 */
+#define FD_OPTIM_LR_TRAIN_NEW 2 /* train_new.py:79-90 */
+
+typedef struct fd_optim_state {
+    int64_t global_step;
+    int64_t skip;
+    double lr[FD_OPTIM_MAX_GROUPS];
+    int64_t applied[FD_OPTIM_MAX_GROUPS];
+    double bc1[FD_OPTIM_MAX_GROUPS];
+    double bc2[FD_OPTIM_MAX_GROUPS];
+} fd_optim_state;
+
+typedef struct fd_optim_chunk {
+    int32_t n; /* tensors in use, 1 .. FD_OPTIM_MAX_TENSORS */
+    int32_t reserved0;
+    float* p[FD_OPTIM_MAX_TENSORS];       /* parameter */
+    const float* g[FD_OPTIM_MAX_TENSORS]; /* gradient (still multiplied by *grad_scale) */
+    float* s0[FD_OPTIM_MAX_TENSORS];      /* SGD momentum buffer (NULL when momentum == 0) / Adam exp_avg */
+    float* s1[FD_OPTIM_MAX_TENSORS];      /* Adam exp_avg_sq (NULL for SGD) */
+    int64_t numel[FD_OPTIM_MAX_TENSORS];  /* 0 is legal: the tensor is skipped and its pointers are not looked at */
+} fd_optim_chunk;
+
+/* Hyper-parameters of one param group; the rate is NOT here, every update reads state->lr[group]. */
+typedef struct fd_optim_hyper {
+    int32_t group;        /* 0 .. FD_OPTIM_MAX_GROUPS - 1 */
+    int32_t nesterov;     /* SGD */
+    int32_t decoupled_wd; /* Adam: 1 = AdamW */
+    int32_t reserved0;
+    double momentum;      /* SGD */
+    double weight_decay;
+    double beta1, beta2, eps; /* Adam */
+} fd_optim_hyper;
+
+/* What the begin launch evaluates.  The rule works in fp64 in the reference's operation order:
+ *   TRAIN_PY:  G < warmup_steps: lr = G / warmup_steps * lr_init; then, for each drop in order, G == drop_step[i]:
+ *              lr = lr_init * drop_factor[i]; a step that meets neither keeps the rate of the step before.
+ *   TRAIN_NEW: lr = lr_init; G < warmup_steps: a = G / warmup_steps, lr = lr * (warmup_factor * (1 - a) + a);
+ *              else for each milestone drop_step[i] in order: stop at the first G < drop_step[i], else lr = lr * gamma.
+ * Every group gets the rule's rate.  active[group] = 0: the group has no tensor this step, its applied count stays. */
+typedef struct fd_optim_begin_params {
+    int32_t n_groups; /* 1 .. FD_OPTIM_MAX_GROUPS */
+    int32_t adam;     /* 1: write bc1 / bc2 */
+    int32_t rule;     /* FD_OPTIM_LR_* */
+    int32_t n_drops;  /* 0 .. FD_OPTIM_MAX_DROPS */
+    double lr_init, warmup_factor, gamma;
+    int64_t warmup_steps;
+    int64_t drop_step[FD_OPTIM_MAX_DROPS];
+    double drop_factor[FD_OPTIM_MAX_DROPS];
+    double lr_value[FD_OPTIM_MAX_GROUPS];
+    const void* lr_ptr[FD_OPTIM_MAX_GROUPS]; /* device scalar, fp64 when lr_ptr_f64[group] else fp32; NULL: lr_value */
+    int32_t lr_ptr_f64[FD_OPTIM_MAX_GROUPS];
+    int32_t active[FD_OPTIM_MAX_GROUPS];
+    double beta1[FD_OPTIM_MAX_GROUPS], beta2[FD_OPTIM_MAX_GROUPS];
+} fd_optim_begin_params;
+
+/* One launch, one lane: global_step += 1; skip = found_inf && *found_inf != 0 (found_inf: device fp32 scalar or NULL);
+ * lr[group]; unless skipped applied[group] += 1 for the active groups; bc1 / bc2 from applied (Adam). */
+int32_t fd_optim_begin(fd_optim_state* state, const float* found_inf, const fd_optim_begin_params* params, fd_stream_t stream);
+
+/* One chunk of fp32 tensors, blockIdx.y = tensor, blockIdx.x grid-strides over its elements.  g is multiplied by
+ * 1 / *grad_scale on load (grad_scale: device fp32 scalar or NULL); nothing is written when state->skip is set.
+ * 16-byte accesses where the tensor's pointers share one alignment (scalar head up to the boundary, scalar tail), scalar
+ * accesses where they do not.  Arithmetic is fp32 without FMA contraction, in the order written here.
+ *   SGD  (torch.optim.SGD, dampening 0):  d = g + wd * p;  momentum != 0: buf = momentum * buf + d,
+ *        d = nesterov ? d + momentum * buf : buf;  p -= lr * d.   Buffers start as zeros.
+ *   Adam (torch.optim.Adam / AdamW, no AMSGrad):  decoupled_wd ? p *= 1 - lr * wd : g += wd * p;
+ *        m += (g - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g * g;
+ *        p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps).
+ * FD_E_INVAL: n outside [1, FD_OPTIM_MAX_TENSORS], a negative numel, a null p / g / needed state pointer of a tensor
+ * with numel > 0, a null state block, a group outside the table. */
+int32_t fd_optim_sgd_f32(const fd_optim_chunk* chunk, const fd_optim_hyper* hyper, const fd_optim_state* state,
+                         const float* grad_scale, fd_stream_t stream);
+int32_t fd_optim_adam_f32(const fd_optim_chunk* chunk, const fd_optim_hyper* hyper, const fd_optim_state* state,
+                          const float* grad_scale, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,34 @@ class AnchorParams(C.Structure):
 
 ANCHOR_MAX_GT, ANCHOR_MAX_CLASSES, ANCHOR_MAX_CAND = 256, 128, 1024     # include/fcosdet.h FD_ANCHOR_MAX_*
 
+OPTIM_MAX_TENSORS, OPTIM_MAX_GROUPS, OPTIM_MAX_DROPS = 64, 8, 4           # include/fcosdet.h FD_OPTIM_MAX_*
+OPTIM_LR_NONE, OPTIM_LR_TRAIN_PY, OPTIM_LR_TRAIN_NEW = 0, 1, 2            # FD_OPTIM_LR_*
+
+
+class OptimState(C.Structure):
+    """fd_optim_state: the optimizer's device block.  Never instantiated on the host: optim.py allocates sizeof() bytes on the device and views the fields."""
+    _fields_ = [("global_step", C.c_int64), ("skip", C.c_int64), ("lr", C.c_double * OPTIM_MAX_GROUPS), ("applied", C.c_int64 * OPTIM_MAX_GROUPS),
+                ("bc1", C.c_double * OPTIM_MAX_GROUPS), ("bc2", C.c_double * OPTIM_MAX_GROUPS)]
+
+
+class OptimChunk(C.Structure):
+    """fd_optim_chunk: up to OPTIM_MAX_TENSORS tensors of one update launch, passed to the kernel by value."""
+    _fields_ = [("n", C.c_int32), ("reserved0", C.c_int32), ("p", C.c_void_p * OPTIM_MAX_TENSORS), ("g", C.c_void_p * OPTIM_MAX_TENSORS),
+                ("s0", C.c_void_p * OPTIM_MAX_TENSORS), ("s1", C.c_void_p * OPTIM_MAX_TENSORS), ("numel", C.c_int64 * OPTIM_MAX_TENSORS)]
+
+
+class OptimHyper(C.Structure):
+    _fields_ = [("group", C.c_int32), ("nesterov", C.c_int32), ("decoupled_wd", C.c_int32), ("reserved0", C.c_int32),
+                ("momentum", C.c_double), ("weight_decay", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
+
+
+class OptimBeginParams(C.Structure):
+    _fields_ = [("n_groups", C.c_int32), ("adam", C.c_int32), ("rule", C.c_int32), ("n_drops", C.c_int32),
+                ("lr_init", C.c_double), ("warmup_factor", C.c_double), ("gamma", C.c_double), ("warmup_steps", C.c_int64),
+                ("drop_step", C.c_int64 * OPTIM_MAX_DROPS), ("drop_factor", C.c_double * OPTIM_MAX_DROPS),
+                ("lr_value", C.c_double * OPTIM_MAX_GROUPS), ("lr_ptr", C.c_void_p * OPTIM_MAX_GROUPS), ("lr_ptr_f64", C.c_int32 * OPTIM_MAX_GROUPS),
+                ("active", C.c_int32 * OPTIM_MAX_GROUPS), ("beta1", C.c_double * OPTIM_MAX_GROUPS), ("beta2", C.c_double * OPTIM_MAX_GROUPS)]
+
 _lib = None
 
 _P, _I, _F, _D, _L = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_int64
@@ -237,6 +265,9 @@ _SIGS = {
     "fd_anchor_encode": (_I, [C.POINTER(AnchorParams), _P, _P, _I, _I, _I, _P, _P, _P]),
     "fd_anchor_decode_workspace_bytes": (_L, [_I, _I, _I]),
     "fd_anchor_decode": (_I, [C.POINTER(AnchorParams), _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "fd_optim_begin": (_I, [_P, _P, C.POINTER(OptimBeginParams), _P]),
+    "fd_optim_sgd_f32": (_I, [C.POINTER(OptimChunk), C.POINTER(OptimHyper), _P, _P, _P]),
+    "fd_optim_adam_f32": (_I, [C.POINTER(OptimChunk), C.POINTER(OptimHyper), _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -47,9 +47,20 @@ class Builder:
             raise NotImplementedError(f"model '{self.model}' is outside the MI355X hot path (FCOS, HISFCOS, MNFCOS)")
         return ctor(block["CannelofBackbone"], self.config["dataset_setting"]["class_num"], block["channel"])
 
-    def opt_build(self, model: nn.Module) -> torch.optim.Optimizer:
+    def opt_build(self, model: nn.Module, hip: bool = False) -> torch.optim.Optimizer:
+        """hip=True: the optimizer of that name from .optim (step() on HIP kernels, capture-safe, GradScaler without a host read) with train.py's learning-rate
+        rule for the block's `lr` evaluated on the device; the default is the stock torch optimizer the reference builds."""
         opt = self._block()["optimizer"]
-        make = _OPTIMIZERS.get(opt["name"])
+        make = (_hip_optimizers() if hip else _OPTIMIZERS).get(opt["name"])
         if make is None:
-            raise NotImplementedError(f"optimizer '{opt['name']}'")
+            raise NotImplementedError(f"optimizer '{opt['name']}'" + (" on the HIP path (SGD, Adam, AdamW)" if hip else ""))
         return make([p for p in model.parameters() if p.requires_grad], opt)
+
+
+def _hip_optimizers() -> Dict[str, Callable[..., torch.optim.Optimizer]]:
+    from . import optim
+    return {
+        "SGD": lambda params, o: optim.SGD(params, lr=o["lr"], momentum=o["momentum"], weight_decay=o["weight_decay"], lr_schedule=optim.TrainPyLR(o["lr"])),
+        "Adam": lambda params, o: optim.Adam(params, lr=o["lr"], weight_decay=o["weight_decay"], lr_schedule=optim.TrainPyLR(o["lr"])),
+        "AdamW": lambda params, o: optim.AdamW(params, lr=o["lr"], weight_decay=o["weight_decay"], lr_schedule=optim.TrainPyLR(o["lr"])),
+    }

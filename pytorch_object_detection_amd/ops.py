@@ -2254,3 +2254,39 @@ def eval_coco(scores: torch.Tensor, labels: torch.Tensor, boxes: torch.Tensor, d
                          G, ptr(image_order), int(num_cats), thr, T, rec, R, ar, A, md, M, precision.data_ptr(), recall.data_ptr(),
                          n_gt.data_ptr(), ws.data_ptr(), _stream()), "fd_eval_coco")
     return precision, recall, n_gt
+
+
+def optim_begin(state: torch.Tensor, found_inf: Optional[torch.Tensor], params: _lib.OptimBeginParams) -> None:
+    """fd_optim_begin on the optimizer's state block (optim.py): counters, skip flag, the step's rates, Adam's bias corrections.  One launch."""
+    _need_gpu(state, found_inf)
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.numel() * 8 < C.sizeof(_lib.OptimState):
+        raise FdError("optim_begin: state must be the optimizer's contiguous float64 block")
+    if found_inf is not None and (found_inf.dtype != torch.float32 or found_inf.numel() != 1 or found_inf.device != state.device):
+        raise FdError("optim_begin: found_inf must be one fp32 element on the optimizer's device")
+    check(_lib.lib().fd_optim_begin(state.data_ptr(), _dptr(found_inf), C.byref(params), _stream()), "fd_optim_begin")
+
+
+def optim_update(adam: bool, p: Sequence[int], g: Sequence[int], s0: Optional[Sequence[int]], s1: Optional[Sequence[int]], numel: Sequence[int],
+                 hyper: _lib.OptimHyper, state: torch.Tensor, grad_scale: Optional[torch.Tensor]) -> int:
+    """fd_optim_sgd_f32 / fd_optim_adam_f32 over a list of tensors given as device addresses (s0 / s1: None when the rule has no such state), in chunks of
+    _lib.OPTIM_MAX_TENSORS whose pointers travel by value in the kernel arguments.  The caller read every address from the live tensors just now: nothing
+    here is kept across calls.  -> launches enqueued."""
+    _need_gpu(state, grad_scale)
+    if grad_scale is not None and (grad_scale.dtype != torch.float32 or grad_scale.numel() != 1 or grad_scale.device != state.device):
+        raise FdError("optim_update: grad_scale must be one fp32 element on the optimizer's device")
+    fn = _lib.lib().fd_optim_adam_f32 if adam else _lib.lib().fd_optim_sgd_f32
+    what = "fd_optim_adam_f32" if adam else "fd_optim_sgd_f32"
+    cap, total, launches = _lib.OPTIM_MAX_TENSORS, len(p), 0
+    st, gs = state.data_ptr(), _dptr(grad_scale)
+    for lo in range(0, total, cap):
+        n = min(cap, total - lo)
+        c = _lib.OptimChunk()
+        c.n = n
+        c.p[:n], c.g[:n], c.numel[:n] = p[lo:lo + n], g[lo:lo + n], numel[lo:lo + n]
+        if s0 is not None:
+            c.s0[:n] = s0[lo:lo + n]
+        if s1 is not None:
+            c.s1[:n] = s1[lo:lo + n]
+        check(fn(C.byref(c), C.byref(hyper), st, gs, _stream()), what)
+        launches += 1
+    return launches

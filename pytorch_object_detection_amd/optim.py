@@ -1,0 +1,333 @@
+"""The optimizer step on HIP kernels: SGD / Adam / AdamW whose step() never reads the device, with the reference's learning-rate rule evaluated on the device.
+
+    opt = optim.SGD(params, lr=0.01, momentum=0.9, weight_decay=1e-4, lr_schedule=optim.TrainPyLR(0.01))
+    scaler.scale(loss).backward(); scaler.step(opt); scaler.update()          # train.py:180-182 unchanged; or opt.step()
+
+Each class subclasses the torch optimizer of its name and overrides step() only: constructor arguments, param_groups, the per-parameter state keys and the
+state-dict format are the parent's, so checkpoints move both ways.  One step() is one fd_optim_begin launch (global step, skip flag from GradScaler's found_inf,
+the step's learning rates, Adam's bias corrections -- all in the optimizer's own state block on the device) and one update launch per 64 tensors, whose pointers
+travel by value in the kernel arguments (include/fcosdet.h "Optimizer step").  Every pointer a launch receives is read from the live tensors inside that step():
+gradients are re-allocated by every backward and live elsewhere during a graph capture, so nothing about them is cached.  The step is therefore capture-safe as it
+is (train_graph.GraphedStep); run one eager step first, because the state tensors are created by the first step that sees a gradient.
+
+What stays stock: torch.amp.GradScaler's own inf check and update().  Moving an optimizer goes through state_dict() / load_state_dict() and
+global_step / set_global_step(); pickling or deep-copying the optimizer object itself is not supported (torch's __getstate__ drops the state block).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Tuple
+
+import torch
+
+from . import _lib, ops
+from ._lib import FdError
+
+
+class TrainPyLR(NamedTuple):
+    """train.py:160-173 as it is written: while G < warmup_steps the rate is G / warmup_steps * lr_init; at G == a drop step it becomes lr_init * factor; any other
+    step keeps the rate of the step before (so steps 501 .. 20000 run at 500/501 * lr_init).  G starts at 1."""
+    lr_init: float
+    warmup_steps: int = 501
+    drops: Tuple[Tuple[int, float], ...] = ((20001, 0.1), (50001, 0.01))
+    first_step = 1
+
+    def at(self, step: int, before: float) -> float:
+        """The rate the reference's loop holds after the lines of step `step` have run for every G in first_step .. step (closed form; `before`: the rate
+        the optimizer was built with).  Used to seed the device scalar when a run resumes at a step (set_global_step)."""
+        when, lr = 0, float(before)
+        if step >= 1 and self.warmup_steps > 1:
+            when = min(step, self.warmup_steps - 1)
+            lr = float(when / self.warmup_steps * self.lr_init)
+        for at_step, factor in self.drops:
+            if at_step <= step and at_step >= max(when, 1):
+                when, lr = at_step, self.lr_init * factor
+        return lr
+
+
+class TrainNewLR(NamedTuple):
+    """train_new.py:79-90: a function of the step alone.  Below warmup_steps a linear blend from warmup_factor to 1 times lr_init; from there lr_init multiplied
+    by gamma once per milestone reached (repeated multiplication, as there).  G starts at 0."""
+    lr_init: float
+    warmup_steps: int = 500
+    warmup_factor: float = 1.0 / 3.0
+    milestones: Tuple[int, ...] = (120000, 160000)
+    gamma: float = 0.1
+    first_step = 0
+
+    def at(self, step: int, before: float) -> float:
+        if step < self.first_step:
+            return float(before)
+        lr = self.lr_init
+        if step < self.warmup_steps:
+            alpha = float(step) / self.warmup_steps
+            lr = lr * (self.warmup_factor * (1.0 - alpha) + alpha)
+        else:
+            for m in self.milestones:
+                if step < m:
+                    break
+                lr *= self.gamma
+        return float(lr)
+
+
+_WORDS = C.sizeof(_lib.OptimState) // 8
+_F = _lib.OptimState
+
+
+def _word(field) -> int:
+    return field.offset // 8
+
+
+class _HipStep:
+    """What the three classes share: the state block, the begin launch, the chunked update launches.  A mixin placed BEFORE the torch optimizer in the bases."""
+    _step_supports_amp_scaling = True      # torch.amp.GradScaler then leaves grad_scale / found_inf on the optimizer as device tensors and does not read them
+    _ADAM = False
+
+    def _fd_init(self, lr_schedule) -> None:
+        if lr_schedule is not None and not isinstance(lr_schedule, (TrainPyLR, TrainNewLR)):
+            raise ValueError("lr_schedule must be an optim.TrainPyLR, an optim.TrainNewLR or None")
+        if len(self.param_groups) > _lib.OPTIM_MAX_GROUPS:
+            raise ValueError(f"param_groups: {len(self.param_groups)} groups (the device state block holds {_lib.OPTIM_MAX_GROUPS})")
+        for name in ("maximize", "differentiable", "amsgrad"):
+            if any(g.get(name) for g in self.param_groups):
+                raise ValueError(f"{name}=True is not implemented by the HIP optimizer step")
+        if any(g.get("dampening", 0) != 0 for g in self.param_groups):
+            raise ValueError("dampening != 0 is not implemented by the HIP optimizer step")
+        if lr_schedule is not None:
+            drops = lr_schedule.drops if isinstance(lr_schedule, TrainPyLR) else lr_schedule.milestones
+            if len(drops) > _lib.OPTIM_MAX_DROPS or lr_schedule.warmup_steps < 1:
+                raise ValueError(f"lr_schedule: at most {_lib.OPTIM_MAX_DROPS} drops / milestones, warmup_steps >= 1")
+        params = [p for g in self.param_groups for p in g["params"]]
+        for p in params:
+            if p.dtype != torch.float32:
+                raise ValueError(f"params: the HIP optimizer step updates fp32 parameters (got {p.dtype}); AMP keeps its parameters in fp32")
+            if p.device != params[0].device:
+                raise ValueError(f"params: all parameters of one optimizer must live on one device (got {params[0].device} and {p.device})")
+            if not p.is_contiguous() and not p.is_contiguous(memory_format=torch.channels_last):
+                raise ValueError("params: parameters must be dense (contiguous or channels_last)")
+        self._fd_schedule = lr_schedule
+        self._fd_device = params[0].device
+        # The state block (fd_optim_state): allocated once, so its address is the same in a capture and in its replays.  Viewed as int64 for the counters.
+        self._fd_state = torch.zeros(_WORDS, dtype=torch.float64, device=self._fd_device)
+        self._fd_state_i = self._fd_state.view(torch.int64)
+        first = lr_schedule.first_step if lr_schedule is not None else 1
+        self._fd_state_i[_word(_F.global_step)] = first - 1
+        self._fd_lr0 = [g["lr"] for g in self.param_groups]
+        if lr_schedule is not None:
+            for i, g in enumerate(self.param_groups):
+                w = _word(_F.lr) + i
+                self._fd_state[w] = float(g["lr"])
+                g["lr"] = self._fd_state[w]            # 0-dim fp64 view: fd_optim_begin overwrites it, logging reads it with .item()
+        self.launches = 0                              # update + begin launches of the last step()
+        self._fd_order = {}                            # id(param group) -> its parameters' indices, largest first
+
+    # ------------------------------------------------------------------ counters
+    @property
+    def global_step(self) -> torch.Tensor:
+        """0-dim int64 device tensor: the step fd_optim_begin evaluated last (the reference's GLOBAL_STEPS)."""
+        return self._fd_state_i[_word(_F.global_step)]
+
+    def set_global_step(self, n: int) -> None:
+        """The next step() evaluates the learning-rate rule at n + 1 (resuming a run; tests).  With a schedule the rate scalars get what the reference's loop
+        would hold after step n, because train.py's rule keeps the previous rate on most steps."""
+        self._fd_state_i[_word(_F.global_step)] = int(n)
+        if self._fd_schedule is not None:
+            for i, lr0 in enumerate(self._fd_lr0):
+                self._fd_state[_word(_F.lr) + i] = self._fd_schedule.at(int(n), float(lr0))
+
+    def _applied(self, i: int) -> torch.Tensor:
+        return self._fd_state_i[_word(_F.applied) + i]
+
+    # ------------------------------------------------------------------ the step
+    def _begin_params(self, active) -> _lib.OptimBeginParams:
+        bp = _lib.OptimBeginParams()
+        bp.n_groups, bp.adam = len(self.param_groups), int(self._ADAM)
+        s = self._fd_schedule
+        if isinstance(s, TrainPyLR):
+            bp.rule, bp.lr_init, bp.warmup_steps, bp.n_drops = _lib.OPTIM_LR_TRAIN_PY, float(s.lr_init), int(s.warmup_steps), len(s.drops)
+            for i, (at_step, factor) in enumerate(s.drops):
+                bp.drop_step[i], bp.drop_factor[i] = int(at_step), float(factor)
+        elif isinstance(s, TrainNewLR):
+            bp.rule, bp.lr_init, bp.warmup_steps, bp.n_drops = _lib.OPTIM_LR_TRAIN_NEW, float(s.lr_init), int(s.warmup_steps), len(s.milestones)
+            bp.warmup_factor, bp.gamma = float(s.warmup_factor), float(s.gamma)
+            for i, m in enumerate(s.milestones):
+                bp.drop_step[i] = int(m)
+        else:
+            bp.rule = _lib.OPTIM_LR_NONE
+        for i, g in enumerate(self.param_groups):
+            bp.active[i] = int(active[i])
+            lr = g["lr"]
+            if s is None:
+                if isinstance(lr, torch.Tensor):
+                    if lr.device != self._fd_device or lr.numel() != 1 or lr.dtype not in (torch.float32, torch.float64):
+                        raise FdError(f"lr: a tensor lr must be one fp32 / fp64 element on {self._fd_device}")
+                    bp.lr_ptr[i], bp.lr_ptr_f64[i] = lr.data_ptr(), int(lr.dtype == torch.float64)
+                else:
+                    bp.lr_value[i] = float(lr)
+            if self._ADAM:
+                b1, b2 = g["betas"]
+                if isinstance(b1, torch.Tensor) or isinstance(b2, torch.Tensor):
+                    raise FdError("betas: tensor betas are not implemented by the HIP optimizer step")
+                bp.beta1[i], bp.beta2[i] = float(b1), float(b2)
+        return bp
+
+    def _state_names(self, group) -> Tuple[str, ...]:
+        raise NotImplementedError
+
+    def _hyper(self, i: int, group) -> _lib.OptimHyper:
+        raise NotImplementedError
+
+    def _gather(self, group):
+        """The live tensors of one group: (params, p / g / state address lists, numels).  Parameters without a gradient are left out and their state is
+        not touched; state tensors are created (zeros) for a parameter the first time it arrives with a gradient, as the parent does."""
+        names = self._state_names(group)
+        ps, pp, gp, sp, ne = [], [], [], [[] for _ in names], []
+        # Largest first, so that the tensors of a chunk are of similar size: a launch's grid follows its largest tensor, and a block past a shorter
+        # tensor's end only exits.  The ORDER is remembered (shapes do not change); every address below is read now.
+        order = self._fd_order.get(id(group))
+        if order is None or len(order) != len(group["params"]):
+            order = self._fd_order[id(group)] = sorted(range(len(group["params"])), key=lambda k: -group["params"][k].numel())
+        for k in order:
+            p = group["params"][k]
+            g = p.grad
+            if g is None:
+                continue
+            if not p.is_cuda:
+                raise FdError("pytorch_object_detection_amd runs on the GPU only (got a CPU parameter); there is no CPU fallback")
+            if g.is_sparse or g.layout != torch.strided:
+                raise FdError("grad: sparse gradients are not implemented by the HIP optimizer step")
+            if g.dtype != torch.float32 or g.device != p.device:
+                raise FdError(f"grad: the HIP optimizer step takes fp32 gradients on the parameter's device (got {g.dtype} on {g.device})")
+            if g.stride() != p.stride() or not (g.is_contiguous() or g.is_contiguous(memory_format=torch.channels_last)):
+                raise FdError(f"grad: a gradient must be dense in its parameter's layout (shape {tuple(g.shape)}, strides {g.stride()} against {p.stride()})")
+            st = self.state[p]
+            for k, name in enumerate(names):
+                s = st.get(name)
+                if s is None:
+                    if torch.cuda.is_current_stream_capturing():
+                        raise FdError(f"{name}: the optimizer state would be created inside a graph capture and zeroed by every replay; run one eager step first")
+                    s = st[name] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                elif s.dtype != torch.float32 or s.device != p.device or s.stride() != p.stride():
+                    raise FdError(f"{name}: state must be fp32 on the parameter's device and in its layout")
+                sp[k].append(s.data_ptr())
+            ps.append(p)
+            pp.append(p.data_ptr())
+            gp.append(g.data_ptr())
+            ne.append(p.numel())
+        return ps, pp, gp, sp, ne
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if self._fd_device.type != "cuda":
+            raise FdError("pytorch_object_detection_amd runs on the GPU only (got CPU parameters); there is no CPU fallback")
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        gathered = [self._gather(g) for g in self.param_groups]
+        with torch.cuda.device(self._fd_device):
+            ops.optim_begin(self._fd_state, found_inf, self._begin_params([bool(t[0]) for t in gathered]))
+            launches, touched = 1, []
+            for i, (group, (ps, pp, gp, sp, ne)) in enumerate(zip(self.param_groups, gathered)):
+                if not ps:
+                    continue
+                launches += ops.optim_update(self._ADAM, pp, gp, sp[0] if len(sp) > 0 else None, sp[1] if len(sp) > 1 else None, ne,
+                                             self._hyper(i, group), self._fd_state, grad_scale)
+                touched += ps
+        self.launches = launches
+        if touched:
+            torch.autograd.graph.increment_version(touched)      # host only: code that keys on _version sees the update
+        return loss
+
+
+class SGD(_HipStep, torch.optim.SGD):
+    """torch.optim.SGD (dampening 0) on fd_optim_sgd_f32.  State key: momentum_buffer (only with momentum != 0), starting as zeros -- with dampening 0 that is
+    torch's 'the first step copies the gradient'."""
+
+    def __init__(self, params, *args, lr_schedule=None, **kwargs):
+        super().__init__(params, *args, **kwargs)
+        self._fd_init(lr_schedule)
+
+    def _state_names(self, group):
+        return ("momentum_buffer",) if group["momentum"] != 0 else ()
+
+    def _hyper(self, i, group):
+        h = _lib.OptimHyper()
+        h.group, h.nesterov, h.momentum, h.weight_decay = i, int(bool(group["nesterov"])), float(group["momentum"]), float(group["weight_decay"])
+        return h
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        _rebind_lr(self)
+        for st in self.state.values():                     # torch.optim.SGD keeps None for a parameter it has not stepped yet
+            if st.get("momentum_buffer", 0) is None:
+                del st["momentum_buffer"]
+
+    def state_dict(self):
+        return _detached_lr(self, super().state_dict())
+
+
+class Adam(_HipStep, torch.optim.Adam):
+    """torch.optim.Adam (no AMSGrad) on fd_optim_adam_f32.  State keys: exp_avg, exp_avg_sq and, in state_dict() only, step: the applied-step count lives once
+    per param group on the device (it does not advance on a step GradScaler skips, as in torch's fused Adam); state_dict() reads it and writes it into every
+    parameter's entry, load_state_dict() takes it back and refuses a group whose entries disagree."""
+    _ADAM = True
+
+    def __init__(self, params, *args, lr_schedule=None, **kwargs):
+        super().__init__(params, *args, **kwargs)
+        self._fd_init(lr_schedule)
+
+    def _state_names(self, group):
+        return ("exp_avg", "exp_avg_sq")
+
+    def _hyper(self, i, group):
+        h = _lib.OptimHyper()
+        h.group, h.decoupled_wd, h.weight_decay, h.eps = i, int(bool(group.get("decoupled_weight_decay", False))), float(group["weight_decay"]), float(group["eps"])
+        h.beta1, h.beta2 = float(group["betas"][0]), float(group["betas"][1])
+        return h
+
+    def state_dict(self):
+        sd = _detached_lr(self, super().state_dict())
+        counts = self._fd_state_i[_word(_F.applied):_word(_F.applied) + len(self.param_groups)].tolist()       # the one host read
+        for gi, g in enumerate(sd["param_groups"]):
+            for idx in g["params"]:
+                if idx in sd["state"]:
+                    sd["state"][idx] = dict(sd["state"][idx], step=torch.tensor(float(counts[gi]), dtype=torch.float32))
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        _rebind_lr(self)
+        for gi, g in enumerate(self.param_groups):
+            steps = set()
+            for p in g["params"]:
+                st = self.state.get(p)
+                if st and "step" in st:
+                    steps.add(float(st.pop("step")))
+            if len(steps) > 1:
+                raise ValueError(f"step: the parameters of param group {gi} carry different step counts {sorted(steps)}; the HIP Adam keeps one per group")
+            self._fd_state_i[_word(_F.applied) + gi] = int(steps.pop()) if steps else 0
+
+
+class AdamW(Adam, torch.optim.AdamW):
+    """torch.optim.AdamW: Adam with decoupled weight decay (p *= 1 - lr * wd before the update)."""
+
+
+def _detached_lr(opt: _HipStep, sd: dict) -> dict:
+    """A scheduled lr is a view of the state block: a state dict gets its value as a tensor of its own."""
+    if opt._fd_schedule is not None:
+        sd["param_groups"] = [dict(g, lr=g["lr"].clone()) if isinstance(g["lr"], torch.Tensor) else g for g in sd["param_groups"]]
+    return sd
+
+
+def _rebind_lr(opt: _HipStep) -> None:
+    """After a load: a scheduled lr is again the view fd_optim_begin writes, holding the loaded value."""
+    if opt._fd_schedule is None:
+        return
+    for i, g in enumerate(opt.param_groups):
+        w = _word(_F.lr) + i
+        view = opt._fd_state[w]
+        if g["lr"] is not view:
+            view.copy_(torch.as_tensor(g["lr"], dtype=torch.float64))
+            g["lr"] = view

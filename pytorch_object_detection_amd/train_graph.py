@@ -7,7 +7,8 @@ recorded with torch.cuda.graph and replayed with one call: 20.4 -> 17.1 ms under
 
 Constraints (those of torch.cuda.graphs): static shapes; inputs are copied into the tensors captured at construction; nothing in `step_fn` may synchronise or read a
 tensor on the host; the optimizer must not synchronise either (torch.optim.SGD(fused=True) / capturable Adam; under GradScaler the fused optimizers take found_inf on
-the device); a learning-rate schedule must write a TENSOR lr in place (a Python float is baked into the recorded launch).  One process per GPU as everywhere else; a
+the device); a learning-rate schedule must write a TENSOR lr in place (a Python float is baked into the recorded launch).  The optimizers of .optim
+(Builder.opt_build(model, hip=True)) meet all of this and carry the reference's learning-rate rule inside the step.  One process per GPU as everywhere else; a
 DistributedDataParallel step is not captured here (its bucket hooks and RCCL launches are left to the eager path).
 """
 from typing import Callable, Sequence
