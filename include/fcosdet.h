@@ -1117,6 +1117,53 @@ int32_t fd_optim_sgd_f32(const fd_optim_chunk* chunk, const fd_optim_hyper* hype
 int32_t fd_optim_adam_f32(const fd_optim_chunk* chunk, const fd_optim_hyper* hyper, const fd_optim_state* state,
                           const float* grad_scale, fd_stream_t stream);
 
+/* Clipping the global gradient norm inside the step.  The gradients are read once more and never written:
+ * the clip coefficient becomes one more factor of the scalar the update launches already divide every gradient by.
+ *   1. fd_grad_sumsq_f32 per chunk of gradients: every block stores ONE fp64 partial into a slot of its own;
+ *   2. fd_grad_clip_finish: one workgroup adds the slots in index order and writes fd_grad_clip;
+ *   3. fd_optim_begin with found_inf = &clip->found;  4. the update launches with grad_scale = &clip->eff_scale.
+ * No floating-point atomics and no block counter: the result does not depend on the order in which blocks run. */
+typedef struct fd_grad_chunk {
+    int32_t n; /* tensors in use, 1 .. FD_OPTIM_MAX_TENSORS */
+    int32_t reserved0;
+    const float* g[FD_OPTIM_MAX_TENSORS]; /* gradient, 4-byte aligned (still multiplied by *grad_scale) */
+    int64_t numel[FD_OPTIM_MAX_TENSORS];  /* 0 is legal: the tensor adds 0.0 and its pointer is not looked at */
+} fd_grad_chunk;
+
+/* The clip block: device memory allocated once (its address must not move between a capture and its replays), written
+ * by fd_grad_clip_finish alone.  fp64 throughout; the three floats are what other launches and the host's logging read. */
+typedef struct fd_grad_clip {
+    double sumsq;         /* sum of g * g over every slot (of the gradients as they are: still scaled) */
+    double total_norm;    /* sqrt(sumsq) / scale, scale = *grad_scale or 1 */
+    double clip_coef;     /* min(1, max_norm / (total_norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s; 1 when found */
+    float eff_scale;      /* (float)(scale / clip_coef): the update launches' grad_scale; the scale itself, bit for bit,
+                             when clip_coef == 1 */
+    float found;          /* 1 when sumsq is not finite or *found_inf != 0, else 0: fd_optim_begin's found_inf */
+    float total_norm_f32; /* (float)total_norm */
+    float reserved0;
+} fd_grad_clip;
+
+/* Slots a chunk's launch writes: n * (blocks per tensor; follows the chunk's largest tensor).  -1: a chunk that
+ * fd_grad_sumsq_f32 refuses.  Host only. */
+int32_t fd_grad_sumsq_slots(const fd_grad_chunk* chunk);
+
+/* Bytes of partials that n_chunks launches can need at most (-1: n_chunks < 0); 8-byte aligned, never cleared. */
+int64_t fd_grad_norm_workspace_bytes(int32_t n_chunks);
+
+/* One chunk: blockIdx.y = tensor, blockIdx.x grid-strides over it with 16-byte loads after a scalar head up to the
+ * boundary, scalar tail; each lane accumulates (double)g * g in fp64; fixed reduction across the wave, then across the
+ * four waves through LDS; block (x, tensor) stores partials[first_slot + tensor * blocks_x + x], 0.0 when it met no
+ * element (blocks_x follows the chunk's largest tensor, one block per 4096 elements up to 128; a shorter tensor is
+ * shared among its first ceil(numel / 4096) blocks).  Writes fd_grad_sumsq_slots(chunk) slots from first_slot on.
+ * FD_E_INVAL: a null chunk / partials, n outside [1, FD_OPTIM_MAX_TENSORS], a negative numel, a null or not 4-byte
+ * aligned g of a tensor with numel > 0, a negative first_slot. */
+int32_t fd_grad_sumsq_f32(const fd_grad_chunk* chunk, double* partials, int32_t first_slot, fd_stream_t stream);
+
+/* One workgroup over partials[0 .. n_slots) (n_slots == 0: no gradient, a norm of 0).  grad_scale / found_inf: device
+ * fp32 scalars or NULL.  FD_E_INVAL: null partials / out, n_slots < 0, max_norm not positive or not finite. */
+int32_t fd_grad_clip_finish(const double* partials, int32_t n_slots, const float* grad_scale, const float* found_inf,
+                            double max_norm, fd_grad_clip* out, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,17 @@ class OptimBeginParams(C.Structure):
                 ("lr_value", C.c_double * OPTIM_MAX_GROUPS), ("lr_ptr", C.c_void_p * OPTIM_MAX_GROUPS), ("lr_ptr_f64", C.c_int32 * OPTIM_MAX_GROUPS),
                 ("active", C.c_int32 * OPTIM_MAX_GROUPS), ("beta1", C.c_double * OPTIM_MAX_GROUPS), ("beta2", C.c_double * OPTIM_MAX_GROUPS)]
 
+
+class GradChunk(C.Structure):
+    """fd_grad_chunk: the gradients of one sum-of-squares launch, passed to the kernel by value."""
+    _fields_ = [("n", C.c_int32), ("reserved0", C.c_int32), ("g", C.c_void_p * OPTIM_MAX_TENSORS), ("numel", C.c_int64 * OPTIM_MAX_TENSORS)]
+
+
+class GradClip(C.Structure):
+    """fd_grad_clip: the clip block on the device, written by fd_grad_clip_finish.  Never instantiated on the host: optim.py views the fields."""
+    _fields_ = [("sumsq", C.c_double), ("total_norm", C.c_double), ("clip_coef", C.c_double), ("eff_scale", C.c_float), ("found", C.c_float),
+                ("total_norm_f32", C.c_float), ("reserved0", C.c_float)]
+
 _lib = None
 
 _P, _I, _F, _D, _L = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_int64
@@ -268,6 +279,10 @@ _SIGS = {
     "fd_optim_begin": (_I, [_P, _P, C.POINTER(OptimBeginParams), _P]),
     "fd_optim_sgd_f32": (_I, [C.POINTER(OptimChunk), C.POINTER(OptimHyper), _P, _P, _P]),
     "fd_optim_adam_f32": (_I, [C.POINTER(OptimChunk), C.POINTER(OptimHyper), _P, _P, _P]),
+    "fd_grad_sumsq_slots": (_I, [C.POINTER(GradChunk)]),
+    "fd_grad_norm_workspace_bytes": (_L, [_I]),
+    "fd_grad_sumsq_f32": (_I, [C.POINTER(GradChunk), _P, _I, _P]),
+    "fd_grad_clip_finish": (_I, [_P, _I, _P, _P, _D, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

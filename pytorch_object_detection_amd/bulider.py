@@ -49,7 +49,8 @@ class Builder:
 
     def opt_build(self, model: nn.Module, hip: bool = False) -> torch.optim.Optimizer:
         """hip=True: the optimizer of that name from .optim (step() on HIP kernels, capture-safe, GradScaler without a host read) with train.py's learning-rate
-        rule for the block's `lr` evaluated on the device; the default is the stock torch optimizer the reference builds."""
+        rule for the block's `lr` evaluated on the device, and the block's `max_grad_norm` when it has that key (clipping inside the step; the shipped configs
+        do not); the default is the stock torch optimizer the reference builds."""
         opt = self._block()["optimizer"]
         make = (_hip_optimizers() if hip else _OPTIMIZERS).get(opt["name"])
         if make is None:
@@ -59,8 +60,11 @@ class Builder:
 
 def _hip_optimizers() -> Dict[str, Callable[..., torch.optim.Optimizer]]:
     from . import optim
+
+    def shared(o):
+        return dict(lr=o["lr"], weight_decay=o["weight_decay"], lr_schedule=optim.TrainPyLR(o["lr"]), max_grad_norm=o.get("max_grad_norm"))
     return {
-        "SGD": lambda params, o: optim.SGD(params, lr=o["lr"], momentum=o["momentum"], weight_decay=o["weight_decay"], lr_schedule=optim.TrainPyLR(o["lr"])),
-        "Adam": lambda params, o: optim.Adam(params, lr=o["lr"], weight_decay=o["weight_decay"], lr_schedule=optim.TrainPyLR(o["lr"])),
-        "AdamW": lambda params, o: optim.AdamW(params, lr=o["lr"], weight_decay=o["weight_decay"], lr_schedule=optim.TrainPyLR(o["lr"])),
+        "SGD": lambda params, o: optim.SGD(params, momentum=o["momentum"], **shared(o)),
+        "Adam": lambda params, o: optim.Adam(params, **shared(o)),
+        "AdamW": lambda params, o: optim.AdamW(params, **shared(o)),
     }

@@ -2290,3 +2290,43 @@ def optim_update(adam: bool, p: Sequence[int], g: Sequence[int], s0: Optional[Se
         check(fn(C.byref(c), C.byref(hyper), st, gs, _stream()), what)
         launches += 1
     return launches
+
+
+def grad_sumsq(g: Sequence[int], numel: Sequence[int], partials: torch.Tensor) -> Tuple[int, int]:
+    """fd_grad_sumsq_f32 over a list of gradients given as device addresses, in chunks of _lib.OPTIM_MAX_TENSORS whose pointers travel by value in the kernel
+    arguments: every block stores one fp64 partial into its own slot of `partials` (the optimizer's workspace, fd_grad_norm_workspace_bytes), the chunks'
+    slots one after the other from slot 0.  Nothing is kept across calls.  -> (launches enqueued, slots written)."""
+    _need_gpu(partials)
+    if partials.dtype != torch.float64 or not partials.is_contiguous():
+        raise FdError("grad_sumsq: partials must be the optimizer's contiguous float64 workspace")
+    L = _lib.lib()
+    cap, total, launches, slot = _lib.OPTIM_MAX_TENSORS, len(g), 0, 0
+    ws = partials.data_ptr()
+    for lo in range(0, total, cap):
+        n = min(cap, total - lo)
+        c = _lib.GradChunk()
+        c.n = n
+        c.g[:n], c.numel[:n] = g[lo:lo + n], numel[lo:lo + n]
+        slots = L.fd_grad_sumsq_slots(C.byref(c))
+        if slots >= 0 and slot + slots > partials.numel():
+            raise FdError(f"grad_sumsq: the workspace holds {partials.numel()} slots, the launches need at least {slot + slots}")
+        check(L.fd_grad_sumsq_f32(C.byref(c), ws, slot, _stream()), "fd_grad_sumsq_f32")         # (slots < 0: the same check refuses the chunk here, with its message)
+        launches += 1
+        slot += slots
+    return launches, slot
+
+
+def grad_clip_finish(partials: torch.Tensor, n_slots: int, grad_scale: Optional[torch.Tensor], found_inf: Optional[torch.Tensor], max_norm: float,
+                     clip: torch.Tensor) -> None:
+    """fd_grad_clip_finish: the slots partials[:n_slots] added in index order, then norm, clip coefficient, effective scale and found flag into the
+    optimizer's clip block (fd_grad_clip, a contiguous float64 tensor of its size).  One launch."""
+    _need_gpu(partials, clip, grad_scale, found_inf)
+    if partials.dtype != torch.float64 or not partials.is_contiguous() or not 0 <= int(n_slots) <= partials.numel():
+        raise FdError(f"grad_clip_finish: n_slots = {n_slots} slots of the optimizer's contiguous float64 workspace ({partials.numel()} slots)")
+    if clip.dtype != torch.float64 or not clip.is_contiguous() or clip.numel() * 8 < C.sizeof(_lib.GradClip) or clip.device != partials.device:
+        raise FdError("grad_clip_finish: clip must be the optimizer's contiguous float64 clip block")
+    for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != clip.device):
+            raise FdError(f"grad_clip_finish: {name} must be one fp32 element on the optimizer's device")
+    check(_lib.lib().fd_grad_clip_finish(partials.data_ptr(), int(n_slots), _dptr(grad_scale), _dptr(found_inf), float(max_norm), clip.data_ptr(), _stream()),
+          "fd_grad_clip_finish")

@@ -10,12 +10,17 @@ travel by value in the kernel arguments (include/fcosdet.h "Optimizer step").  E
 gradients are re-allocated by every backward and live elsewhere during a graph capture, so nothing about them is cached.  The step is therefore capture-safe as it
 is (train_graph.GraphedStep); run one eager step first, because the state tensors are created by the first step that sees a gradient.
 
+Clipping the global gradient norm is a constructor argument, max_grad_norm=35.0: step() then first enqueues one sum-of-squares launch per 64 gradients and one
+finish launch that turns them into the clip coefficient, and the update launches divide every gradient by scale / coefficient instead of by the scale -- one
+more read of the gradients, no write to them, no host read.  p.grad is NOT modified: the one difference from torch.nn.utils.clip_grad_norm_.
+
 What stays stock: torch.amp.GradScaler's own inf check and update().  Moving an optimizer goes through state_dict() / load_state_dict() and
 global_step / set_global_step(); pickling or deep-copying the optimizer object itself is not supported (torch's __getstate__ drops the state block).
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple, Tuple
 
 import torch
@@ -72,6 +77,7 @@ class TrainNewLR(NamedTuple):
 
 _WORDS = C.sizeof(_lib.OptimState) // 8
 _F = _lib.OptimState
+_CLIP = _lib.GradClip
 
 
 def _word(field) -> int:
@@ -79,11 +85,18 @@ def _word(field) -> int:
 
 
 class _HipStep:
-    """What the three classes share: the state block, the begin launch, the chunked update launches.  A mixin placed BEFORE the torch optimizer in the bases."""
+    """What the three classes share: the state block, the begin launch, the chunked update launches.  A mixin placed BEFORE the torch optimizer in the bases.
+
+    max_grad_norm (keyword of the three constructors, default None = the step as it is without it): clip the global 2-norm of all gradients of all param groups
+    to this value, with torch.nn.utils.clip_grad_norm_'s coefficient min(1, max_norm / (norm + 1e-6)), inside step().  It is an attribute of the optimizer, not
+    a param-group key and not part of the state dict.  The gradients themselves are never written (p.grad still holds the unclipped, still scaled values after
+    the step); a step whose gradients hold an inf or a NaN is skipped like one GradScaler flags, with or without a scaler.  opt.grad_norm is the unscaled norm of
+    the last step as a device scalar.  The value travels by value in the finish launch: changing opt.max_grad_norm after a graph capture does not reach the
+    replays -- capture again."""
     _step_supports_amp_scaling = True      # torch.amp.GradScaler then leaves grad_scale / found_inf on the optimizer as device tensors and does not read them
     _ADAM = False
 
-    def _fd_init(self, lr_schedule) -> None:
+    def _fd_init(self, lr_schedule, max_grad_norm=None) -> None:
         if lr_schedule is not None and not isinstance(lr_schedule, (TrainPyLR, TrainNewLR)):
             raise ValueError("lr_schedule must be an optim.TrainPyLR, an optim.TrainNewLR or None")
         if len(self.param_groups) > _lib.OPTIM_MAX_GROUPS:
@@ -118,8 +131,20 @@ class _HipStep:
                 w = _word(_F.lr) + i
                 self._fd_state[w] = float(g["lr"])
                 g["lr"] = self._fd_state[w]            # 0-dim fp64 view: fd_optim_begin overwrites it, logging reads it with .item()
-        self.launches = 0                              # update + begin launches of the last step()
+        self.launches = 0                              # launches of the last step(): begin + updates (+ sum-of-squares + finish with max_grad_norm)
         self._fd_order = {}                            # id(param group) -> its parameters' indices, largest first
+        # Clipping: the value travels BY VALUE in the finish launch, so a change after a graph capture does not reach the replays.
+        self._fd_clip = None
+        if max_grad_norm is not None:
+            if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not math.isfinite(max_grad_norm) or max_grad_norm <= 0:
+                raise ValueError(f"max_grad_norm must be a positive finite number or None (got {max_grad_norm!r})")
+            max_grad_norm = float(max_grad_norm)
+            # The clip block (fd_grad_clip) and the partials for the largest possible chunk count, both allocated once: same addresses in a capture and its replays.
+            self._fd_clip = torch.zeros(C.sizeof(_CLIP) // 8, dtype=torch.float64, device=self._fd_device)
+            self._fd_clip_f = self._fd_clip.view(torch.float32)
+            chunks = -(-len(params) // _lib.OPTIM_MAX_TENSORS)
+            self._fd_partials = torch.empty(_lib.lib().fd_grad_norm_workspace_bytes(chunks) // 8, dtype=torch.float64, device=self._fd_device)
+        self.max_grad_norm = max_grad_norm
 
     # ------------------------------------------------------------------ counters
     @property
@@ -134,6 +159,14 @@ class _HipStep:
         if self._fd_schedule is not None:
             for i, lr0 in enumerate(self._fd_lr0):
                 self._fd_state[_word(_F.lr) + i] = self._fd_schedule.at(int(n), float(lr0))
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """0-dim fp32 device tensor, a view of the clip block: the global 2-norm of the UNSCALED gradients of the last step(), before clipping (inf / nan on a
+        step that was skipped for a non-finite gradient).  Only with max_grad_norm."""
+        if self.max_grad_norm is None:
+            raise AttributeError("grad_norm: the optimizer was built without max_grad_norm, its step() does not compute the norm")
+        return self._fd_clip_f[_CLIP.total_norm_f32.offset // 4]
 
     def _applied(self, i: int) -> torch.Tensor:
         return self._fd_state_i[_word(_F.applied) + i]
@@ -227,8 +260,17 @@ class _HipStep:
         grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
         gathered = [self._gather(g) for g in self.param_groups]
         with torch.cuda.device(self._fd_device):
+            launches = 0
+            if self.max_grad_norm is not None:
+                if self._fd_clip is None:
+                    raise FdError("max_grad_norm: the optimizer was built without it; pass it to the constructor, which allocates the clip block")
+                # one global norm over every group's live gradients; from here on the step's scale and skip flag are the clip block's
+                n, slots = ops.grad_sumsq([a for t in gathered for a in t[2]], [k for t in gathered for k in t[4]], self._fd_partials)
+                ops.grad_clip_finish(self._fd_partials, slots, grad_scale, found_inf, self.max_grad_norm, self._fd_clip)
+                launches = n + 1
+                grad_scale, found_inf = self._fd_clip_f[_CLIP.eff_scale.offset // 4], self._fd_clip_f[_CLIP.found.offset // 4]
             ops.optim_begin(self._fd_state, found_inf, self._begin_params([bool(t[0]) for t in gathered]))
-            launches, touched = 1, []
+            launches, touched = launches + 1, []
             for i, (group, (ps, pp, gp, sp, ne)) in enumerate(zip(self.param_groups, gathered)):
                 if not ps:
                     continue
@@ -245,9 +287,9 @@ class SGD(_HipStep, torch.optim.SGD):
     """torch.optim.SGD (dampening 0) on fd_optim_sgd_f32.  State key: momentum_buffer (only with momentum != 0), starting as zeros -- with dampening 0 that is
     torch's 'the first step copies the gradient'."""
 
-    def __init__(self, params, *args, lr_schedule=None, **kwargs):
+    def __init__(self, params, *args, lr_schedule=None, max_grad_norm=None, **kwargs):
         super().__init__(params, *args, **kwargs)
-        self._fd_init(lr_schedule)
+        self._fd_init(lr_schedule, max_grad_norm)
 
     def _state_names(self, group):
         return ("momentum_buffer",) if group["momentum"] != 0 else ()
@@ -274,9 +316,9 @@ class Adam(_HipStep, torch.optim.Adam):
     parameter's entry, load_state_dict() takes it back and refuses a group whose entries disagree."""
     _ADAM = True
 
-    def __init__(self, params, *args, lr_schedule=None, **kwargs):
+    def __init__(self, params, *args, lr_schedule=None, max_grad_norm=None, **kwargs):
         super().__init__(params, *args, **kwargs)
-        self._fd_init(lr_schedule)
+        self._fd_init(lr_schedule, max_grad_norm)
 
     def _state_names(self, group):
         return ("exp_avg", "exp_avg_sq")
