@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's train.py:97-181 loop on the MI355X path, with synthetic VOC-shaped batches.
 
-    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-optim]
+    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-optim] [--ema 0.999]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_like_train_py.py   # DDP / RCCL
 
 Same objects and call order as the reference: HalfInvertedStageFCOS([512, 1024, 2048], 20, 256), FCOSGenTargets,
@@ -14,7 +14,8 @@ with model.enable_training() (which also freezes the Cin = 3 stem: the optimizer
 (fd_stem7x7_bwd_weight_nhwc4) instead: MNFCOS keeps the stem trainable (enable_training(train_stem=True)), HISFCOS un-freezes conv1 and sets
 enable_stem_training() -- without the option a trainable stem runs on stock ops.  --hip-optim takes the optimizer from pytorch_object_detection_amd.optim:
 step() on the HIP update kernels, GradScaler without a host read, and the warm-up / drop lines of train.py:160-173 evaluated on the device (optim.TrainPyLR)
-instead of the host lines below.
+instead of the host lines below.  --ema DECAY (with --hip-optim) keeps an exponential moving average of the weights in optim.AveragedModel, updated on the
+device after every scaler.step(optimizer) -- a step GradScaler skips leaves it untouched -- and runs the averaged copy, avg.module, in eval mode at the end.
 """
 import argparse
 import os
@@ -39,7 +40,10 @@ def main():
     ap.add_argument("--model", choices=["HISFCOS", "MNFCOS"], default="HISFCOS")
     ap.add_argument("--hip-stem", action="store_true", help="train the 7x7 stem (conv1) on its HIP forward / weight-gradient node")
     ap.add_argument("--hip-optim", action="store_true", help="optim.SGD with the learning-rate rule on the device instead of torch.optim.SGD and the host lines")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="average the weights on the device (optim.AveragedModel); needs --hip-optim")
     args = ap.parse_args()
+    if args.ema is not None and not args.hip_optim:
+        ap.error("--ema gates on the HIP optimizer's skip flag: pass --hip-optim as well")
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -66,6 +70,8 @@ def main():
         optimizer = optim.SGD(trainable, lr=LR_INIT, momentum=0.9, weight_decay=1e-4, lr_schedule=optim.TrainPyLR(LR_INIT, WARMUP_STEPS))
     else:
         optimizer = torch.optim.SGD(trainable, lr=LR_INIT, momentum=0.9, weight_decay=1e-4)
+    # train.py:125 (commented out there): the averaged copy; pairs by position, so the DDP wrapper's parameters pair with the bare copy's
+    avg = optim.AveragedModel(model.module if world > 1 else model, decay=args.ema, optimizer=optimizer) if args.ema is not None else None
     scaler = torch.amp.GradScaler("cuda", enabled=args.amp)                                         # train.py:133
     criterion = FCOSLoss("giou")
 
@@ -90,6 +96,8 @@ def main():
         scaler.scale(loss.mean()).backward()
         scaler.step(optimizer)
         scaler.update()
+        if avg is not None:
+            avg.update_parameters(model)                                                            # train.py:203; after the step: the gate reads its skip flag
         if step == 3:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -100,6 +108,10 @@ def main():
     if rank == 0 and t0 is not None and args.steps > 3:
         dt = (time.perf_counter() - t0) / (args.steps - 3)
         print(f"{dt * 1e3:.1f} ms/step, {args.batch * world / dt:.1f} img/s over {world} GPU(s)")
+    if avg is not None and rank == 0:
+        with torch.no_grad():
+            cls_logits = avg.module.eval()(imgs)[0]                                                 # the averaged weights, on their own plans
+        print(f"averaged model after {int(avg.n_averaged)} updates: largest class logit {max(float(t.max()) for t in cls_logits):.4f}")
     if world > 1:
         dist.destroy_process_group()
 

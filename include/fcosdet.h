@@ -1164,6 +1164,82 @@ int32_t fd_grad_sumsq_f32(const fd_grad_chunk* chunk, double* partials, int32_t 
 int32_t fd_grad_clip_finish(const double* partials, int32_t n_slots, const float* grad_scale, const float* found_inf,
                             double max_norm, fd_grad_clip* out, fd_stream_t stream);
 
+/* Averaging the model's weights (torch.optim.swa_utils.AveragedModel: SWA, the equal average, and EMA).
+ *
+ * One update is ONE begin launch, one fd_avg_update_f32 launch per chunk of averaged fp32 tensors and one
+ * fd_avg_copy_bytes launch per chunk of buffers that are copied instead.  As in the optimizer step the tensor lists
+ * travel BY VALUE in the kernel arguments: nothing on the device outlives the launch, a capture records the arguments as
+ * they are, and no launch makes the host read the device.
+ *
+ * fd_avg_state is the averager's own block of device memory (allocated once: its address must not move between a capture
+ * and its replays).  Only the begin launch writes it; the update and copy launches only read it. */
+#define FD_AVG_SWA 0 /* equal average: weight = 1 / (n_averaged + 1) */
+#define FD_AVG_EMA 1 /* exponential moving average: weight = 1 - decay */
+
+typedef struct fd_avg_state {
+    int64_t apply;    /* 1: this call averages; 0: its update / copy launches write nothing */
+    double weight;    /* blend factor of this call (0 when apply == 0) */
+    float weight_f32; /* (float)weight: what the update launches multiply by */
+    float reserved0;
+    int64_t reserved1; /* up to a multiple of 16 bytes */
+} fd_avg_state;
+
+typedef struct fd_avg_begin_params {
+    int32_t mode; /* FD_AVG_SWA / FD_AVG_EMA */
+    int32_t reserved0;
+    double decay;       /* EMA, in [0, 1] */
+    int64_t start_step; /* the gate on *global_step: averages when *global_step >= start_step ... */
+    int64_t every;      /* ... and (*global_step - start_step) % every == 0; >= 1 */
+} fd_avg_begin_params;
+
+/* One launch, one lane.  n_averaged: the module's int64 device scalar.  skip / global_step: device pointers into an
+ * optimizer's fd_optim_state, &state->skip and &state->global_step (the step the optimizer evaluated LAST, so the update
+ * follows the optimizer's step), or NULL.
+ *   apply = !(skip && *skip) && (global_step == NULL || (*global_step >= start_step && (*global_step - start_step) % every == 0))
+ *   apply:  weight = *n_averaged == 0 ? 1.0 : (mode == FD_AVG_SWA ? 1.0 / (double)(*n_averaged + 1) : 1.0 - decay);
+ *           weight_f32 = (float)weight;  *n_averaged += 1.
+ *   else:   weight = 0, *n_averaged untouched.
+ * FD_E_INVAL: a null state / n_averaged / params, a mode outside the two, decay outside [0, 1] or not finite,
+ * every < 1, global_step == NULL with start_step != 0 or every != 1. */
+int32_t fd_avg_begin(fd_avg_state* state, int64_t* n_averaged, const int64_t* skip, const int64_t* global_step,
+                     const fd_avg_begin_params* params, fd_stream_t stream);
+
+typedef struct fd_avg_chunk {
+    int32_t n; /* tensors in use, 1 .. FD_OPTIM_MAX_TENSORS */
+    int32_t reserved0;
+    float* avg[FD_OPTIM_MAX_TENSORS];     /* the averaged copy */
+    const float* p[FD_OPTIM_MAX_TENSORS]; /* the model's tensor */
+    int64_t numel[FD_OPTIM_MAX_TENSORS];  /* 0 is legal: the tensor is skipped and its pointers are not looked at */
+} fd_avg_chunk;                           /* 64 * 24 B + 8 B = 1544 B of the 4 KB kernel-argument segment */
+
+/* One chunk of fp32 tensors, blockIdx.y = tensor, blockIdx.x grid-strides over its elements, 256 lanes; the grid's x extent
+ * follows the chunk's largest tensor (capped as in the optimizer kernels), a block past a shorter tensor's end exits.
+ * 16-byte accesses where avg and p share one alignment (scalar head up to the boundary, scalar tail), scalar accesses where
+ * they do not.  12 B per element, no LDS, no atomics.
+ *   state->apply == 0:          nothing is written.
+ *   state->weight_f32 == 1.0f:  avg = p bit for bit, NaN payloads included (the first update; decay == 0).
+ *   otherwise:                  avg = avg + (p - avg) * weight_f32 in fp32, in that order, without FMA contraction.
+ * So an element with p == avg comes back unchanged ((p - avg) is 0): tensors that never train stay identical to the
+ * model's (a -0.0 comes back as +0.0, the sum of two zeros of opposite sign).
+ * FD_E_INVAL: a null chunk / state, n outside [1, FD_OPTIM_MAX_TENSORS], a negative numel, a null or not 4-byte aligned
+ * avg / p of a tensor with numel > 0. */
+int32_t fd_avg_update_f32(const fd_avg_chunk* chunk, const fd_avg_state* state, fd_stream_t stream);
+
+typedef struct fd_avg_copy_chunk {
+    int32_t n; /* buffers in use, 1 .. FD_OPTIM_MAX_TENSORS */
+    int32_t reserved0;
+    void* dst[FD_OPTIM_MAX_TENSORS];
+    const void* src[FD_OPTIM_MAX_TENSORS];
+    int64_t nbytes[FD_OPTIM_MAX_TENSORS]; /* 0 is legal */
+} fd_avg_copy_chunk;
+
+/* Buffers that are copied, not averaged (integer buffers such as BatchNorm's 0-dim int64 num_batches_tracked; every buffer
+ * without use_buffers): dst = src exactly, at any alignment, gated by the same state->apply.  The launch shape is
+ * fd_avg_update_f32's: 16-byte accesses where dst and src share one alignment (byte head and tail), bytes where not.
+ * FD_E_INVAL: a null chunk / state, n outside [1, FD_OPTIM_MAX_TENSORS], a negative nbytes, a null dst / src of a buffer
+ * with nbytes > 0. */
+int32_t fd_avg_copy_bytes(const fd_avg_copy_chunk* chunk, const fd_avg_state* state, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

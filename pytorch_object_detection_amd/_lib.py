@@ -157,6 +157,30 @@ class GradClip(C.Structure):
     _fields_ = [("sumsq", C.c_double), ("total_norm", C.c_double), ("clip_coef", C.c_double), ("eff_scale", C.c_float), ("found", C.c_float),
                 ("total_norm_f32", C.c_float), ("reserved0", C.c_float)]
 
+
+AVG_SWA, AVG_EMA = 0, 1                                                   # include/fcosdet.h FD_AVG_*
+
+
+class AvgState(C.Structure):
+    """fd_avg_state: the averager's device block, written by fd_avg_begin.  Never instantiated on the host: optim.py allocates sizeof() bytes on the device."""
+    _fields_ = [("apply", C.c_int64), ("weight", C.c_double), ("weight_f32", C.c_float), ("reserved0", C.c_float), ("reserved1", C.c_int64)]
+
+
+class AvgBeginParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("reserved0", C.c_int32), ("decay", C.c_double), ("start_step", C.c_int64), ("every", C.c_int64)]
+
+
+class AvgChunk(C.Structure):
+    """fd_avg_chunk: up to OPTIM_MAX_TENSORS (averaged copy, model tensor) pairs of one update launch, passed to the kernel by value."""
+    _fields_ = [("n", C.c_int32), ("reserved0", C.c_int32), ("avg", C.c_void_p * OPTIM_MAX_TENSORS), ("p", C.c_void_p * OPTIM_MAX_TENSORS),
+                ("numel", C.c_int64 * OPTIM_MAX_TENSORS)]
+
+
+class AvgCopyChunk(C.Structure):
+    """fd_avg_copy_chunk: the buffers of one copy launch, passed to the kernel by value."""
+    _fields_ = [("n", C.c_int32), ("reserved0", C.c_int32), ("dst", C.c_void_p * OPTIM_MAX_TENSORS), ("src", C.c_void_p * OPTIM_MAX_TENSORS),
+                ("nbytes", C.c_int64 * OPTIM_MAX_TENSORS)]
+
 _lib = None
 
 _P, _I, _F, _D, _L = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_int64
@@ -283,6 +307,9 @@ _SIGS = {
     "fd_grad_norm_workspace_bytes": (_L, [_I]),
     "fd_grad_sumsq_f32": (_I, [C.POINTER(GradChunk), _P, _I, _P]),
     "fd_grad_clip_finish": (_I, [_P, _I, _P, _P, _D, _P, _P]),
+    "fd_avg_begin": (_I, [_P, _P, _P, _P, C.POINTER(AvgBeginParams), _P]),
+    "fd_avg_update_f32": (_I, [C.POINTER(AvgChunk), _P, _P]),
+    "fd_avg_copy_bytes": (_I, [C.POINTER(AvgCopyChunk), _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

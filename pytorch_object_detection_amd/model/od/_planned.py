@@ -1,6 +1,7 @@
 """Shared plumbing of the detector modules: plan cache, input checks, pyramid-aware output lists."""
 from __future__ import annotations
 
+import copy
 from typing import Callable, Dict, List, Tuple
 
 import torch
@@ -56,6 +57,17 @@ class PlannedModule(nn.Module):
 
     def invalidate_plans(self) -> None:
         self._plans.clear()
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy(model) (torch.optim.swa_utils.AveragedModel, optim.AveragedModel): parameters, buffers, sub-modules and the plain-attribute
+        switches (conv_precision, hip_bn_train, ...) are copied as for any nn.Module; the plan cache is NOT -- a plan holds ctypes structures and pooled
+        device buffers bound to this module's tensors.  The copy starts with an empty cache and builds its own plans on its first forward; this module's
+        plans stay as they are."""
+        new = self.__class__.__new__(self.__class__)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            new.__dict__[k] = {} if k == "_plans" else copy.deepcopy(v, memo)
+        return new
 
     max_plan_batch = None    # optional cap on the images one plan handles (larger batches run as consecutive sub-batches)
     _largest_map_channels = 64   # channels of the widest stride-2 activation (ResNet stem: 64)

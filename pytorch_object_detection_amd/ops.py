@@ -2330,3 +2330,48 @@ def grad_clip_finish(partials: torch.Tensor, n_slots: int, grad_scale: Optional[
             raise FdError(f"grad_clip_finish: {name} must be one fp32 element on the optimizer's device")
     check(_lib.lib().fd_grad_clip_finish(partials.data_ptr(), int(n_slots), _dptr(grad_scale), _dptr(found_inf), float(max_norm), clip.data_ptr(), _stream()),
           "fd_grad_clip_finish")
+
+
+def avg_begin(state: torch.Tensor, n_averaged: torch.Tensor, skip: Optional[torch.Tensor], global_step: Optional[torch.Tensor],
+              params: _lib.AvgBeginParams) -> None:
+    """fd_avg_begin on the averager's state block (optim.AveragedModel): the gate (skip / global_step: 0-dim int64 views of an optimizer's state block, or
+    None), this call's blend factor, n_averaged += 1 when it applies.  One launch."""
+    _need_gpu(state, n_averaged, skip, global_step)
+    if state.dtype != torch.float64 or not state.is_contiguous() or state.numel() * 8 < C.sizeof(_lib.AvgState):
+        raise FdError("avg_begin: state must be the averager's contiguous float64 block")
+    for name, t in (("n_averaged", n_averaged), ("skip", skip), ("global_step", global_step)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != 1 or t.device != state.device):
+            raise FdError(f"avg_begin: {name} must be one int64 element on the averager's device ({state.device})")
+    check(_lib.lib().fd_avg_begin(state.data_ptr(), n_averaged.data_ptr(), _dptr(skip), _dptr(global_step), C.byref(params), _stream()), "fd_avg_begin")
+
+
+def avg_update(avg: Sequence[int], p: Sequence[int], numel: Sequence[int], state: torch.Tensor) -> int:
+    """fd_avg_update_f32 over a list of (averaged copy, model tensor) pairs given as device addresses, in chunks of _lib.OPTIM_MAX_TENSORS whose pointers
+    travel by value in the kernel arguments.  Nothing is kept across calls.  -> launches enqueued."""
+    _need_gpu(state)
+    fn, st = _lib.lib().fd_avg_update_f32, state.data_ptr()
+    cap, total, launches = _lib.OPTIM_MAX_TENSORS, len(avg), 0
+    for lo in range(0, total, cap):
+        n = min(cap, total - lo)
+        c = _lib.AvgChunk()
+        c.n = n
+        c.avg[:n], c.p[:n], c.numel[:n] = avg[lo:lo + n], p[lo:lo + n], numel[lo:lo + n]
+        check(fn(C.byref(c), st, _stream()), "fd_avg_update_f32")
+        launches += 1
+    return launches
+
+
+def avg_copy(dst: Sequence[int], src: Sequence[int], nbytes: Sequence[int], state: torch.Tensor) -> int:
+    """fd_avg_copy_bytes over a list of (destination, source) buffers given as device addresses and byte counts, chunked like avg_update and gated by the
+    same state block.  -> launches enqueued."""
+    _need_gpu(state)
+    fn, st = _lib.lib().fd_avg_copy_bytes, state.data_ptr()
+    cap, total, launches = _lib.OPTIM_MAX_TENSORS, len(dst), 0
+    for lo in range(0, total, cap):
+        n = min(cap, total - lo)
+        c = _lib.AvgCopyChunk()
+        c.n = n
+        c.dst[:n], c.src[:n], c.nbytes[:n] = dst[lo:lo + n], src[lo:lo + n], nbytes[lo:lo + n]
+        check(fn(C.byref(c), st, _stream()), "fd_avg_copy_bytes")
+        launches += 1
+    return launches

@@ -14,6 +14,9 @@ Clipping the global gradient norm is a constructor argument, max_grad_norm=35.0:
 finish launch that turns them into the clip coefficient, and the update launches divide every gradient by scale / coefficient instead of by the scale -- one
 more read of the gradients, no write to them, no host read.  p.grad is NOT modified: the one difference from torch.nn.utils.clip_grad_norm_.
 
+Averaging the weights (SWA / EMA) is optim.AveragedModel at the end of this file: torch.optim.swa_utils.AveragedModel on the same terms -- no host read, the
+optimizer's skip flag honoured, capture-safe.
+
 What stays stock: torch.amp.GradScaler's own inf check and update().  Moving an optimizer goes through state_dict() / load_state_dict() and
 global_step / set_global_step(); pickling or deep-copying the optimizer object itself is not supported (torch's __getstate__ drops the state block).
 """
@@ -24,6 +27,7 @@ import math
 from typing import NamedTuple, Tuple
 
 import torch
+import torch.optim.swa_utils
 
 from . import _lib, ops
 from ._lib import FdError
@@ -373,3 +377,129 @@ def _rebind_lr(opt: _HipStep) -> None:
         if g["lr"] is not view:
             view.copy_(torch.as_tensor(g["lr"], dtype=torch.float64))
             g["lr"] = view
+
+
+_AVG_WORDS = C.sizeof(_lib.AvgState) // 8
+
+
+def _dense(t: torch.Tensor) -> bool:
+    return t.layout == torch.strided and (t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)))
+
+
+class AveragedModel(torch.optim.swa_utils.AveragedModel):
+    """torch.optim.swa_utils.AveragedModel whose update_parameters() never reads the device (include/fcosdet.h "Averaging the model's weights").
+
+        avg = optim.AveragedModel(model, decay=0.999, optimizer=opt)            # EMA; decay=None: SWA, the equal average of the parent's default
+        scaler.step(opt); scaler.update(); avg.update_parameters(model)         # after the optimizer's step; evaluate avg.module
+
+    .module (a deep copy of the model), .n_averaged (registered 0-dim int64 buffer), .use_buffers, forward and the state-dict keys (n_averaged + module.*) are
+    the parent's, so checkpoints move both ways.  One difference: n_averaged is created on the device of the copy's parameters (the parent leaves it on the CPU
+    unless device= is given), because the begin launch increments it.
+
+    One update is one fd_avg_begin launch (the gate, this call's blend factor, n_averaged += 1), one fd_avg_update_f32 launch per 64 averaged fp32 tensors
+    (avg = avg + (p - avg) * w in fp32; the first applied update copies) and one fd_avg_copy_bytes launch per 64 copied buffers; every address is read from the
+    live tensors inside the call and travels by value in the kernel arguments, so the call can be recorded into a HIP graph with the optimizer's step.
+
+    decay=None: weight 1 / (n_averaged + 1) (get_swa_multi_avg_fn); decay=d in [0, 1]: weight 1 - d (get_ema_multi_avg_fn(d)).  A callable avg_fn / multi_avg_fn
+    is refused: Python cannot run inside the launch.
+    optimizer=: one of this module's SGD / Adam / AdamW.  The begin launch then reads that optimizer's skip flag and global step on the device: a step that
+    GradScaler or clipping skipped leaves the average and n_averaged untouched, and start_step / every gate the update (it applies when
+    global_step >= start_step and (global_step - start_step) % every == 0 -- SWA from step N, every k steps).  The gate compares against the step the optimizer
+    evaluated LAST, so call update_parameters() after opt.step() / scaler.step(opt).  Without optimizer every call averages, as in the parent.
+    decay, start_step and every travel by value in the begin launch: changing them after a graph capture does not reach the replays -- capture again.
+
+    Buffers: use_buffers=False (default) copies every buffer from the model on every applied call; use_buffers=True averages the floating buffers with the
+    parameters and COPIES the integer ones (BatchNorm's num_batches_tracked).  The parent pushes integer buffers through a truncating blend, an accident of
+    its non-floating fallback branch; that is not followed.
+
+    Refused: non-fp32 floating tensors, pairs whose shapes / strides / devices differ, non-dense tensors, CPU tensors (there is no CPU fallback), a model with
+    more tensors than the copy.  Not here: update_bn, SWALR, a decay warm-up, averaging in fp64.  Moving an averaged model goes through state_dict() /
+    load_state_dict(); with optimizer= the object itself can be neither pickled nor deep-copied, as the optimizer cannot."""
+
+    def __init__(self, model, device=None, avg_fn=None, multi_avg_fn=None, use_buffers=False, *, decay=None, optimizer=None, start_step=0, every=1):
+        for name, fn in (("avg_fn", avg_fn), ("multi_avg_fn", multi_avg_fn)):
+            if fn is not None:
+                raise ValueError(f"{name}: a Python callable cannot run inside the launch; pass decay= (EMA) or leave it None (SWA, the equal average)")
+        if decay is not None:
+            if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not math.isfinite(decay) or not 0.0 <= decay <= 1.0:
+                raise ValueError(f"decay must be a number in [0, 1] or None (got {decay!r})")
+            decay = float(decay)
+        if optimizer is not None and not isinstance(optimizer, _HipStep):
+            raise ValueError(f"optimizer must be one of this module's SGD / Adam / AdamW (got {type(optimizer).__name__}): the gate reads its device state block")
+        for name, v, lo in (("start_step", start_step, None), ("every", every, 1)):
+            if isinstance(v, bool) or not isinstance(v, int) or (lo is not None and v < lo):
+                raise ValueError(f"{name} must be an integer" + (f" >= {lo}" if lo is not None else "") + f" (got {v!r})")
+        if optimizer is None and (start_step != 0 or every != 1):
+            raise ValueError("start_step / every gate on an optimizer's global step: pass optimizer= as well")
+        super().__init__(model, device, None, None, use_buffers)
+        self.decay, self.start_step, self.every = decay, int(start_step), int(every)
+        self._fd_opt = [optimizer]                         # in a list: not a sub-module, not part of the state dict
+        first = next(iter(self.module.parameters()), None)
+        if device is None and first is not None:
+            self.n_averaged = self.n_averaged.to(first.device)
+        self._fd_state = None                              # fd_avg_state on n_averaged's device, allocated by the first update
+        self._fd_order = None
+        self.launches = 0                                  # launches of the last update_parameters(): begin + updates + copies
+
+    def _begin_params(self) -> _lib.AvgBeginParams:
+        bp = _lib.AvgBeginParams()
+        bp.mode, bp.decay = (_lib.AVG_SWA, 0.0) if self.decay is None else (_lib.AVG_EMA, float(self.decay))
+        bp.start_step, bp.every = int(self.start_step), int(self.every)
+        return bp
+
+    def _pairs(self, model):
+        """The live tensors of one update: (averaged pairs, copied pairs), each a list of (copy's tensor, model's tensor) in the parent's pairing."""
+        mine_p, theirs_p = list(self.module.parameters()), list(model.parameters())
+        mine_b, theirs_b = list(self.module.buffers()), list(model.buffers())
+        if len(theirs_p) > len(mine_p) or len(theirs_b) != len(mine_b):
+            raise ValueError(f"model: {len(theirs_p)} parameters / {len(theirs_b)} buffers against {len(mine_p)} / {len(mine_b)} on the averaged copy")
+        averaged, copied = list(zip(mine_p, theirs_p)), []
+        for a, b in zip(mine_b, theirs_b):
+            (averaged if self.use_buffers and a.is_floating_point() else copied).append((a, b))
+        dev = self.n_averaged.device
+        for kind, pairs in (("averaged", averaged), ("copied", copied)):
+            for a, b in pairs:
+                if not a.is_cuda or not b.is_cuda:
+                    raise FdError("model: pytorch_object_detection_amd runs on the GPU only (got a CPU tensor); there is no CPU fallback")
+                if a.device != dev or b.device != dev:
+                    raise ValueError(f"model: every tensor must live on n_averaged's device {dev} (got {a.device} and {b.device})")
+                if kind == "averaged" and (a.dtype != torch.float32 or b.dtype != torch.float32):
+                    raise ValueError(f"model: the averaging kernel takes fp32 tensors (got {a.dtype} and {b.dtype}, shape {tuple(a.shape)})")
+                if a.dtype != b.dtype or a.shape != b.shape or a.stride() != b.stride():
+                    raise ValueError(f"model: a pair differs in dtype / shape / strides ({a.dtype} {tuple(a.shape)} {a.stride()} against "
+                                     f"{b.dtype} {tuple(b.shape)} {b.stride()})")
+                if not _dense(a) or not _dense(b):
+                    raise ValueError(f"model: tensors must be dense (contiguous or channels_last; shape {tuple(a.shape)}, strides {a.stride()})")
+        return averaged, copied
+
+    @torch.no_grad()
+    def update_parameters(self, model) -> None:
+        n = self.n_averaged                                # the live buffer: .to() / load_state_dict may have moved it
+        averaged, copied = self._pairs(model)
+        if not n.is_cuda:
+            raise FdError("n_averaged: pytorch_object_detection_amd runs on the GPU only (the averaged model is on the CPU); there is no CPU fallback")
+        if self._fd_state is None or self._fd_state.device != n.device:
+            if torch.cuda.is_current_stream_capturing():
+                raise FdError("update_parameters: the state block would be allocated inside a graph capture; run one eager update first")
+            self._fd_state = torch.zeros(_AVG_WORDS, dtype=torch.float64, device=n.device)
+        # Largest first, so that the tensors of a launch are of similar size (its grid follows the largest).  The ORDER is remembered; every address is read now.
+        sig = (len(averaged), len(copied))
+        if self._fd_order is None or self._fd_order[0] != sig:
+            self._fd_order = (sig, sorted(range(len(averaged)), key=lambda k: -averaged[k][0].numel()),
+                              sorted(range(len(copied)), key=lambda k: -copied[k][0].numel() * copied[k][0].element_size()))
+        averaged, copied = [averaged[k] for k in self._fd_order[1]], [copied[k] for k in self._fd_order[2]]
+        opt = self._fd_opt[0]
+        skip = opt._fd_state_i[_word(_F.skip)] if opt is not None else None
+        step = opt._fd_state_i[_word(_F.global_step)] if opt is not None else None
+        with torch.cuda.device(n.device):
+            ops.avg_begin(self._fd_state, n, skip, step, self._begin_params())
+            launches = 1
+            if averaged:
+                launches += ops.avg_update([a.data_ptr() for a, _ in averaged], [b.data_ptr() for _, b in averaged], [a.numel() for a, _ in averaged],
+                                           self._fd_state)
+            if copied:
+                launches += ops.avg_copy([a.data_ptr() for a, _ in copied], [b.data_ptr() for _, b in copied],
+                                         [a.numel() * a.element_size() for a, _ in copied], self._fd_state)
+        self.launches = launches
+        # host only: the averaged module's plans and folded BatchNorms key on _version and re-pack on its next forward
+        torch.autograd.graph.increment_version([n] + [a for a, _ in averaged] + [a for a, _ in copied])
