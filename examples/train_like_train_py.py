@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's train.py:97-181 loop on the MI355X path, with synthetic VOC-shaped batches.
 
-    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-optim] [--ema 0.999]
+    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-optim] [--ema 0.999] [--update-bn 8]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_like_train_py.py   # DDP / RCCL
 
 Same objects and call order as the reference: HalfInvertedStageFCOS([512, 1024, 2048], 20, 256), FCOSGenTargets,
@@ -16,6 +16,9 @@ enable_stem_training() -- without the option a trainable stem runs on stock ops.
 step() on the HIP update kernels, GradScaler without a host read, and the warm-up / drop lines of train.py:160-173 evaluated on the device (optim.TrainPyLR)
 instead of the host lines below.  --ema DECAY (with --hip-optim) keeps an exponential moving average of the weights in optim.AveragedModel, updated on the
 device after every scaler.step(optimizer) -- a step GradScaler skips leaves it untouched -- and runs the averaged copy, avg.module, in eval mode at the end.
+--update-bn N (with --ema) first runs optim.update_bn over N synthetic batches: the averaged copy holds averaged weights but only copied running
+statistics, and its FPN BatchNorms run on batch statistics; update_bn recomputes exactly those on the HIP kernels (every rank passes its own batches under
+DDP: the statistics are global) and leaves the frozen backbone's alone.
 """
 import argparse
 import os
@@ -41,9 +44,13 @@ def main():
     ap.add_argument("--hip-stem", action="store_true", help="train the 7x7 stem (conv1) on its HIP forward / weight-gradient node")
     ap.add_argument("--hip-optim", action="store_true", help="optim.SGD with the learning-rate rule on the device instead of torch.optim.SGD and the host lines")
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="average the weights on the device (optim.AveragedModel); needs --hip-optim")
+    ap.add_argument("--update-bn", type=int, default=0, metavar="N",
+                    help="recompute the averaged copy's batch-statistics BatchNorms over N batches before its eval forward (optim.update_bn); needs --ema")
     args = ap.parse_args()
     if args.ema is not None and not args.hip_optim:
         ap.error("--ema gates on the HIP optimizer's skip flag: pass --hip-optim as well")
+    if args.update_bn < 0 or (args.update_bn and args.ema is None):
+        ap.error("--update-bn N (N >= 1) recomputes the statistics of the averaged model: pass --ema as well")
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -108,6 +115,10 @@ def main():
     if rank == 0 and t0 is not None and args.steps > 3:
         dt = (time.perf_counter() - t0) / (args.steps - 3)
         print(f"{dt * 1e3:.1f} ms/step, {args.batch * world / dt:.1f} img/s over {world} GPU(s)")
+    if avg is not None and args.update_bn:                      # on every rank: SyncBatchNorm's statistics are collective
+        optim.update_bn((torch.randn(args.batch, 3, 512, 512, generator=g, device=dev) for _ in range(args.update_bn)), avg)
+        if rank == 0:
+            print(f"update_bn: the averaged model's batch-statistics BatchNorms recomputed over {args.update_bn} batches")
     if avg is not None and rank == 0:
         with torch.no_grad():
             cls_logits = avg.module.eval()(imgs)[0]                                                 # the averaged weights, on their own plans

@@ -810,6 +810,34 @@ int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t x_cs, int32
                                              int32_t act, int32_t phase, double* sums, double total_rows, float momentum, float* running_mean,
                                              float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream);
 
+/* The cumulative moving average, nn.BatchNorm2d(momentum=None): every entry point above that takes `float momentum` has a `_cma` sibling that takes the
+ * layer's num_batches_tracked in DEVICE memory instead (one int64, 8-byte aligned, already incremented for this batch: the host enqueues add_(1) before the
+ * call).  The lanes that blend the running statistics read it and use momentum = (float)(1.0 / (double)n): no launch more, nothing read on the host, so a
+ * captured forward follows the counter.  CONTRACT: for a counter holding n >= 1 a `_cma` call is BIT FOR BIT its plain sibling called with
+ * momentum = (float)(1.0 / n) -- y, the statistics block, both running tensors.  n < 1 writes neither running tensor; y and the statistics block are written
+ * as always.  Everything else (shapes, partition, fp64 sums, workspaces, error codes) is the plain sibling's.  FD_E_INVAL before any launch: running tensors
+ * with a null or misaligned counter, one running tensor without the other.  Null running tensors (the counter may then be null too) update no statistics.
+ * Phase 1 of the synchronised forms does not look at the counter.  The backwards are the plain ones. */
+int32_t fd_batchnorm_update_running_cma(const void* gn_workspace, int64_t rows, int32_t C, const int64_t* num_batches_tracked, float eps,
+                                        float* running_mean, float* running_var, fd_stream_t stream);
+int32_t fd_batchnorm_update_running_dev_cma(const void* gn_workspace, const double* count_dev, int32_t C, const int64_t* num_batches_tracked, float eps,
+                                            float* running_mean, float* running_var, fd_stream_t stream);
+int32_t fd_batchnorm_train_fwd_cma_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
+                                        int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, const int64_t* num_batches_tracked,
+                                        float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream);
+int32_t fd_batchnorm_train_res_fwd_cma_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
+                                            int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
+                                            int32_t act, const int64_t* num_batches_tracked, float* running_mean, float* running_var, void* workspace,
+                                            int64_t workspace_bytes, fd_stream_t stream);
+int32_t fd_batchnorm_train_sync_fwd_cma_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
+                                             int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums,
+                                             double total_rows, const int64_t* num_batches_tracked, float* running_mean, float* running_var,
+                                             void* workspace, int64_t workspace_bytes, fd_stream_t stream);
+int32_t fd_batchnorm_train_sync_res_fwd_cma_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
+                                                 int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
+                                                 int32_t act, int32_t phase, double* sums, double total_rows, const int64_t* num_batches_tracked,
+                                                 float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream);
+
 /* Drop-connect (stochastic depth) on [N][HW][C] fp32 channel views: y = a * s[n] + r, s = N floats on the device, r may be NULL; y may alias a.
  * Two roundings, like the torch expression a * s + r. */
 int32_t fd_sample_scale_add_nhwc(const float* a, int32_t a_cs, int32_t a_co, const float* s, const float* r, int32_t r_cs, int32_t r_co, float* y,

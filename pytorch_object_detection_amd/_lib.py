@@ -270,6 +270,13 @@ _SIGS = {
     "fd_batchnorm_train_sync_bwd_nhwc": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _L, _I, _F, _I, _I, _P, _D, _P, _P, _L, _P]),
     "fd_batchnorm_train_res_fwd_nhwc": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _L, _I, _F, _I, _F, _P, _P, _P, _L, _P]),
     "fd_batchnorm_train_sync_res_fwd_nhwc": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _L, _I, _F, _I, _I, _P, _D, _F, _P, _P, _P, _L, _P]),
+    # the cumulative-average siblings: `float momentum` replaced by the device pointer of num_batches_tracked
+    "fd_batchnorm_update_running_cma": (_I, [_P, _L, _I, _P, _F, _P, _P, _P]),
+    "fd_batchnorm_update_running_dev_cma": (_I, [_P, _P, _I, _P, _F, _P, _P, _P]),
+    "fd_batchnorm_train_fwd_cma_nhwc": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _L, _I, _F, _I, _P, _P, _P, _P, _L, _P]),
+    "fd_batchnorm_train_res_fwd_cma_nhwc": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _L, _I, _F, _I, _P, _P, _P, _P, _L, _P]),
+    "fd_batchnorm_train_sync_fwd_cma_nhwc": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _L, _I, _F, _I, _I, _P, _D, _P, _P, _P, _P, _L, _P]),
+    "fd_batchnorm_train_sync_res_fwd_cma_nhwc": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _L, _I, _F, _I, _I, _P, _D, _P, _P, _P, _P, _L, _P]),
     "fd_sample_scale_add_nhwc": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
     "fd_stem_conv_wgrad_workspace_bytes": (_L, [_I, _I, _I, _I, _I, _I]),
     "fd_stem_conv_bwd_weight_nhwc4": (_I, [_P, _P, _I, _I, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -16,6 +16,7 @@
 // workspace (both directions, fd_batchnorm_train_workspace_bytes): double [2][C] then double [nchunk][2][C].  The forward leaves mean[C], rstd[C] in the first
 // block (rstd rounded to fp32 first: the value the apply kernels multiply by); the backward leaves c1[C], c2[C] there.
 // The same kernels serve nn.SyncBatchNorm (fd_batchnorm_train_sync_*, below): each direction in two phases around an all-reduce the caller issues.
+// Every forward has a `_cma` sibling for nn.BatchNorm2d(momentum=None): the blend factor 1 / num_batches_tracked, read from the counter on the device.
 #include "fd_common.h"
 
 #define BN_MAXCHUNK 1024
@@ -120,14 +121,21 @@ __device__ __forceinline__ bool bn_chunk_sums(const double* __restrict__ part, i
 
 // channel c's statistics from its two sums over `count` rows (one rank's, or all ranks' behind an all-reduce): shared by the unsynchronised final kernel and
 // the synchronised one, so that one rank gives the same bits through either
-__device__ __forceinline__ void bn_fwd_stats(int c, int C, double A, double B, double count, float eps, float momentum, double* __restrict__ stat,
-                                             float* __restrict__ rmean, float* __restrict__ rvar) {
+// nbt (or null): the layer's num_batches_tracked on the device, already incremented for this batch -- the cumulative moving average of momentum=None,
+// momentum = (float)(1 / n), read here by the lane that blends; n < 1 writes neither running tensor
+__device__ __forceinline__ void bn_fwd_stats(int c, int C, double A, double B, double count, float eps, float momentum, const int64_t* __restrict__ nbt,
+                                             double* __restrict__ stat, float* __restrict__ rmean, float* __restrict__ rvar) {
     const double mean = A / count;
     double var = B / count - mean * mean;               // the biased batch variance
     if (var < 0) var = 0;
     stat[c] = mean;
     stat[C + c] = (double)(float)(1.0 / sqrt(var + (double)eps));
     if (rmean) {                                        // nn.BatchNorm2d: momentum update with the UNBIASED variance
+        if (nbt) {
+            const int64_t n = *nbt;
+            if (n < 1) return;
+            momentum = (float)(1.0 / (double)n);
+        }
         const double unbiased = var * count / (count - 1.0);
         rmean[c] = (float)((1.0 - (double)momentum) * (double)rmean[c] + (double)momentum * mean);
         rvar[c] = (float)((1.0 - (double)momentum) * (double)rvar[c] + (double)momentum * unbiased);
@@ -143,11 +151,12 @@ __device__ __forceinline__ void bn_bwd_coef(int c, int C, double A, double B, do
 }
 
 __global__ __launch_bounds__(256) void bn_fwd_final_kernel(const double* __restrict__ part, int nchunk, int C, double count, float eps, float momentum,
-                                                            double* __restrict__ stat, float* __restrict__ rmean, float* __restrict__ rvar) {
+                                                            const int64_t* __restrict__ nbt, double* __restrict__ stat, float* __restrict__ rmean,
+                                                            float* __restrict__ rvar) {
     __shared__ double s_a[256], s_b[256];
     int c; double A, B;
     if (!bn_chunk_sums(part, nchunk, C, s_a, s_b, c, A, B)) return;
-    bn_fwd_stats(c, C, A, B, count, eps, momentum, stat, rmean, rvar);
+    bn_fwd_stats(c, C, A, B, count, eps, momentum, nbt, stat, rmean, rvar);
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const double* __restrict__ part, int nchunk, int C, double count, const float* __restrict__ gamma,
@@ -288,12 +297,12 @@ static BnLaunch bn_prologue(const char* who, bool bwd, bool sync, bool res, cons
 #undef BN_REQUIRE
 
 // the forward's launches; the residual form (`res` a fourth channel view, act in {NONE, RELU}) differs in the apply kernel alone
-static int32_t bn_fwd_launches(const BnLaunch& L, bool res, float eps, float momentum, float* running_mean, float* running_var) {
+static int32_t bn_fwd_launches(const BnLaunch& L, bool res, float eps, float momentum, const int64_t* nbt, float* running_mean, float* running_var) {
     const int C = L.a.C;
     hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (partial)");
     hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, L.st, (const double*)L.part, L.p.nchunk, C, (double)L.a.rows, eps, momentum,
-                       L.head, running_mean, running_var);
+                       nbt, L.head, running_mean, running_var);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (statistics)");
     if (!res) hipLaunchKernelGGL((bn_apply_kernel<false, false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
     else hipLaunchKernelGGL((bn_apply_kernel<false, true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
@@ -306,7 +315,7 @@ extern "C" int32_t fd_batchnorm_train_fwd_nhwc(const float* x, int32_t x_cs, int
                                                float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
     const BnLaunch L = bn_prologue("fd_batchnorm_train_fwd", false, false, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr, nullptr,
                                    rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
-    return L.rc != FD_OK ? L.rc : bn_fwd_launches(L, false, eps, momentum, running_mean, running_var);
+    return L.rc != FD_OK ? L.rc : bn_fwd_launches(L, false, eps, momentum, nullptr, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
@@ -315,7 +324,38 @@ extern "C" int32_t fd_batchnorm_train_res_fwd_nhwc(const float* x, int32_t x_cs,
                                                    int64_t workspace_bytes, fd_stream_t stream) {
     const BnLaunch L = bn_prologue("fd_batchnorm_train_res_fwd", false, false, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co, nullptr,
                                    nullptr, rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
-    return L.rc != FD_OK ? L.rc : bn_fwd_launches(L, true, eps, momentum, running_mean, running_var);
+    return L.rc != FD_OK ? L.rc : bn_fwd_launches(L, true, eps, momentum, nullptr, running_mean, running_var);
+}
+
+// ---- The cumulative moving average (nn.BatchNorm2d(momentum=None)): the `_cma` siblings take the layer's num_batches_tracked in DEVICE memory where the
+// plain forms take `float momentum`, and are bit for bit the plain form called with momentum = (float)(1.0 / n) for a counter holding n >= 1; n < 1 writes
+// neither running tensor.  The counter is read by the statistics launch the plain form has anyway: no launch more, nothing read on the host.
+static int32_t bn_counter_check(const char* who, const int64_t* nbt, const float* running_mean, const float* running_var) {
+    FD_REQUIRE((!running_mean && !running_var) || (nbt && ((uintptr_t)nbt & 7) == 0), FD_E_INVAL,
+               "%s: running tensors need num_batches_tracked, one int64 on the device (8-byte aligned)", who);
+    return FD_OK;
+}
+
+extern "C" int32_t fd_batchnorm_train_fwd_cma_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
+                                                   int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, const int64_t* num_batches_tracked,
+                                                   float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_fwd_cma", false, false, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr,
+                                   nullptr, rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
+    if (L.rc != FD_OK) return L.rc;
+    const int32_t rc = bn_counter_check("fd_batchnorm_train_fwd_cma", num_batches_tracked, running_mean, running_var);
+    return rc != FD_OK ? rc : bn_fwd_launches(L, false, eps, 0.f, num_batches_tracked, running_mean, running_var);
+}
+
+extern "C" int32_t fd_batchnorm_train_res_fwd_cma_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
+                                                       int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C,
+                                                       float eps, int32_t act, const int64_t* num_batches_tracked, float* running_mean, float* running_var,
+                                                       void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_res_fwd_cma", false, false, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co,
+                                   nullptr, nullptr, rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes,
+                                   stream);
+    if (L.rc != FD_OK) return L.rc;
+    const int32_t rc = bn_counter_check("fd_batchnorm_train_res_fwd_cma", num_batches_tracked, running_mean, running_var);
+    return rc != FD_OK ? rc : bn_fwd_launches(L, true, eps, 0.f, num_batches_tracked, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
@@ -354,11 +394,12 @@ __global__ __launch_bounds__(256) void bn_wide_sync_sums_kernel(const double* __
 }
 
 __global__ __launch_bounds__(256) void bn_wide_sync_fwd_final_kernel(const double* __restrict__ sums, int C, double count, float eps, float momentum,
-                                                                 double* __restrict__ stat, float* __restrict__ rmean, float* __restrict__ rvar) {
+                                                                 const int64_t* __restrict__ nbt, double* __restrict__ stat, float* __restrict__ rmean,
+                                                                 float* __restrict__ rvar) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
     if (count <= 0.0) count = sums[2 * C];
-    bn_fwd_stats(c, C, sums[c], sums[C + c], count, eps, momentum, stat, rmean, rvar);
+    bn_fwd_stats(c, C, sums[c], sums[C + c], count, eps, momentum, nbt, stat, rmean, rvar);
 }
 
 __global__ __launch_bounds__(256) void bn_wide_sync_bwd_coef_kernel(const double* __restrict__ sums, int C, double count, const float* __restrict__ gamma,
@@ -371,7 +412,7 @@ __global__ __launch_bounds__(256) void bn_wide_sync_bwd_coef_kernel(const double
 
 // one phase of the synchronised forward; the residual form adds the `res` view in phase 2's apply kernel (act in {NONE, RELU}), phase 1 never reads it
 static int32_t bn_sync_fwd_launches(const BnLaunch& L, bool res, int32_t phase, double* sums, double total_rows, float eps, float momentum,
-                                    float* running_mean, float* running_var) {
+                                    const int64_t* nbt, float* running_mean, float* running_var) {
     const int C = L.a.C;
     if (phase == 1) {
         hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
@@ -381,8 +422,8 @@ static int32_t bn_sync_fwd_launches(const BnLaunch& L, bool res, int32_t phase, 
         FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (sums)");
         return FD_OK;
     }
-    hipLaunchKernelGGL(bn_wide_sync_fwd_final_kernel, dim3((C + 255) / 256), dim3(256), 0, L.st, (const double*)sums, C, total_rows, eps, momentum, L.head,
-                       running_mean, running_var);
+    hipLaunchKernelGGL(bn_wide_sync_fwd_final_kernel, dim3((C + 255) / 256), dim3(256), 0, L.st, (const double*)sums, C, total_rows, eps, momentum, nbt,
+                       L.head, running_mean, running_var);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (statistics)");
     if (!res) hipLaunchKernelGGL((bn_apply_kernel<false, false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
     else hipLaunchKernelGGL((bn_apply_kernel<false, true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
@@ -396,7 +437,7 @@ extern "C" int32_t fd_batchnorm_train_sync_fwd_nhwc(const float* x, int32_t x_cs
                                                     int64_t workspace_bytes, fd_stream_t stream) {
     const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_fwd", false, true, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr, nullptr,
                                    rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
-    return L.rc != FD_OK ? L.rc : bn_sync_fwd_launches(L, false, phase, sums, total_rows, eps, momentum, running_mean, running_var);
+    return L.rc != FD_OK ? L.rc : bn_sync_fwd_launches(L, false, phase, sums, total_rows, eps, momentum, nullptr, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
@@ -406,7 +447,33 @@ extern "C" int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t 
                                                         fd_stream_t stream) {
     const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_res_fwd", false, true, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co, nullptr,
                                    nullptr, rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
-    return L.rc != FD_OK ? L.rc : bn_sync_fwd_launches(L, true, phase, sums, total_rows, eps, momentum, running_mean, running_var);
+    return L.rc != FD_OK ? L.rc : bn_sync_fwd_launches(L, true, phase, sums, total_rows, eps, momentum, nullptr, running_mean, running_var);
+}
+
+// the `_cma` siblings of the two synchronised forwards; phase 1 does not look at the counter, as it does not look at the momentum
+extern "C" int32_t fd_batchnorm_train_sync_fwd_cma_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y,
+                                                        int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase,
+                                                        double* sums, double total_rows, const int64_t* num_batches_tracked, float* running_mean,
+                                                        float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_fwd_cma", false, true, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr,
+                                   nullptr, rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace, workspace_bytes,
+                                   stream);
+    if (L.rc != FD_OK) return L.rc;
+    const int32_t rc = bn_counter_check("fd_batchnorm_train_sync_fwd_cma", num_batches_tracked, running_mean, running_var);
+    return rc != FD_OK ? rc : bn_sync_fwd_launches(L, false, phase, sums, total_rows, eps, 0.f, num_batches_tracked, running_mean, running_var);
+}
+
+extern "C" int32_t fd_batchnorm_train_sync_res_fwd_cma_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta,
+                                                            const float* res, int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co,
+                                                            int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums, double total_rows,
+                                                            const int64_t* num_batches_tracked, float* running_mean, float* running_var, void* workspace,
+                                                            int64_t workspace_bytes, fd_stream_t stream) {
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_res_fwd_cma", false, true, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co,
+                                   nullptr, nullptr, rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace,
+                                   workspace_bytes, stream);
+    if (L.rc != FD_OK) return L.rc;
+    const int32_t rc = bn_counter_check("fd_batchnorm_train_sync_res_fwd_cma", num_batches_tracked, running_mean, running_var);
+    return rc != FD_OK ? rc : bn_sync_fwd_launches(L, true, phase, sums, total_rows, eps, 0.f, num_batches_tracked, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_sync_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co,

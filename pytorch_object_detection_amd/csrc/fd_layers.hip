@@ -1667,10 +1667,16 @@ extern "C" int32_t fd_se_scale_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_
 // its workspace into the running statistics the way nn.BatchNorm2d does (momentum update, unbiased variance; HISFcos.py FPN
 // BatchNorms under the reference's model.train(), train.py:151).
 __global__ __launch_bounds__(256) void bn_running_kernel(const double* __restrict__ gstat, float* __restrict__ rmean, float* __restrict__ rvar,
-                                                          int C, double count, float momentum, float eps, const double* __restrict__ count_dev = nullptr) {
+                                                          int C, double count, float momentum, float eps, const double* __restrict__ count_dev = nullptr,
+                                                          const int64_t* __restrict__ nbt = nullptr) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
     if (count_dev) count = *count_dev;
+    if (nbt) {                                               // momentum=None: the cumulative average, 1 / num_batches_tracked (already incremented)
+        const int64_t n = *nbt;
+        if (n < 1) return;
+        momentum = (float)(1.0 / (double)n);
+    }
     const double mean = gstat[2 * c], rstd = gstat[2 * c + 1];
     double var = 1.0 / (rstd * rstd) - (double)eps;          // biased batch variance the forward normalised with
     if (var < 0) var = 0;
@@ -1697,6 +1703,35 @@ extern "C" int32_t fd_batchnorm_update_running_dev(const void* gn_workspace, con
                        0.0, momentum, eps, count_dev);
     FD_CHECK_LAUNCH("fd_batchnorm_update_running_dev");
     return FD_OK;
+}
+
+// The `_cma` siblings (nn.BatchNorm2d(momentum=None), the cumulative moving average): the layer's num_batches_tracked in DEVICE memory in place of
+// `float momentum`; bit for bit the plain form with momentum = (float)(1.0 / n) for a counter holding n >= 1, n < 1 writes nothing.  Running tensors both
+// or neither; neither (then the counter may be null too) updates nothing.
+static int32_t bn_running_cma(const char* who, const double* gstat, double count, const double* count_dev, int32_t C, const int64_t* nbt, float eps,
+                              float* running_mean, float* running_var, fd_stream_t stream) {
+    FD_REQUIRE((running_mean == nullptr) == (running_var == nullptr), FD_E_INVAL, "%s: running_mean and running_var go together", who);
+    FD_REQUIRE(!running_mean || (nbt && ((uintptr_t)nbt & 7) == 0), FD_E_INVAL,
+               "%s: running tensors need num_batches_tracked, one int64 on the device (8-byte aligned)", who);
+    if (!running_mean) return FD_OK;
+    hipLaunchKernelGGL(bn_running_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, gstat, running_mean, running_var, C, count, 0.f, eps,
+                       count_dev, nbt);
+    FD_CHECK_LAUNCH(who);
+    return FD_OK;
+}
+
+extern "C" int32_t fd_batchnorm_update_running_cma(const void* gn_workspace, int64_t rows, int32_t C, const int64_t* num_batches_tracked, float eps,
+                                                   float* running_mean, float* running_var, fd_stream_t stream) {
+    FD_REQUIRE(gn_workspace && rows >= 1 && C >= 1, FD_E_INVAL, "fd_batchnorm_update_running_cma: bad argument");
+    return bn_running_cma("fd_batchnorm_update_running_cma", (const double*)gn_workspace + (long)GN_MAXCHUNK * C * 2, (double)rows, nullptr, C,
+                          num_batches_tracked, eps, running_mean, running_var, stream);
+}
+
+extern "C" int32_t fd_batchnorm_update_running_dev_cma(const void* gn_workspace, const double* count_dev, int32_t C, const int64_t* num_batches_tracked,
+                                                       float eps, float* running_mean, float* running_var, fd_stream_t stream) {
+    FD_REQUIRE(gn_workspace && count_dev && C >= 1, FD_E_INVAL, "fd_batchnorm_update_running_dev_cma: bad argument");
+    return bn_running_cma("fd_batchnorm_update_running_dev_cma", (const double*)gn_workspace + (long)GN_MAXCHUNK * C * 2, 0.0, count_dev, C,
+                          num_batches_tracked, eps, running_mean, running_var, stream);
 }
 
 // ---- nn.SyncBatchNorm (train.py:103 converts the model; collective C3 of SURVEY 2.1) on the same kernels.  Batch statistics

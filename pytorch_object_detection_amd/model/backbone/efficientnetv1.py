@@ -121,6 +121,11 @@ class _EfficientNet(nn.Module):
         self._bn1 = nn.BatchNorm2d(head, momentum=BN_MOMENTUM, eps=BN_EPS)
         self._fc = nn.Linear(head, 1000)
 
+    def bn_on_running_stats(self):
+        """The BatchNorms that a training forward runs on their running statistics whatever their .training flag says: without train_stem the stem's _bn0,
+        folded into the stem launch (trunk_train_forward).  optim.update_bn leaves these alone."""
+        return [] if self.train_stem else [self._bn0]
+
 
 def _out_hw(h: int, w: int, k: int, s: int, pad) -> Tuple[int, int]:
     return (h + pad[0] + pad[1] - k) // s + 1, (w + pad[0] + pad[1] - k) // s + 1
@@ -153,7 +158,9 @@ def _trunk_stock(net: "_EfficientNet", x: torch.Tensor, drop_u=None):
     def batch(m, t):
         if m.num_batches_tracked is not None:
             m.num_batches_tracked.add_(1)
-        return F.batch_norm(t, m.running_mean, m.running_var, m.weight, m.bias, True, m.momentum, m.eps)
+        # (momentum=None, the cumulative average of optim.update_bn: this diagnostic path reads the counter on the host, as nn.BatchNorm2d.forward does)
+        momentum = m.momentum if m.momentum is not None else 1.0 / float(m.num_batches_tracked)
+        return F.batch_norm(t, m.running_mean, m.running_var, m.weight, m.bias, True, momentum, m.eps)
 
     bn = batch if net.batch_stats else frozen
     same = lambda t, pad: F.pad(t, (pad[0], pad[1], pad[0], pad[1])) if (pad[0] or pad[1]) else t  # noqa: E731

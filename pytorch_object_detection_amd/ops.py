@@ -1623,19 +1623,39 @@ def upsample2x_bwd(dy: Rows, dx: Rows, N: int, H: int, W: int) -> None:
     check(_lib.lib().fd_upsample2x_bwd_nhwc(dy.ptr, dy.cs, dy.co, dx.ptr, dx.cs, dx.co, N, H, W, dx.C, _stream()), "fd_upsample2x_bwd_nhwc")
 
 
-def batchnorm_update_running(gn_ws: torch.Tensor, rows: int, Cc: int, momentum: float, eps: float, running_mean: torch.Tensor,
+def _bn_counter(momentum) -> bool:
+    """`momentum` is the layer's live num_batches_tracked tensor (nn.BatchNorm2d(momentum=None), the cumulative moving average): the `_cma` entry points
+    read it on the device and blend with (float)(1 / n).  One int64 element on the device, already incremented for this batch."""
+    if not isinstance(momentum, torch.Tensor):
+        return False
+    if momentum.dtype != torch.int64 or momentum.numel() != 1 or not momentum.is_cuda:
+        raise FdError("a BatchNorm momentum given as a tensor must be num_batches_tracked: one int64 element on the device")
+    return True
+
+
+def batchnorm_update_running(gn_ws: torch.Tensor, rows: int, Cc: int, momentum, eps: float, running_mean: torch.Tensor,
                              running_var: torch.Tensor) -> None:
+    """momentum: a float, or the layer's num_batches_tracked tensor (fd_batchnorm_update_running_cma: momentum = 1 / n, read on the device)."""
     _need_gpu(gn_ws, running_mean, running_var)
+    if _bn_counter(momentum):
+        check(_lib.lib().fd_batchnorm_update_running_cma(gn_ws.data_ptr(), rows, Cc, momentum.data_ptr(), float(eps), running_mean.data_ptr(),
+                                                         running_var.data_ptr(), _stream()), "fd_batchnorm_update_running_cma")
+        return
     check(_lib.lib().fd_batchnorm_update_running(gn_ws.data_ptr(), rows, Cc, float(momentum), float(eps), running_mean.data_ptr(),
                                                  running_var.data_ptr(), _stream()), "fd_batchnorm_update_running")
 
 
-def batchnorm_update_running_dev(gn_ws: torch.Tensor, count: torch.Tensor, Cc: int, momentum: float, eps: float, running_mean: torch.Tensor,
+def batchnorm_update_running_dev(gn_ws: torch.Tensor, count: torch.Tensor, Cc: int, momentum, eps: float, running_mean: torch.Tensor,
                                  running_var: torch.Tensor) -> None:
     """As batchnorm_update_running with the row count in device memory (`count`: one float64 element, e.g. the tail of SyncBatchNorm's
     all-reduced buffer): no host round trip."""
     _need_gpu(gn_ws, count, running_mean, running_var)
     assert count.dtype == torch.float64 and count.numel() == 1
+    if _bn_counter(momentum):
+        check(_lib.lib().fd_batchnorm_update_running_dev_cma(gn_ws.data_ptr(), count.data_ptr(), Cc, momentum.data_ptr(), float(eps),
+                                                             running_mean.data_ptr(), running_var.data_ptr(), _stream()),
+              "fd_batchnorm_update_running_dev_cma")
+        return
     check(_lib.lib().fd_batchnorm_update_running_dev(gn_ws.data_ptr(), count.data_ptr(), Cc, float(momentum), float(eps), running_mean.data_ptr(),
                                                      running_var.data_ptr(), _stream()), "fd_batchnorm_update_running_dev")
 
@@ -1668,9 +1688,13 @@ def _bn_running(momentum, running_mean, running_var) -> bool:
 
 
 def _bn_running_args(momentum, running_mean, running_var):
+    """(`_cma` entry point?, the three operands).  A tensor momentum is the layer's num_batches_tracked: its address goes where the float would, read from
+    the live tensor in every call (nothing cached: a captured forward follows the counter)."""
     if not _bn_running(momentum, running_mean, running_var):
-        return 0.0, None, None
-    return float(momentum), running_mean.data_ptr(), running_var.data_ptr()
+        return False, (0.0, None, None)
+    if _bn_counter(momentum):
+        return True, (momentum.data_ptr(), running_mean.data_ptr(), running_var.data_ptr())
+    return False, (float(momentum), running_mean.data_ptr(), running_var.data_ptr())
 
 
 def _dptr(t: Optional[torch.Tensor]):
@@ -1686,23 +1710,26 @@ def _bn_train_fwd(who: str, res_form: bool, phase: Optional[int], x, sums, gamma
         raise FdError(f"{who}: fp32 views of the same shape and C-element gamma / beta expected")
     if res_form:
         _bn_res_check(who, x, res, act_id)
+    cma, running = _bn_running_args(momentum, running_mean, running_var)
+    name = f"fd_{who}_cma_nhwc" if cma else f"fd_{who}_nhwc"
     if phase is None:
-        sync, sym = (), f"fd_{who}_nhwc"
+        sync, sym = (), name
     else:
         _bn_sums_check(who, sums, x.C)
-        sync, sym = (phase, sums.data_ptr(), float(total_rows)), f"fd_{who}_nhwc (phase {phase})"
+        sync, sym = (phase, sums.data_ptr(), float(total_rows)), f"{name} (phase {phase})"
     if ws is None:
         ws = (batchnorm_train_workspace if phase is None else batchnorm_train_sync_workspace)(x.rows, x.C, x.buf.device)
-    check(getattr(_lib.lib(), f"fd_{who}_nhwc")(x.ptr, x.cs, x.co, _dptr(gamma), _dptr(beta), *(_view3(res) if res_form else ()), *_view3(y), x.rows, x.C,
-                                                float(eps), act_id, *sync, *_bn_running_args(momentum, running_mean, running_var), ws.data_ptr(),
-                                                ws.numel() * ws.element_size(), _stream()), sym)
+    check(getattr(_lib.lib(), name)(x.ptr, x.cs, x.co, _dptr(gamma), _dptr(beta), *(_view3(res) if res_form else ()), *_view3(y), x.rows, x.C, float(eps),
+                                    act_id, *sync, *running, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), sym)
     return ws
 
 
 def batchnorm_train_fwd(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, y: Rows, eps: float, act_id: int = ACT_NONE, momentum: Optional[float] = None,
                         running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = act(BatchNorm(x)) on the batch statistics of the fp32 channel view x (fd_batchnorm_train_fwd_nhwc: any C % 4 == 0 up to 4096).  With `momentum`
-    and the running tensors given they are updated in place like nn.BatchNorm2d's.  Returns the workspace batchnorm_train_bwd needs."""
+    and the running tensors given they are updated in place like nn.BatchNorm2d's.  `momentum` in this and the three wrappers below: a float, or the
+    layer's live num_batches_tracked tensor for nn.BatchNorm2d(momentum=None) -- the `_cma` entry point then reads it on the device and blends with 1 / n,
+    bit for bit the float form at float32(1 / n).  Returns the workspace batchnorm_train_bwd needs."""
     return _bn_train_fwd("batchnorm_train_fwd", False, None, x, None, gamma, beta, None, y, eps, act_id, 0.0, momentum, running_mean, running_var, ws)
 
 

@@ -15,7 +15,8 @@ finish launch that turns them into the clip coefficient, and the update launches
 more read of the gradients, no write to them, no host read.  p.grad is NOT modified: the one difference from torch.nn.utils.clip_grad_norm_.
 
 Averaging the weights (SWA / EMA) is optim.AveragedModel at the end of this file: torch.optim.swa_utils.AveragedModel on the same terms -- no host read, the
-optimizer's skip flag honoured, capture-safe.
+optimizer's skip flag honoured, capture-safe (DESIGN 4.3m).  optim.update_bn(loader, avg) then recomputes the running statistics of the averaged copy's
+batch-statistics BatchNorms on the HIP kernels, leaving the frozen ones alone.
 
 What stays stock: torch.amp.GradScaler's own inf check and update().  Moving an optimizer goes through state_dict() / load_state_dict() and
 global_step / set_global_step(); pickling or deep-copying the optimizer object itself is not supported (torch's __getstate__ drops the state block).
@@ -413,7 +414,8 @@ class AveragedModel(torch.optim.swa_utils.AveragedModel):
     its non-floating fallback branch; that is not followed.
 
     Refused: non-fp32 floating tensors, pairs whose shapes / strides / devices differ, non-dense tensors, CPU tensors (there is no CPU fallback), a model with
-    more tensors than the copy.  Not here: update_bn, SWALR, a decay warm-up, averaging in fp64.  Moving an averaged model goes through state_dict() /
+    more tensors than the copy.  The copy's batch-statistics BatchNorms get statistics that belong to the averaged weights from update_bn(loader, avg) below.
+    Not here: SWALR, a decay warm-up, averaging in fp64.  Moving an averaged model goes through state_dict() /
     load_state_dict(); with optimizer= the object itself can be neither pickled nor deep-copied, as the optimizer cannot."""
 
     def __init__(self, model, device=None, avg_fn=None, multi_avg_fn=None, use_buffers=False, *, decay=None, optimizer=None, start_step=0, every=1):
@@ -503,3 +505,53 @@ class AveragedModel(torch.optim.swa_utils.AveragedModel):
         self.launches = launches
         # host only: the averaged module's plans and folded BatchNorms key on _version and re-pack on its next forward
         torch.autograd.graph.increment_version([n] + [a for a, _ in averaged] + [a for a, _ in copied])
+
+
+def update_bn(loader, model, device=None) -> None:
+    """torch.optim.swa_utils.update_bn for this project's models: recompute the running statistics of the BatchNorms that run on BATCH statistics as the equal
+    average over `loader`.  Same signature and batch conventions: a batch is a tensor, or a list / tuple whose first element is the input, moved
+    to `device` when one is given.  The main use is the averaged copy, whose weights are averaged but whose running statistics are only copied:
+
+        optim.update_bn(loader, avg)                  # avg = optim.AveragedModel(...); also a bare detector or a DistributedDataParallel wrapper
+
+    It runs under torch.no_grad() in fp32 and never reads the device.  Three differences from the stock function:
+      * it records model.training, calls model.train(), and THEN resets (device fills) and sets momentum = None on only the BatchNorms for which
+        `training and track_running_stats` holds -- the set that will run on batch statistics.  What train() keeps in eval mode (the backbone the constructor
+        froze, everything under freeze_all_bn, a stem enable_training() froze) keeps its statistics bit for bit; the stock function resets those to 0 / 1
+        and never recomputes them.  An empty set returns with the mode restored.
+      * momentum = None stays on the HIP batch-statistics kernels: they read num_batches_tracked on the device and blend with 1 / n (the `_cma` entry
+        points), at the launches of an ordinary train-mode forward, and the forward can be captured.
+      * momenta and model.train(was_training) are restored in a finally:, and every running tensor it wrote has its version counter bumped (HIP launches do
+        not bump them), so folded BatchNorms and plans re-pack on the next eval forward.
+    Under nn.SyncBatchNorm on more than one rank every rank passes its own shard: the statistics are global and all ranks end with identical buffers."""
+    with torch.no_grad():
+        was_training = model.training
+        model.train()
+        momenta = {}
+        try:
+            # (a trunk names the layers it keeps on their running statistics whatever .training says: the EfficientNet stem without train_stem)
+            kept = {id(b) for m in model.modules() if hasattr(m, "bn_on_running_stats") for b in m.bn_on_running_stats()}
+            for m in model.modules():
+                if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and m.training and m.track_running_stats and id(m) not in kept:
+                    momenta[m] = m.momentum
+            if not momenta:
+                return
+            for m in momenta:
+                m.running_mean.zero_()
+                m.running_var.fill_(1)
+                if m.num_batches_tracked is not None:
+                    m.num_batches_tracked.zero_()
+                m.momentum = None
+            for batch in loader:
+                if isinstance(batch, (list, tuple)):
+                    batch = batch[0]
+                if device is not None:
+                    batch = batch.to(device)
+                model(batch)
+        finally:
+            for m, momentum in momenta.items():
+                m.momentum = momentum
+            model.train(was_training)
+            written = [t for m in momenta for t in (m.running_mean, m.running_var, m.num_batches_tracked) if t is not None]
+            if written:
+                torch.autograd.graph.increment_version(written)

@@ -1228,7 +1228,7 @@ def syncbn_finish(h: "_SyncHandle", res: Optional[torch.Tensor] = None) -> torch
         bn.num_batches_tracked.add_(1)
     if res is not None and (h.res_fwd is None or h.defer):
         raise FdError("syncbn_finish(res=...): the residual form exists for the any-width kernels (wide=True) without a deferred backward")
-    return _SyncBatchNormApply.apply(h.x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, bn.momentum, bn.eps, h.act, h)
+    return _SyncBatchNormApply.apply(h.x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, h.act, h)
 
 
 def _syncbn_backward(x, g, gm, bt, ws, buf, eps, act, group, defer, bwd):
@@ -1311,10 +1311,21 @@ class _SyncBatchNormApply(torch.autograd.Function):
         return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None, None
 
 
+def _bn_momentum(bn: nn.Module):
+    """What the batch-statistics nodes carry to the kernels as the blend factor of bn's running statistics: the float momentum, or for momentum=None (the
+    cumulative moving average, 1 / num_batches_tracked) the LIVE counter tensor -- the `_cma` entry points read it on the device behind the add_(1) the
+    caller has enqueued.  The wrappers take its address in every call and nothing is cached, so a captured forward follows the counter."""
+    if bn.momentum is not None:
+        return bn.momentum
+    if getattr(bn, "num_batches_tracked", None) is None:
+        raise FdError(f"{type(bn).__name__}({bn.num_features}) with momentum=None has no num_batches_tracked: the cumulative average needs the counter")
+    return bn.num_batches_tracked
+
+
 def _bn_train_wide_ok(bn: nn.Module, x: torch.Tensor) -> bool:
     """A BatchNorm in training mode that batchnorm_train_wide_rows takes: any width C % 4 == 0 up to 4096 (x may be held wider)."""
     Cc = getattr(bn, "num_features", 0)
-    return (not _STOCK and isinstance(bn, BN_TYPES) and bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+    return (not _STOCK and isinstance(bn, BN_TYPES) and bn.training and bn.affine and bn.track_running_stats
             and Cc % 4 == 0 and 4 <= Cc <= 4096 and _f32(x))
 
 
@@ -1340,7 +1351,7 @@ def batchnorm_train_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) ->
         return syncbn_finish(syncbn_begin(bn, x, act))          # one-shot form: nothing enqueued between issue and wait
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    return _BatchNormTrainRows.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act)
+    return _BatchNormTrainRows.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, act)
 
 
 def _is_sync(bn: nn.Module) -> bool:
@@ -1406,7 +1417,7 @@ def batchnorm_train_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NON
         raise FdError(f"batch-statistics BatchNorm({Cc}) on rows of shape {tuple(x.shape)}: at least 2 rows of at least {Cc} channels (a multiple of 4) expected")
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    return _BatchNormWideRows.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act)
+    return _BatchNormWideRows.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, act)
 
 
 def _bn_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) -> torch.Tensor:
@@ -1443,8 +1454,8 @@ def batchnorm_train_res_rows(bn: nn.Module, x: torch.Tensor, res: torch.Tensor, 
     if act not in (ACT_NONE, ACT_RELU):
         raise FdError("batchnorm_train_res_rows differentiates ACT_NONE / ACT_RELU only (the backward takes its mask from the output)")
     if not _bn_train_wide_ok(bn, x):
-        raise FdError(f"batchnorm_train_res_rows: {type(bn).__name__}({Cc}) must be a BatchNorm in training mode with affine parameters, running statistics "
-                      "and a momentum, C % 4 == 0, 4 <= C <= 4096, on floating-point rows")
+        raise FdError(f"batchnorm_train_res_rows: {type(bn).__name__}({Cc}) must be a BatchNorm in training mode with affine parameters, running statistics, "
+                      "C % 4 == 0, 4 <= C <= 4096, on floating-point rows")
     if x.dim() != 2 or x.shape[1] != Cc or tuple(res.shape) != tuple(x.shape):
         raise FdError(f"batchnorm_train_res_rows: BatchNorm({Cc}) on rows of shape {tuple(x.shape)} with a residual of shape {tuple(res.shape)}: "
                       f"two [rows, {Cc}] maps expected")
@@ -1454,7 +1465,7 @@ def batchnorm_train_res_rows(bn: nn.Module, x: torch.Tensor, res: torch.Tensor, 
         raise FdError(f"batchnorm_train_res_rows: batch statistics need at least 2 rows (got {x.shape[0]})")
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    return _BatchNormResRows.apply(x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, bn.momentum, bn.eps, act)
+    return _BatchNormResRows.apply(x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, act)
 
 
 class _SampleScaleAddRows(torch.autograd.Function):
