@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's train.py:97-181 loop on the MI355X path, with synthetic VOC-shaped batches.
 
-    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-optim] [--ema 0.999] [--update-bn 8]
+    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-bn-f16] [--hip-optim] [--ema 0.999] [--update-bn 8]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_like_train_py.py   # DDP / RCCL
 
 Same objects and call order as the reference: HalfInvertedStageFCOS([512, 1024, 2048], 20, 256), FCOSGenTargets,
@@ -12,7 +12,9 @@ the reference's AMP arithmetic), normalisation and losses in fp32; under DDP the
 --model MNFCOS (what the reference's config/main.yaml selects) builds MNFCOS([2048, 1024, 512], 20, 256) and opts in to its HIP training nodes
 with model.enable_training() (which also freezes the Cin = 3 stem: the optimizer is built after it).  --hip-stem trains the 7x7 stem on its HIP node
 (fd_stem7x7_bwd_weight_nhwc4) instead: MNFCOS keeps the stem trainable (enable_training(train_stem=True)), HISFCOS un-freezes conv1 and sets
-enable_stem_training() -- without the option a trainable stem runs on stock ops.  --hip-optim takes the optimizer from pytorch_object_detection_amd.optim:
+enable_stem_training() -- without the option a trainable stem runs on stock ops.  --hip-bn-f16 (HISFCOS) builds the model with bn_freeze=False and calls
+enable_stem_training().enable_trunk_batch_stats(f16_maps=True): the trunk's BatchNorms train on batch statistics on the HIP nodes and, with --amp, on f16
+maps (fd_batchnorm_train_*_nhwc_h).  --hip-optim takes the optimizer from pytorch_object_detection_amd.optim:
 step() on the HIP update kernels, GradScaler without a host read, and the warm-up / drop lines of train.py:160-173 evaluated on the device (optim.TrainPyLR)
 instead of the host lines below.  --ema DECAY (with --hip-optim) keeps an exponential moving average of the weights in optim.AveragedModel, updated on the
 device after every scaler.step(optimizer) -- a step GradScaler skips leaves it untouched -- and runs the averaged copy, avg.module, in eval mode at the end.
@@ -42,6 +44,8 @@ def main():
     ap.add_argument("--amp", action="store_true")
     ap.add_argument("--model", choices=["HISFCOS", "MNFCOS"], default="HISFCOS")
     ap.add_argument("--hip-stem", action="store_true", help="train the 7x7 stem (conv1) on its HIP forward / weight-gradient node")
+    ap.add_argument("--hip-bn-f16", action="store_true",
+                    help="HISFCOS with bn_freeze=False: the trunk's BatchNorms on batch statistics on the HIP nodes, on f16 maps under --amp")
     ap.add_argument("--hip-optim", action="store_true", help="optim.SGD with the learning-rate rule on the device instead of torch.optim.SGD and the host lines")
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="average the weights on the device (optim.AveragedModel); needs --hip-optim")
     ap.add_argument("--update-bn", type=int, default=0, metavar="N",
@@ -49,6 +53,8 @@ def main():
     args = ap.parse_args()
     if args.ema is not None and not args.hip_optim:
         ap.error("--ema gates on the HIP optimizer's skip flag: pass --hip-optim as well")
+    if args.hip_bn_f16 and args.model != "HISFCOS":
+        ap.error("--hip-bn-f16 is for --model HISFCOS (the ResNet-50 trunk's switch)")
     if args.update_bn < 0 or (args.update_bn and args.ema is None):
         ap.error("--update-bn N (N >= 1) recomputes the statistics of the averaged model: pass --ema as well")
     rank, world, local = (int(os.environ.get(k, d)) for k, d in (("RANK", 0), ("WORLD_SIZE", 1), ("LOCAL_RANK", 0)))
@@ -61,6 +67,8 @@ def main():
     torch.manual_seed(0)
     if args.model == "MNFCOS":
         model = MNFCOS([2048, 1024, 512], 20, 256).enable_training(train_stem=args.hip_stem).to(dev)   # config/main.yaml:2, mnfcos.yaml
+    elif args.hip_bn_f16:
+        model = HalfInvertedStageFCOS([512, 1024, 2048], 20, 256, bn_freeze=False).enable_stem_training().enable_trunk_batch_stats(f16_maps=True).to(dev)
     else:
         model = HalfInvertedStageFCOS([512, 1024, 2048], 20, 256).to(dev)                           # train.py:97
         if args.hip_stem:

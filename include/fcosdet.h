@@ -810,6 +810,41 @@ int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t x_cs, int32
                                              int32_t act, int32_t phase, double* sums, double total_rows, float momentum, float* running_mean,
                                              float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream);
 
+/* The six entry points above on f16 MAPS (torch.autocast(float16) with f16-stored activations and gradients, train.py:175-181): x, res, y, dy and dx hold
+ * _Float16 elements on channel views that are 8-byte aligned, cs and co multiples of 4 (the rule of fd_act_bwd_nhwc_h); every other argument is the fp32
+ * entry point's -- gamma, beta, dgamma, dbeta and the running statistics fp32, sums fp64, the same workspace (fd_batchnorm_train_workspace_bytes /
+ * fd_batchnorm_train_sync_workspace_bytes) with mean / rstd and c1 / c2 as doubles in its first block, the same error codes in the same order, all before
+ * any launch (SILU in the residual form: FD_E_UNSUPPORTED).  No atomics, no host synchronisation, no allocation; cs / co enter the address computation only
+ * and nothing outside an output view is written.
+ * The arithmetic is the fp32 kernels': the same kernel code instantiated on the element type, four halves per 8-byte access where the fp32 form moves a
+ * float4.  An f16 element converts to fp32 exactly, the fp32 / fp64 operations run in the same order over the same (tile, chunk) partition, and y / dx are
+ * rounded to f16 ONCE at the store, to nearest even, a value beyond 65504 becoming inf (not saturated: a GradScaler must see the overflow).  So for f16
+ * inputs and their exact fp32 upcasts, y and dx equal round_f16(fp32 entry point's y / dx) bit for bit, and the statistics block, the coefficient block, the
+ * running statistics, dgamma, dbeta and the phase-1 sums equal the fp32 entry point's bit for bit (tests/test_bn_f16_kernels_gpu.py).
+ * The `_cma` forms below and the narrow route (fd_batchnorm_sync_*, fd_groupnorm_*) have no f16 form: these serve every width. */
+int32_t fd_batchnorm_train_fwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, void* y, int32_t y_cs, int32_t y_co,
+                                      int64_t rows, int32_t C, float eps, int32_t act, float momentum, float* running_mean, float* running_var,
+                                      void* workspace, int64_t workspace_bytes, fd_stream_t stream);
+int32_t fd_batchnorm_train_res_fwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const void* res, int32_t res_cs,
+                                          int32_t res_co, void* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act,
+                                          float momentum, float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes,
+                                          fd_stream_t stream);
+int32_t fd_batchnorm_train_bwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const void* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
+                                      const float* beta, void* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows, int32_t C,
+                                      float eps, int32_t act, const void* fwd_workspace, void* workspace, int64_t workspace_bytes, fd_stream_t stream);
+int32_t fd_batchnorm_train_sync_fwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, void* y, int32_t y_cs,
+                                           int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums, double total_rows,
+                                           float momentum, float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes,
+                                           fd_stream_t stream);
+int32_t fd_batchnorm_train_sync_res_fwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const void* res,
+                                               int32_t res_cs, int32_t res_co, void* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
+                                               int32_t act, int32_t phase, double* sums, double total_rows, float momentum, float* running_mean,
+                                               float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream);
+int32_t fd_batchnorm_train_sync_bwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const void* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
+                                           const float* beta, void* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows, int32_t C,
+                                           float eps, int32_t act, int32_t phase, double* sums, double total_rows, const void* fwd_workspace,
+                                           void* workspace, int64_t workspace_bytes, fd_stream_t stream);
+
 /* The cumulative moving average, nn.BatchNorm2d(momentum=None): every entry point above that takes `float momentum` has a `_cma` sibling that takes the
  * layer's num_batches_tracked in DEVICE memory instead (one int64, 8-byte aligned, already incremented for this batch: the host enqueues add_(1) before the
  * call).  The lanes that blend the running statistics read it and use momentum = (float)(1.0 / (double)n): no launch more, nothing read on the host, so a

@@ -270,6 +270,13 @@ _SIGS = {
     "fd_batchnorm_train_sync_bwd_nhwc": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _L, _I, _F, _I, _I, _P, _D, _P, _P, _L, _P]),
     "fd_batchnorm_train_res_fwd_nhwc": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _L, _I, _F, _I, _F, _P, _P, _P, _L, _P]),
     "fd_batchnorm_train_sync_res_fwd_nhwc": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _L, _I, _F, _I, _I, _P, _D, _F, _P, _P, _P, _L, _P]),
+    # the same six on f16 maps (x, res, y, dy, dx as _Float16): the fp32 forms' argument lists
+    "fd_batchnorm_train_fwd_nhwc_h": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _L, _I, _F, _I, _F, _P, _P, _P, _L, _P]),
+    "fd_batchnorm_train_bwd_nhwc_h": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _L, _I, _F, _I, _P, _P, _L, _P]),
+    "fd_batchnorm_train_sync_fwd_nhwc_h": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _L, _I, _F, _I, _I, _P, _D, _F, _P, _P, _P, _L, _P]),
+    "fd_batchnorm_train_sync_bwd_nhwc_h": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _L, _I, _F, _I, _I, _P, _D, _P, _P, _L, _P]),
+    "fd_batchnorm_train_res_fwd_nhwc_h": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _L, _I, _F, _I, _F, _P, _P, _P, _L, _P]),
+    "fd_batchnorm_train_sync_res_fwd_nhwc_h": (_I, [_P, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _L, _I, _F, _I, _I, _P, _D, _F, _P, _P, _P, _L, _P]),
     # the cumulative-average siblings: `float momentum` replaced by the device pointer of num_batches_tracked
     "fd_batchnorm_update_running_cma": (_I, [_P, _L, _I, _P, _F, _P, _P, _P]),
     "fd_batchnorm_update_running_dev_cma": (_I, [_P, _P, _I, _P, _F, _P, _P, _P]),

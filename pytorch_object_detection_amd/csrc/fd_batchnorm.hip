@@ -17,6 +17,9 @@
 // block (rstd rounded to fp32 first: the value the apply kernels multiply by); the backward leaves c1[C], c2[C] there.
 // The same kernels serve nn.SyncBatchNorm (fd_batchnorm_train_sync_*, below): each direction in two phases around an all-reduce the caller issues.
 // Every forward has a `_cma` sibling for nn.BatchNorm2d(momentum=None): the blend factor 1 / num_batches_tracked, read from the counter on the device.
+// Every entry point with a float momentum, and both backwards, have an `_h` sibling on f16 MAPS (AMP: x, res, y, dy, dx as _Float16, 8-byte aligned views):
+// the same kernels instantiated on the element type, so the same partition, operations and order -- y / dx are the fp32 kernel's rounded to f16 once, and
+// the statistics, coefficients, running statistics, dgamma / dbeta and phase-1 sums are the fp32 kernel's bits on the upcast inputs.
 #include "fd_common.h"
 
 #define BN_MAXCHUNK 1024
@@ -36,8 +39,9 @@ static BnPart bn_partition(int64_t rows, int32_t C) {
     return p;
 }
 
-static inline bool bn_view_ok(const void* p, int cs, int co, int C) {
-    return p && cs % 4 == 0 && co % 4 == 0 && co >= 0 && cs >= co + C && ((uintptr_t)p & 15) == 0;
+// four elements per access: 16-byte aligned fp32 views, 8-byte aligned f16 views (half)
+static inline bool bn_view_ok(const void* p, int cs, int co, int C, bool half = false) {
+    return p && cs % 4 == 0 && co % 4 == 0 && co >= 0 && cs >= co + C && ((uintptr_t)p & (half ? 7 : 15)) == 0;
 }
 
 __device__ __forceinline__ float bn_act_grad(float z, int act) {
@@ -46,14 +50,41 @@ __device__ __forceinline__ float bn_act_grad(float z, int act) {
     return 1.f;
 }
 
+// The MAPS (x, dy / res, y / dx) hold fp32 or, in the `_h` entry points, _Float16 elements: the kernels are templates on the element type T.  Four elements
+// are one access (16 bytes of fp32, 8 bytes of f16); an f16 element converts to fp32 exactly, every operation after the load is the fp32 kernel's in its
+// order, and the result is rounded to f16 ONCE at the store (to nearest even; what exceeds 65504 becomes inf).  Parameters, statistics and sums do not change.
+typedef _Float16 bn_h4_t __attribute__((ext_vector_type(4)));
+
+template <typename T> __device__ __forceinline__ void bn_load4(const void* base, long i, float v[4]) {
+    if constexpr (sizeof(T) == 4) {
+        const float4 v4 = *reinterpret_cast<const float4*>((const float*)base + i);
+        v[0] = v4.x; v[1] = v4.y; v[2] = v4.z; v[3] = v4.w;
+    } else {
+        const bn_h4_t h = *reinterpret_cast<const bn_h4_t*>((const _Float16*)base + i);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (float)h[e];
+    }
+}
+
+template <typename T> __device__ __forceinline__ void bn_store4(void* base, long i, const float o[4]) {
+    if constexpr (sizeof(T) == 4) {
+        *reinterpret_cast<float4*>((float*)base + i) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+        bn_h4_t h;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) h[e] = (_Float16)o[e];
+        *reinterpret_cast<bn_h4_t*>((_Float16*)base + i) = h;
+    }
+}
+
 struct BnArgs {                                         // (dy: the incoming gradient of the backward; the residual of the forward's residual form)
-    const float* x; const float* dy; const float* gamma; const float* beta; float* out;
+    const void* x; const void* dy; const float* gamma; const float* beta; void* out;     // x, dy, out: elements of the kernel's T
     int x_cs, x_co, dy_cs, dy_co, out_cs, out_co, C, QT, RT, act;
     long rows, rows_per;
 };
 
 // per (tile, chunk): forward (sum x, sum x^2), backward (sum dz, sum dz * xhat) -> part[chunk][2][C]
-template <bool BWD>
+template <bool BWD, typename T = float>
 __global__ __launch_bounds__(256) void bn_partial_kernel(BnArgs a, const double* __restrict__ stat, double* __restrict__ part) {
     __shared__ double s_a[1024], s_b[1024];          // [row lane][quad of the tile][4], at most 256 x 4
     const int tid = threadIdx.x, ql = tid % a.QT, rt = tid / a.QT;
@@ -71,11 +102,11 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(BnArgs a, const double*
         const long r_begin = (long)chunk * a.rows_per, r_end = min(a.rows, r_begin + a.rows_per);
 #pragma unroll 4
         for (long r = r_begin + rt; r < r_end; r += a.RT) {
-            const float4 v4 = *reinterpret_cast<const float4*>(a.x + r * a.x_cs + a.x_co + 4 * q);
-            const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+            float v[4];
+            bn_load4<T>(a.x, r * a.x_cs + a.x_co + 4 * q, v);
             if constexpr (BWD) {
-                const float4 g4 = *reinterpret_cast<const float4*>(a.dy + r * a.dy_cs + a.dy_co + 4 * q);
-                const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+                float g[4];
+                bn_load4<T>(a.dy, r * a.dy_cs + a.dy_co + 4 * q, g);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float xh = (v[e] - mean[e]) * rstd[e];
@@ -172,7 +203,7 @@ __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const double* __restr
 
 // forward: y = act(xhat * gamma + beta), RES: y = act(xhat * gamma + beta + res), one float4 of res (a.dy) per float4 of x; backward: dx = rstd * gamma * dz
 // - c1 - xhat * c2.  Same (tile, chunk) ownership as the partial kernel.
-template <bool BWD, bool RES = false>
+template <bool BWD, bool RES = false, typename T = float>
 __global__ __launch_bounds__(256) void bn_apply_kernel(BnArgs a, const double* __restrict__ stat, const double* __restrict__ coef) {
     const int tid = threadIdx.x, ql = tid % a.QT, rt = tid / a.QT;
     const int q = blockIdx.x * a.QT + ql, chunk = blockIdx.y;
@@ -186,12 +217,11 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BnArgs a, const double* _
     const long r_begin = (long)chunk * a.rows_per, r_end = min(a.rows, r_begin + a.rows_per);
 #pragma unroll 4
     for (long r = r_begin + rt; r < r_end; r += a.RT) {
-        const float4 v4 = *reinterpret_cast<const float4*>(a.x + r * a.x_cs + a.x_co + 4 * q);
-        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-        float o[4];
+        float v[4], o[4];
+        bn_load4<T>(a.x, r * a.x_cs + a.x_co + 4 * q, v);
         if constexpr (BWD) {
-            const float4 g4 = *reinterpret_cast<const float4*>(a.dy + r * a.dy_cs + a.dy_co + 4 * q);
-            const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+            float g[4];
+            bn_load4<T>(a.dy, r * a.dy_cs + a.dy_co + 4 * q, g);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float xh = (v[e] - mean[e]) * rstd[e];
@@ -199,15 +229,15 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BnArgs a, const double* _
                 o[e] = (k1[e] * dz - c1[e]) - xh * c2[e];
             }
         } else if constexpr (RES) {
-            const float4 u4 = *reinterpret_cast<const float4*>(a.dy + r * a.dy_cs + a.dy_co + 4 * q);
-            const float u[4] = {u4.x, u4.y, u4.z, u4.w};
+            float u[4];
+            bn_load4<T>(a.dy, r * a.dy_cs + a.dy_co + 4 * q, u);
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = fd_act1(((v[e] - mean[e]) * rstd[e] * gm[e] + bt[e]) + u[e], a.act, 0.f);
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = fd_act1((v[e] - mean[e]) * rstd[e] * gm[e] + bt[e], a.act, 0.f);
         }
-        *reinterpret_cast<float4*>(a.out + r * a.out_cs + a.out_co + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
+        bn_store4<T>(a.out, r * a.out_cs + a.out_co + 4 * q, o);
     }
 }
 
@@ -231,6 +261,7 @@ struct BnLaunch {
     int32_t rc;
     BnArgs a;
     BnPart p;
+    bool half;                                          // the maps hold _Float16 (the `_h` entry points)
     const double* stat;
     double* head;                                       // [2][C] in front of the workspace: the forward's statistics, the backward's c1, c2
     double* part;                                       // [nchunk][2][C] behind it
@@ -245,13 +276,15 @@ struct BnLaunch {
 // bwd: the backward (g = dy, out = dx; else out = y and g = the residual view of the residual form `res`, otherwise unused).  sync: one phase of the
 // synchronised form -- rows from 1, and a call needs only what its phase touches (phase 1: the sums, and dgamma / dbeta in the backward; phase 2: out, and
 // gamma / beta / res in the forward), where the unsynchronised call runs both halves and needs all of it.  `who` names the entry point in the messages.
-static BnLaunch bn_prologue(const char* who, bool bwd, bool sync, bool res, const float* x, int32_t x_cs, int32_t x_co, const float* g, int32_t g_cs,
-                            int32_t g_co, const float* gamma, const float* beta, float* out, int32_t out_cs, int32_t out_co, const float* dgamma,
+// half: x, g and out hold _Float16 (8-byte aligned views); every check, its code and their order are the fp32 form's.
+static BnLaunch bn_prologue(const char* who, bool half, bool bwd, bool sync, bool res, const void* x, int32_t x_cs, int32_t x_co, const void* g, int32_t g_cs,
+                            int32_t g_co, const float* gamma, const float* beta, void* out, int32_t out_cs, int32_t out_co, const float* dgamma,
                             const float* dbeta, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, const double* sums, double total_rows,
                             const float* running_mean, const float* running_var, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
                             fd_stream_t stream) {
     BnLaunch L;
     L.rc = FD_OK;
+    L.half = half;
     BN_REQUIRE(bn_shape_ok(rows, C, sync ? 1 : 2), FD_E_UNSUPPORTED, "%s: rows=%lld C=%d unsupported (C %% 4 == 0, 4 <= C <= %d, %d <= rows < 2^31)", who,
                (long long)rows, C, BN_MAXC, sync ? 1 : 2);
     BN_REQUIRE(act == FD_ACT_NONE || act == FD_ACT_RELU || (!res && act == FD_ACT_SILU), FD_E_UNSUPPORTED,
@@ -259,8 +292,8 @@ static BnLaunch bn_prologue(const char* who, bool bwd, bool sync, bool res, cons
     BN_REQUIRE(!sync || phase == 1 || phase == 2, FD_E_UNSUPPORTED,
                bwd ? "%s: phase %d (1: this rank's sums, dgamma, dbeta; 2: dx)" : "%s: phase %d (1: this rank's sums, 2: statistics + apply)", who, phase);
     const bool first = !sync || phase == 1, second = !sync || phase == 2;
-    const bool in_ok = bn_view_ok(x, x_cs, x_co, C) && (!bwd || (bn_view_ok(g, g_cs, g_co, C) && gamma && beta));
-    const bool phase_ok = (!second || (bn_view_ok(out, out_cs, out_co, C) && gamma && beta && (!res || bn_view_ok(g, g_cs, g_co, C)))) &&
+    const bool in_ok = bn_view_ok(x, x_cs, x_co, C, half) && (!bwd || (bn_view_ok(g, g_cs, g_co, C, half) && gamma && beta));
+    const bool phase_ok = (!second || (bn_view_ok(out, out_cs, out_co, C, half) && gamma && beta && (!res || bn_view_ok(g, g_cs, g_co, C, half)))) &&
                           (!(bwd && first) || (dgamma && dbeta));
     if (!sync) {
         BN_REQUIRE(in_ok && phase_ok, FD_E_INVAL, "%s: bad pointer / channel view (C=%d)", who, C);
@@ -296,35 +329,82 @@ static BnLaunch bn_prologue(const char* who, bool bwd, bool sync, bool res, cons
 }
 #undef BN_REQUIRE
 
+// the two kinds of launch over the maps, on the element type of the entry point (same grid, same ownership)
+static void bn_launch_partial(const BnLaunch& L, bool bwd) {
+    const dim3 grid(L.p.ntile, L.p.nchunk);
+    if (!L.half) {
+        if (bwd) hipLaunchKernelGGL((bn_partial_kernel<true, float>), grid, dim3(256), 0, L.st, L.a, L.stat, L.part);
+        else hipLaunchKernelGGL((bn_partial_kernel<false, float>), grid, dim3(256), 0, L.st, L.a, L.stat, L.part);
+    } else {
+        if (bwd) hipLaunchKernelGGL((bn_partial_kernel<true, _Float16>), grid, dim3(256), 0, L.st, L.a, L.stat, L.part);
+        else hipLaunchKernelGGL((bn_partial_kernel<false, _Float16>), grid, dim3(256), 0, L.st, L.a, L.stat, L.part);
+    }
+}
+
+template <typename T> static void bn_launch_apply_t(const BnLaunch& L, bool bwd, bool res) {
+    const dim3 grid(L.p.ntile, L.p.nchunk);
+    if (bwd) hipLaunchKernelGGL((bn_apply_kernel<true, false, T>), grid, dim3(256), 0, L.st, L.a, L.stat, (const double*)L.head);
+    else if (res) hipLaunchKernelGGL((bn_apply_kernel<false, true, T>), grid, dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
+    else hipLaunchKernelGGL((bn_apply_kernel<false, false, T>), grid, dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
+}
+
+static void bn_launch_apply(const BnLaunch& L, bool bwd, bool res) {
+    if (!L.half) bn_launch_apply_t<float>(L, bwd, res);
+    else bn_launch_apply_t<_Float16>(L, bwd, res);
+}
+
 // the forward's launches; the residual form (`res` a fourth channel view, act in {NONE, RELU}) differs in the apply kernel alone
 static int32_t bn_fwd_launches(const BnLaunch& L, bool res, float eps, float momentum, const int64_t* nbt, float* running_mean, float* running_var) {
     const int C = L.a.C;
-    hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
+    bn_launch_partial(L, false);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (partial)");
     hipLaunchKernelGGL(bn_fwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, L.st, (const double*)L.part, L.p.nchunk, C, (double)L.a.rows, eps, momentum,
                        nbt, L.head, running_mean, running_var);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (statistics)");
-    if (!res) hipLaunchKernelGGL((bn_apply_kernel<false, false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
-    else hipLaunchKernelGGL((bn_apply_kernel<false, true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
+    bn_launch_apply(L, false, res);
     FD_CHECK_LAUNCH("fd_batchnorm_train_fwd (apply)");
     return FD_OK;
+}
+
+// Each entry point with a float momentum exists twice: on fp32 maps and, `_h`, on f16 maps.  One body serves both (half: the maps' element type;
+// res_form false: the plain form, `res` unused).
+static int32_t bn_train_fwd(const char* who, bool half, bool res_form, const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta,
+                            const void* res, int32_t res_cs, int32_t res_co, void* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
+                            int32_t act, float momentum, float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes,
+                            fd_stream_t stream) {
+    const BnLaunch L = bn_prologue(who, half, false, false, res_form, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co, nullptr, nullptr, rows,
+                                   C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
+    return L.rc != FD_OK ? L.rc : bn_fwd_launches(L, res_form, eps, momentum, nullptr, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
                                                int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, float momentum, float* running_mean,
                                                float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_fwd", false, false, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr, nullptr,
-                                   rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
-    return L.rc != FD_OK ? L.rc : bn_fwd_launches(L, false, eps, momentum, nullptr, running_mean, running_var);
+    return bn_train_fwd("fd_batchnorm_train_fwd", false, false, x, x_cs, x_co, gamma, beta, nullptr, 0, 0, y, y_cs, y_co, rows, C, eps, act, momentum,
+                        running_mean, running_var, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t fd_batchnorm_train_fwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, void* y, int32_t y_cs,
+                                                 int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, float momentum, float* running_mean,
+                                                 float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    return bn_train_fwd("fd_batchnorm_train_fwd_h", true, false, x, x_cs, x_co, gamma, beta, nullptr, 0, 0, y, y_cs, y_co, rows, C, eps, act, momentum,
+                        running_mean, running_var, workspace, workspace_bytes, stream);
 }
 
 extern "C" int32_t fd_batchnorm_train_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
                                                    int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
                                                    int32_t act, float momentum, float* running_mean, float* running_var, void* workspace,
                                                    int64_t workspace_bytes, fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_res_fwd", false, false, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co, nullptr,
-                                   nullptr, rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
-    return L.rc != FD_OK ? L.rc : bn_fwd_launches(L, true, eps, momentum, nullptr, running_mean, running_var);
+    return bn_train_fwd("fd_batchnorm_train_res_fwd", false, true, x, x_cs, x_co, gamma, beta, res, res_cs, res_co, y, y_cs, y_co, rows, C, eps, act, momentum,
+                        running_mean, running_var, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t fd_batchnorm_train_res_fwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const void* res,
+                                                     int32_t res_cs, int32_t res_co, void* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
+                                                     int32_t act, float momentum, float* running_mean, float* running_var, void* workspace,
+                                                     int64_t workspace_bytes, fd_stream_t stream) {
+    return bn_train_fwd("fd_batchnorm_train_res_fwd_h", true, true, x, x_cs, x_co, gamma, beta, res, res_cs, res_co, y, y_cs, y_co, rows, C, eps, act,
+                        momentum, running_mean, running_var, workspace, workspace_bytes, stream);
 }
 
 // ---- The cumulative moving average (nn.BatchNorm2d(momentum=None)): the `_cma` siblings take the layer's num_batches_tracked in DEVICE memory where the
@@ -339,7 +419,7 @@ static int32_t bn_counter_check(const char* who, const int64_t* nbt, const float
 extern "C" int32_t fd_batchnorm_train_fwd_cma_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
                                                    int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, const int64_t* num_batches_tracked,
                                                    float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_fwd_cma", false, false, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr,
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_fwd_cma", false, false, false, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr,
                                    nullptr, rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
     if (L.rc != FD_OK) return L.rc;
     const int32_t rc = bn_counter_check("fd_batchnorm_train_fwd_cma", num_batches_tracked, running_mean, running_var);
@@ -350,7 +430,7 @@ extern "C" int32_t fd_batchnorm_train_res_fwd_cma_nhwc(const float* x, int32_t x
                                                        int32_t res_cs, int32_t res_co, float* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C,
                                                        float eps, int32_t act, const int64_t* num_batches_tracked, float* running_mean, float* running_var,
                                                        void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_res_fwd_cma", false, false, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co,
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_res_fwd_cma", false, false, false, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co,
                                    nullptr, nullptr, rows, C, eps, act, 0, nullptr, 0.0, running_mean, running_var, nullptr, workspace, workspace_bytes,
                                    stream);
     if (L.rc != FD_OK) return L.rc;
@@ -358,21 +438,36 @@ extern "C" int32_t fd_batchnorm_train_res_fwd_cma_nhwc(const float* x, int32_t x
     return rc != FD_OK ? rc : bn_fwd_launches(L, true, eps, 0.f, num_batches_tracked, running_mean, running_var);
 }
 
-extern "C" int32_t fd_batchnorm_train_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
-                                               const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows,
-                                               int32_t C, float eps, int32_t act, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
-                                               fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_bwd", true, false, false, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta,
+static int32_t bn_train_bwd(const char* who, bool half, const void* x, int32_t x_cs, int32_t x_co, const void* dy, int32_t dy_cs, int32_t dy_co,
+                            const float* gamma, const float* beta, void* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows, int32_t C,
+                            float eps, int32_t act, const void* fwd_workspace, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    const BnLaunch L = bn_prologue(who, half, true, false, false, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta,
                                    rows, C, eps, act, 0, nullptr, 0.0, nullptr, nullptr, fwd_workspace, workspace, workspace_bytes, stream);
     if (L.rc != FD_OK) return L.rc;
-    hipLaunchKernelGGL((bn_partial_kernel<true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
+    bn_launch_partial(L, true);
     FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (partial)");
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(256), 0, L.st, (const double*)L.part, L.p.nchunk, C, (double)rows, gamma, L.stat, L.head,
                        dgamma, dbeta);
     FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (sums)");
-    hipLaunchKernelGGL((bn_apply_kernel<true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)L.head);
+    bn_launch_apply(L, true, false);
     FD_CHECK_LAUNCH("fd_batchnorm_train_bwd (apply)");
     return FD_OK;
+}
+
+extern "C" int32_t fd_batchnorm_train_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
+                                               const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows,
+                                               int32_t C, float eps, int32_t act, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
+                                               fd_stream_t stream) {
+    return bn_train_bwd("fd_batchnorm_train_bwd", false, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta, rows, C, eps, act,
+                        fwd_workspace, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t fd_batchnorm_train_bwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const void* dy, int32_t dy_cs, int32_t dy_co, const float* gamma,
+                                                 const float* beta, void* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows,
+                                                 int32_t C, float eps, int32_t act, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
+                                                 fd_stream_t stream) {
+    return bn_train_bwd("fd_batchnorm_train_bwd_h", true, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta, rows, C, eps, act,
+                        fwd_workspace, workspace, workspace_bytes, stream);
 }
 
 // ---- The synchronised form (nn.SyncBatchNorm at these widths): each direction cut in two around ONE all-reduce that the CALLER issues.
@@ -415,7 +510,7 @@ static int32_t bn_sync_fwd_launches(const BnLaunch& L, bool res, int32_t phase, 
                                     const int64_t* nbt, float* running_mean, float* running_var) {
     const int C = L.a.C;
     if (phase == 1) {
-        hipLaunchKernelGGL((bn_partial_kernel<false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
+        bn_launch_partial(L, false);
         FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (partial)");
         hipLaunchKernelGGL(bn_wide_sync_sums_kernel, dim3((C + 63) / 64), dim3(256), 0, L.st, (const double*)L.part, L.p.nchunk, C, sums, (float*)nullptr,
                            (float*)nullptr);
@@ -425,19 +520,34 @@ static int32_t bn_sync_fwd_launches(const BnLaunch& L, bool res, int32_t phase, 
     hipLaunchKernelGGL(bn_wide_sync_fwd_final_kernel, dim3((C + 255) / 256), dim3(256), 0, L.st, (const double*)sums, C, total_rows, eps, momentum, nbt,
                        L.head, running_mean, running_var);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (statistics)");
-    if (!res) hipLaunchKernelGGL((bn_apply_kernel<false, false>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
-    else hipLaunchKernelGGL((bn_apply_kernel<false, true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)nullptr);
+    bn_launch_apply(L, false, res);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_fwd (apply)");
     return FD_OK;
+}
+
+static int32_t bn_train_sync_fwd(const char* who, bool half, bool res_form, const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta,
+                                 const void* res, int32_t res_cs, int32_t res_co, void* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps,
+                                 int32_t act, int32_t phase, double* sums, double total_rows, float momentum, float* running_mean, float* running_var,
+                                 void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    const BnLaunch L = bn_prologue(who, half, false, true, res_form, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co, nullptr, nullptr, rows, C,
+                                   eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
+    return L.rc != FD_OK ? L.rc : bn_sync_fwd_launches(L, res_form, phase, sums, total_rows, eps, momentum, nullptr, running_mean, running_var);
 }
 
 extern "C" int32_t fd_batchnorm_train_sync_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, float* y, int32_t y_cs,
                                                     int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums,
                                                     double total_rows, float momentum, float* running_mean, float* running_var, void* workspace,
                                                     int64_t workspace_bytes, fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_fwd", false, true, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr, nullptr,
-                                   rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
-    return L.rc != FD_OK ? L.rc : bn_sync_fwd_launches(L, false, phase, sums, total_rows, eps, momentum, nullptr, running_mean, running_var);
+    return bn_train_sync_fwd("fd_batchnorm_train_sync_fwd", false, false, x, x_cs, x_co, gamma, beta, nullptr, 0, 0, y, y_cs, y_co, rows, C, eps, act, phase,
+                             sums, total_rows, momentum, running_mean, running_var, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t fd_batchnorm_train_sync_fwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, void* y, int32_t y_cs,
+                                                      int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums,
+                                                      double total_rows, float momentum, float* running_mean, float* running_var, void* workspace,
+                                                      int64_t workspace_bytes, fd_stream_t stream) {
+    return bn_train_sync_fwd("fd_batchnorm_train_sync_fwd_h", true, false, x, x_cs, x_co, gamma, beta, nullptr, 0, 0, y, y_cs, y_co, rows, C, eps, act, phase,
+                             sums, total_rows, momentum, running_mean, running_var, workspace, workspace_bytes, stream);
 }
 
 extern "C" int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const float* res,
@@ -445,9 +555,17 @@ extern "C" int32_t fd_batchnorm_train_sync_res_fwd_nhwc(const float* x, int32_t 
                                                         float eps, int32_t act, int32_t phase, double* sums, double total_rows, float momentum,
                                                         float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes,
                                                         fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_res_fwd", false, true, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co, nullptr,
-                                   nullptr, rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace, workspace_bytes, stream);
-    return L.rc != FD_OK ? L.rc : bn_sync_fwd_launches(L, true, phase, sums, total_rows, eps, momentum, nullptr, running_mean, running_var);
+    return bn_train_sync_fwd("fd_batchnorm_train_sync_res_fwd", false, true, x, x_cs, x_co, gamma, beta, res, res_cs, res_co, y, y_cs, y_co, rows, C, eps, act,
+                             phase, sums, total_rows, momentum, running_mean, running_var, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t fd_batchnorm_train_sync_res_fwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const float* gamma, const float* beta, const void* res,
+                                                          int32_t res_cs, int32_t res_co, void* y, int32_t y_cs, int32_t y_co, int64_t rows, int32_t C,
+                                                          float eps, int32_t act, int32_t phase, double* sums, double total_rows, float momentum,
+                                                          float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes,
+                                                          fd_stream_t stream) {
+    return bn_train_sync_fwd("fd_batchnorm_train_sync_res_fwd_h", true, true, x, x_cs, x_co, gamma, beta, res, res_cs, res_co, y, y_cs, y_co, rows, C, eps,
+                             act, phase, sums, total_rows, momentum, running_mean, running_var, workspace, workspace_bytes, stream);
 }
 
 // the `_cma` siblings of the two synchronised forwards; phase 1 does not look at the counter, as it does not look at the momentum
@@ -455,7 +573,7 @@ extern "C" int32_t fd_batchnorm_train_sync_fwd_cma_nhwc(const float* x, int32_t 
                                                         int32_t y_cs, int32_t y_co, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase,
                                                         double* sums, double total_rows, const int64_t* num_batches_tracked, float* running_mean,
                                                         float* running_var, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_fwd_cma", false, true, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr,
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_fwd_cma", false, false, true, false, x, x_cs, x_co, nullptr, 0, 0, gamma, beta, y, y_cs, y_co, nullptr,
                                    nullptr, rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace, workspace_bytes,
                                    stream);
     if (L.rc != FD_OK) return L.rc;
@@ -468,7 +586,7 @@ extern "C" int32_t fd_batchnorm_train_sync_res_fwd_cma_nhwc(const float* x, int3
                                                             int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums, double total_rows,
                                                             const int64_t* num_batches_tracked, float* running_mean, float* running_var, void* workspace,
                                                             int64_t workspace_bytes, fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_res_fwd_cma", false, true, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co,
+    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_res_fwd_cma", false, false, true, true, x, x_cs, x_co, res, res_cs, res_co, gamma, beta, y, y_cs, y_co,
                                    nullptr, nullptr, rows, C, eps, act, phase, sums, total_rows, running_mean, running_var, nullptr, workspace,
                                    workspace_bytes, stream);
     if (L.rc != FD_OK) return L.rc;
@@ -476,15 +594,15 @@ extern "C" int32_t fd_batchnorm_train_sync_res_fwd_cma_nhwc(const float* x, int3
     return rc != FD_OK ? rc : bn_sync_fwd_launches(L, true, phase, sums, total_rows, eps, 0.f, num_batches_tracked, running_mean, running_var);
 }
 
-extern "C" int32_t fd_batchnorm_train_sync_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co,
-                                                    const float* gamma, const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta,
-                                                    int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums, double total_rows,
-                                                    const void* fwd_workspace, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
-    const BnLaunch L = bn_prologue("fd_batchnorm_train_sync_bwd", true, true, false, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta,
+static int32_t bn_train_sync_bwd(const char* who, bool half, const void* x, int32_t x_cs, int32_t x_co, const void* dy, int32_t dy_cs, int32_t dy_co,
+                                 const float* gamma, const float* beta, void* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta, int64_t rows,
+                                 int32_t C, float eps, int32_t act, int32_t phase, double* sums, double total_rows, const void* fwd_workspace, void* workspace,
+                                 int64_t workspace_bytes, fd_stream_t stream) {
+    const BnLaunch L = bn_prologue(who, half, true, true, false, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta,
                                    rows, C, eps, act, phase, sums, total_rows, nullptr, nullptr, fwd_workspace, workspace, workspace_bytes, stream);
     if (L.rc != FD_OK) return L.rc;
     if (phase == 1) {
-        hipLaunchKernelGGL((bn_partial_kernel<true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, L.part);
+        bn_launch_partial(L, true);
         FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (partial)");
         hipLaunchKernelGGL(bn_wide_sync_sums_kernel, dim3((C + 63) / 64), dim3(256), 0, L.st, (const double*)L.part, L.p.nchunk, C, sums, dgamma, dbeta);
         FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (sums)");
@@ -492,9 +610,26 @@ extern "C" int32_t fd_batchnorm_train_sync_bwd_nhwc(const float* x, int32_t x_cs
     }
     hipLaunchKernelGGL(bn_wide_sync_bwd_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, L.st, (const double*)sums, C, total_rows, gamma, L.stat, L.head);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (coefficients)");
-    hipLaunchKernelGGL((bn_apply_kernel<true>), dim3(L.p.ntile, L.p.nchunk), dim3(256), 0, L.st, L.a, L.stat, (const double*)L.head);
+    bn_launch_apply(L, true, false);
     FD_CHECK_LAUNCH("fd_batchnorm_train_sync_bwd (apply)");
     return FD_OK;
+}
+
+extern "C" int32_t fd_batchnorm_train_sync_bwd_nhwc(const float* x, int32_t x_cs, int32_t x_co, const float* dy, int32_t dy_cs, int32_t dy_co,
+                                                    const float* gamma, const float* beta, float* dx, int32_t dx_cs, int32_t dx_co, float* dgamma, float* dbeta,
+                                                    int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums, double total_rows,
+                                                    const void* fwd_workspace, void* workspace, int64_t workspace_bytes, fd_stream_t stream) {
+    return bn_train_sync_bwd("fd_batchnorm_train_sync_bwd", false, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta, rows, C, eps,
+                             act, phase, sums, total_rows, fwd_workspace, workspace, workspace_bytes, stream);
+}
+
+extern "C" int32_t fd_batchnorm_train_sync_bwd_nhwc_h(const void* x, int32_t x_cs, int32_t x_co, const void* dy, int32_t dy_cs, int32_t dy_co,
+                                                      const float* gamma, const float* beta, void* dx, int32_t dx_cs, int32_t dx_co, float* dgamma,
+                                                      float* dbeta, int64_t rows, int32_t C, float eps, int32_t act, int32_t phase, double* sums,
+                                                      double total_rows, const void* fwd_workspace, void* workspace, int64_t workspace_bytes,
+                                                      fd_stream_t stream) {
+    return bn_train_sync_bwd("fd_batchnorm_train_sync_bwd_h", true, x, x_cs, x_co, dy, dy_cs, dy_co, gamma, beta, dx, dx_cs, dx_co, dgamma, dbeta, rows, C,
+                             eps, act, phase, sums, total_rows, fwd_workspace, workspace, workspace_bytes, stream);
 }
 
 // ---- drop-connect: y = a * s[n] + r on [N][HW][C] channel views, s one fp32 per sample ON THE DEVICE (0 or 1 / (1 - p)), r may be NULL (the backward of the

@@ -40,6 +40,7 @@ class _Trunk(nn.Module):
 
     hip_stem_train = False       # opt-in: a trainable stem on the HIP node (train_ops.stem_rows) instead of stock ops
     hip_bn_train = False         # opt-in: bottlenecks whose BatchNorms are in training mode run on the batch-statistics HIP nodes instead of stock BatchNorm
+    hip_bn_f16_maps = False      # opt-in beside it: under torch.autocast(float16) those blocks keep f16 maps (the `_h` BatchNorm kernels)
 
     def __init__(self):
         super().__init__()
@@ -82,7 +83,8 @@ def trunk_train_forward(trunk: nn.Module, x: torch.Tensor):
     HIP launch (conv + frozen BN + residual + ReLU, train_ops.conv_bn_act) differentiated by the HIP data- / weight-
     gradient kernels; a frozen stem (freeze_stages(1)) runs on the inference kernels; a trainable one runs on train_ops.stem_rows (the stem kernel +
     fd_stem7x7_bwd_weight_nhwc4) when `trunk.hip_stem_train` is set, else on stock ops.  With `trunk.hip_bn_train` set, a block whose BatchNorms are in
-    training mode runs on the batch-statistics nodes (train_ops._bottleneck_bn_rows) instead of conv on HIP + stock BatchNorm.  Returns (C3, C4, C5)."""
+    training mode runs on the batch-statistics nodes (train_ops._bottleneck_bn_rows) instead of conv on HIP + stock BatchNorm, and with
+    `trunk.hip_bn_f16_maps` beside it on f16 maps under torch.autocast(float16).  Returns (C3, C4, C5)."""
     import torch.nn.functional as F
 
     from ...train_ops import bottleneck, stem_frozen, stem_is_frozen, stem_rows, stem_rows_ok
@@ -96,10 +98,11 @@ def trunk_train_forward(trunk: nn.Module, x: torch.Tensor):
         x = F.max_pool2d(F.relu(trunk.bn1(trunk.conv1(x))), 3, 2, 1)
     feats = []
     batch_stats = bool(getattr(trunk, "hip_bn_train", False))
+    f16_maps = batch_stats and bool(getattr(trunk, "hip_bn_f16_maps", False))
     for li in (1, 2, 3, 4):
         for blk in getattr(trunk, f"layer{li}"):
             # frozen BatchNorm: one autograd node per block (train_ops._BottleneckRows); the switch adds the per-block choice of the batch-statistics path
-            x = bottleneck(blk, x, batch_stats=True) if batch_stats else bottleneck(blk, x)
+            x = bottleneck(blk, x, batch_stats=True, f16_maps=f16_maps) if batch_stats else bottleneck(blk, x)
         feats.append(x)
     return feats[1], feats[2], feats[3]
 
@@ -139,6 +142,15 @@ class ResNet50v2(nn.Module):
     def hip_bn_train(self, on: bool) -> None:
         self.extract_feature.hip_bn_train = bool(on)
 
+    @property
+    def hip_bn_f16_maps(self) -> bool:
+        """Opt-in (default False) beside hip_bn_train: those blocks keep f16 maps under torch.autocast(float16).  Lives on the trunk too."""
+        return self.extract_feature.hip_bn_f16_maps
+
+    @hip_bn_f16_maps.setter
+    def hip_bn_f16_maps(self, on: bool) -> None:
+        self.extract_feature.hip_bn_f16_maps = bool(on)
+
     forward = _no_torch_forward
     freeze_bn, freeze_stages = _freeze_bn, _freeze_stages
 
@@ -148,6 +160,7 @@ class ResNet50(nn.Module):
 
     hip_stem_train = False       # opt-in: a trainable stem on the HIP node (train_ops.stem_rows) instead of stock ops
     hip_bn_train = False         # opt-in: BatchNorms in training mode on the batch-statistics HIP nodes (PlannedModule.enable_trunk_batch_stats)
+    hip_bn_f16_maps = False      # opt-in beside it: f16 maps on those nodes under torch.autocast(float16) (enable_trunk_batch_stats(f16_maps=True))
 
     def __init__(self, re_layer: int = 1):
         super().__init__()

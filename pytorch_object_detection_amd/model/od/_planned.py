@@ -99,12 +99,15 @@ class PlannedModule(nn.Module):
                 for p in m.parameters():
                     p.requires_grad = False
 
-    def enable_trunk_batch_stats(self):
+    def enable_trunk_batch_stats(self, f16_maps: bool = False):
         """Opt in to training the ResNet-50 trunk on BATCH statistics on the HIP nodes (backbone.trunk.hip_bn_train): every bottleneck whose BatchNorms are in
         training mode runs conv -> batch-statistics BatchNorm -> ReLU on rows (train_ops.conv_norm_act_rows) and its output relu(bn3(conv3(.)) + identity) as
         one residual apply pass (fd_batchnorm_train_res_fwd_nhwc), also as nn.SyncBatchNorm across ranks; frozen blocks keep their fused node.  Needs a model
         whose constructor left the BatchNorms trainable (bn_freeze=False / freeze_bn=False).  Without this call such a model trains with the convs on HIP
-        and stock BatchNorm.  The sibling of enable_stem_training().  Returns self."""
+        and stock BatchNorm.  The sibling of enable_stem_training().  Returns self.
+        f16_maps (backbone.trunk.hip_bn_f16_maps, default off): under torch.autocast(float16) these blocks keep their maps and gradients in f16, as the
+        frozen blocks do -- the raw conv outputs are stored as f16 and every BatchNorm of the block runs on the f16-map kernels (fd_batchnorm_train_*_nhwc_h:
+        the fp32 kernels' arithmetic, one rounding at the store).  Without autocast the switch changes nothing."""
         if getattr(self, "efficientnet", False):
             raise FdError("enable_trunk_batch_stats() is for the ResNet-50 trunk; FCOS(efficientnet=True) trains on batch statistics through "
                           "enable_training(batch_stats=True)")
@@ -114,6 +117,7 @@ class PlannedModule(nn.Module):
         if getattr(self, "backbone_freeze", False):
             raise FdError("enable_trunk_batch_stats() needs a model constructed with bn_freeze=False / freeze_bn=False (this one froze its BatchNorm layers)")
         trunk.hip_bn_train = True
+        trunk.hip_bn_f16_maps = bool(f16_maps)
         return self
 
     # ---- what a detector (backbone + FPN + head) supplies, and what it gets for it ----

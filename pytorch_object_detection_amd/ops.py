@@ -1670,11 +1670,22 @@ def batchnorm_train_workspace(rows: int, Cc: int, device) -> torch.Tensor:
 
 
 def _bn_res_check(who: str, x: Rows, res: Optional[Rows], act_id: int) -> None:
-    """The residual forms' own contract: act in {NONE, RELU} (the backward takes its mask from y) and an fp32 residual view of x's shape."""
+    """The residual forms' own contract: act in {NONE, RELU} (the backward takes its mask from y) and a residual view of x's shape (and element type:
+    _bn_maps_f16)."""
     if act_id not in (ACT_NONE, ACT_RELU):
         raise FdError(f"{who}: act must be ACT_NONE or ACT_RELU (the backward takes its mask from the output)", rc=_lib.E_UNSUPPORTED)
-    if res is not None and (res.f16 or res.C != x.C or res.rows != x.rows):
-        raise FdError(f"{who}: the residual must be an fp32 view of x's shape")
+    if res is not None and (res.C != x.C or res.rows != x.rows):
+        raise FdError(f"{who}: the residual must be a view of x's shape")
+
+
+def _bn_maps_f16(who: str, x: Rows, **maps: Optional[Rows]) -> bool:
+    """The element type of one call's map operands: all fp32 (False) or all f16 (True: the `_h` entry point), x deciding.  A map of the other type is
+    refused by name -- the kernels convert nothing between maps."""
+    for name, m in maps.items():
+        if m is not None and m.f16 != x.f16:
+            raise FdError(f"{who}: {name} is {'an f16' if m.f16 else 'an fp32'} map but x is {'f16' if x.f16 else 'fp32'}: the map operands of one call "
+                          "share one element type")
+    return x.f16
 
 
 def _bn_sums_check(who: str, sums: torch.Tensor, Cc: int) -> None:
@@ -1706,12 +1717,15 @@ def _bn_train_fwd(who: str, res_form: bool, phase: Optional[int], x, sums, gamma
     """The one body of the four any-width forward wrappers, fd_<who>_nhwc: phase None = the unsynchronised entry point (no phase, sums, total_rows
     operands), res_form = the entry point that takes a residual view behind beta."""
     _need_gpu(x.buf, sums, gamma, beta, res.buf if res is not None else None, y.buf if y is not None else None, running_mean, running_var, ws)
-    if x.f16 or (y is not None and (y.f16 or y.C != x.C or y.rows != x.rows)) or any(t is not None and t.numel() != x.C for t in (gamma, beta)):
-        raise FdError(f"{who}: fp32 views of the same shape and C-element gamma / beta expected")
+    if (y is not None and (y.C != x.C or y.rows != x.rows)) or any(t is not None and t.numel() != x.C for t in (gamma, beta)):
+        raise FdError(f"{who}: views of the same shape and C-element gamma / beta expected")
+    half = _bn_maps_f16(who, x, res=res, y=y)
     if res_form:
         _bn_res_check(who, x, res, act_id)
     cma, running = _bn_running_args(momentum, running_mean, running_var)
-    name = f"fd_{who}_cma_nhwc" if cma else f"fd_{who}_nhwc"
+    if cma and half:
+        raise FdError(f"{who}: the cumulative moving average (momentum=None) has no f16-map form; hand it fp32 maps", rc=_lib.E_UNSUPPORTED)
+    name = f"fd_{who}_cma_nhwc" if cma else f"fd_{who}_nhwc_h" if half else f"fd_{who}_nhwc"
     if phase is None:
         sync, sym = (), name
     else:
@@ -1726,7 +1740,9 @@ def _bn_train_fwd(who: str, res_form: bool, phase: Optional[int], x, sums, gamma
 
 def batchnorm_train_fwd(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, y: Rows, eps: float, act_id: int = ACT_NONE, momentum: Optional[float] = None,
                         running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = act(BatchNorm(x)) on the batch statistics of the fp32 channel view x (fd_batchnorm_train_fwd_nhwc: any C % 4 == 0 up to 4096).  With `momentum`
+    """y = act(BatchNorm(x)) on the batch statistics of the channel view x (fd_batchnorm_train_fwd_nhwc: any C % 4 == 0 up to 4096).  x and y -- in this and
+    the wrappers below every MAP operand: x, res, y, dy, dx -- are all fp32 or all f16 Rows; f16 maps go to the `_h` entry point, whose y / dx are the fp32
+    kernel's rounded to f16 once and whose statistics, running tensors, dgamma / dbeta and sums are the fp32 kernel's bits (float momentum only).  With `momentum`
     and the running tensors given they are updated in place like nn.BatchNorm2d's.  `momentum` in this and the three wrappers below: a float, or the
     layer's live num_batches_tracked tensor for nn.BatchNorm2d(momentum=None) -- the `_cma` entry point then reads it on the device and blends with 1 / n,
     bit for bit the float form at float32(1 / n).  Returns the workspace batchnorm_train_bwd needs."""
@@ -1774,16 +1790,17 @@ def batchnorm_train_sync_res_fwd(phase: int, x: Rows, sums: torch.Tensor, gamma:
 def _bn_train_bwd(who: str, phase: Optional[int], x, dy, gamma, beta, sums, fwd_ws, dx, dgamma, dbeta, eps, act_id, total_rows, ws) -> torch.Tensor:
     """The one body of the two any-width backward wrappers, fd_<who>_nhwc (phase None: the unsynchronised entry point)."""
     _need_gpu(x.buf, dy.buf, dx.buf if dx is not None else None, gamma, beta, sums, fwd_ws, dgamma, dbeta, ws)
-    if x.f16 or dy.f16 or x.C != dy.C or x.rows != dy.rows or (dx is not None and (dx.f16 or dx.C != x.C or dx.rows != x.rows)):
-        raise FdError(f"{who}: fp32 views of the same shape expected")
+    if x.C != dy.C or x.rows != dy.rows or (dx is not None and (dx.C != x.C or dx.rows != x.rows)):
+        raise FdError(f"{who}: views of the same shape expected")
+    name = f"fd_{who}_nhwc_h" if _bn_maps_f16(who, x, dy=dy, dx=dx) else f"fd_{who}_nhwc"
     if phase is None:
-        sync, sym = (), f"fd_{who}_nhwc"
+        sync, sym = (), name
     else:
         _bn_sums_check(who, sums, x.C)
-        sync, sym = (phase, sums.data_ptr(), float(total_rows)), f"fd_{who}_nhwc (phase {phase})"
+        sync, sym = (phase, sums.data_ptr(), float(total_rows)), f"{name} (phase {phase})"
     if ws is None:
         ws = (batchnorm_train_workspace if phase is None else batchnorm_train_sync_workspace)(x.rows, x.C, x.buf.device)
-    check(getattr(_lib.lib(), f"fd_{who}_nhwc")(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gamma.data_ptr(), beta.data_ptr(), *_view3(dx), _dptr(dgamma),
+    check(getattr(_lib.lib(), name)(x.ptr, x.cs, x.co, dy.ptr, dy.cs, dy.co, gamma.data_ptr(), beta.data_ptr(), *_view3(dx), _dptr(dgamma),
                                                 _dptr(dbeta), x.rows, x.C, float(eps), act_id, *sync, fwd_ws.data_ptr(), ws.data_ptr(),
                                                 ws.numel() * ws.element_size(), _stream()), sym)
     return ws

@@ -20,7 +20,9 @@ over the whole pyramid exactly as at inference.
   stem_rows                 the trainable 7x7 stem (Cin = 3), opt-in (trunk.hip_stem_train): fd_stem7x7_nhwc4 forward, fd_stem7x7_bwd_weight_nhwc4 backward.
   batchnorm_train_res_rows  act(bn(x) + res) on batch statistics, the output of a ResNet bottleneck: fd_batchnorm_train_res_fwd_nhwc forward (the add and the ReLU in the
                             apply pass), ReLU-mask pass + fd_batchnorm_train_bwd_nhwc backward; bottleneck(blk, x, batch_stats=True) = the whole block with its
-                            BatchNorms in training mode, opt-in (trunk.hip_bn_train), nn.SyncBatchNorm across ranks included.
+                            BatchNorms in training mode, opt-in (trunk.hip_bn_train), nn.SyncBatchNorm across ranks included.  With f16_maps=True
+                            (trunk.hip_bn_f16_maps) under torch.autocast(float16) those nodes keep f16 maps: _BatchNormWideRowsH, _BatchNormResRowsH,
+                            _SyncBatchNormApplyH on fd_batchnorm_train_*_nhwc_h, the raw conv outputs stored as f16.
 
 What the kernels do not cover falls back to stock PyTorch-ROCm ops on the GPU: the data gradient of strided layers other than the
 parity-class geometries and of layers padded by more than dil * (k - 1) (the rungs of _dense_dgrad), a padding='same' that torch pads asymmetrically,
@@ -575,30 +577,42 @@ class _BottleneckRows(torch.autograd.Function):
         return gx, gw1, gw2, gw3, gwd, None, None, None, None, None, None, None
 
 
-def _bottleneck_bn_rows(blk: nn.Module, x: torch.Tensor) -> torch.Tensor:
+def _bottleneck_bn_rows(blk: nn.Module, x: torch.Tensor, f16_maps: bool = False) -> torch.Tensor:
     """A bottleneck whose BatchNorms run on batch statistics (any of them may also be frozen), every layer a HIP node on rows: conv1/bn1/ReLU, conv2/bn2/ReLU
     and the downsample conv/BN through conv_norm_act_rows' dispatch, then the raw conv3 and act(bn3(.) + identity) as one node (batchnorm_train_res_rows).
-    Across ranks the downsample BatchNorm's statistics all-reduce is issued before conv1 and waited for where the residual is needed."""
+    Across ranks the downsample BatchNorm's statistics all-reduce is issued before conv1 and waited for where the residual is needed.
+    f16_maps (the trunk's opt-in hip_bn_f16_maps) under torch.autocast(float16) with AMP_F16_STORE; otherwise the graph is the one above, unchanged.  The
+    f16 maps are then: the raw output of every conv that feeds a BatchNorm in training mode with a float momentum, and that BatchNorm's output (the
+    any-width `_h` kernels at every width, narrow ones included); the output of every conv with a frozen BatchNorm folded in, the downsample's and conv3's
+    included; hence y1, y2, the identity and the block's output whenever their BatchNorm is one of those two kinds -- what _BottleneckRows keeps in f16.  A
+    BatchNorm with momentum=None keeps the fp32 node behind a raw fp32 conv output, so its own output map (and, for bn3, the block's) is fp32; its
+    neighbours take either type as it comes, and an fp32 identity reaching an f16 bn3 node is converted once on entry."""
     B, _, H, W = x.shape
     ds, s = blk.downsample, blk.conv2.stride[0]
     segs = Segs.make(B, [(H, W)])
     so = ops.conv_out_segs(segs, 3, s, 1, 1)
     xr = to_rows(x)
-    hd = conv_norm_begin(ds[0], ds[1], xr, segs, ACT_NONE) if ds is not None else None
-    y = conv_norm_act_rows(blk.conv1, blk.bn1, xr, segs, ACT_RELU)
-    y = conv_norm_act_rows(blk.conv2, blk.bn2, y, segs, ACT_RELU)
+    hd = conv_norm_begin(ds[0], ds[1], xr, segs, ACT_NONE, f16_maps) if ds is not None else None
+    y = conv_norm_act_rows(blk.conv1, blk.bn1, xr, segs, ACT_RELU, f16_maps)
+    y = conv_norm_act_rows(blk.conv2, blk.bn2, y, segs, ACT_RELU, f16_maps)
     idt = xr if ds is None else conv_norm_finish(hd)
+    f16_maps = _f16_maps_on(f16_maps)
     if bn_is_frozen(blk.bn3):
-        out = conv_rows(blk.conv3, y, so, blk.bn3, ACT_RELU, residual=idt.float())      # (fp32 maps on this path, whatever the block before stored)
+        if f16_maps:
+            out = conv_rows(blk.conv3, y, so, blk.bn3, ACT_RELU, residual=idt, out_f16=True)
+        else:
+            out = conv_rows(blk.conv3, y, so, blk.bn3, ACT_RELU, residual=idt.float())      # (fp32 maps on this path, whatever the block before stored)
     else:
-        out = batchnorm_train_res_rows(blk.bn3, conv_rows(blk.conv3, y, so, None, ACT_NONE), idt, ACT_RELU)
+        f16 = _bn_f16_ok(blk.bn3, f16_maps)
+        out = batchnorm_train_res_rows(blk.bn3, conv_rows(blk.conv3, y, so, None, ACT_NONE, out_f16=f16), idt, ACT_RELU, f16=f16)
     return from_rows(out, B, so.H[0], so.W[0])
 
 
-def bottleneck(blk: nn.Module, x: torch.Tensor, batch_stats: bool = False) -> torch.Tensor:
+def bottleneck(blk: nn.Module, x: torch.Tensor, batch_stats: bool = False, f16_maps: bool = False) -> torch.Tensor:
     """torchvision-style Bottleneck (conv1/bn1, conv2/bn2, conv3/bn3, optional downsample) on an NCHW-shaped tensor: one
     fused autograd node when every BatchNorm is frozen and the shapes are covered, else layer by layer (conv_bn_act).  batch_stats (the trunk's opt-in
-    hip_bn_train): a covered block with BatchNorms in training mode runs on the batch-statistics nodes instead (_bottleneck_bn_rows)."""
+    hip_bn_train): a covered block with BatchNorms in training mode runs on the batch-statistics nodes instead (_bottleneck_bn_rows); f16_maps (the trunk's
+    hip_bn_f16_maps, read with batch_stats only): those nodes keep f16 maps under torch.autocast(float16)."""
     _need_cuda(x)
     ds = blk.downsample
     bns = [blk.bn1, blk.bn2, blk.bn3] + ([ds[1]] if ds is not None else [])
@@ -609,7 +623,7 @@ def bottleneck(blk: nn.Module, x: torch.Tensor, batch_stats: bool = False) -> to
                  and (ds is None or (ds[0].kernel_size == (1, 1) and ds[0].stride == blk.conv2.stride)))
     ok = shapes_ok and all(bn_is_frozen(b) for b in bns)
     if batch_stats and shapes_ok and not ok and all(bn_is_frozen(b) or _bn_family(b, x) is not None for b in bns):
-        return _bottleneck_bn_rows(blk, x)
+        return _bottleneck_bn_rows(blk, x, f16_maps)
     if not ok:
         idt = x if ds is None else conv_bn_act(ds[0], ds[1], x, ACT_NONE)
         y = conv_bn_act(blk.conv1, blk.bn1, x, ACT_RELU)
@@ -1188,7 +1202,7 @@ def flush_pending() -> None:
 
 
 class _SyncHandle:
-    __slots__ = ("bn", "x", "act", "group", "buf", "ws", "work", "launches_at_issue", "defer", "wide", "fwd", "bwd", "res_fwd")
+    __slots__ = ("bn", "x", "act", "group", "buf", "ws", "work", "launches_at_issue", "defer", "wide", "fwd", "bwd", "res_fwd", "f16")
 
 
 # THE place the synchronised code looks at the kernel family, keyed by syncbn_begin's `wide`: the family's two-phase forward and backward wrappers (both
@@ -1197,18 +1211,23 @@ _SYNC_KERNELS = {False: (ops.batchnorm_sync_fwd, ops.batchnorm_sync_bwd, None),
                  True: (ops.batchnorm_train_sync_fwd, ops.batchnorm_train_sync_bwd, ops.batchnorm_train_sync_res_fwd)}
 
 
-def syncbn_begin(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE, defer_backward: bool = False, wide: bool = False) -> "_SyncHandle":
+def syncbn_begin(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE, defer_backward: bool = False, wide: bool = False,
+                 f16: bool = False) -> "_SyncHandle":
     """Phase 1 of nn.SyncBatchNorm's forward on rows + the asynchronous all-reduce of the [2C + 1] fp64 buffer (sums and row count).  wide: the any-width
     kernel family (fd_batchnorm_train_sync_*; check with _bn_train_wide_ok) on the C-channel view of x [rows, Cw >= C] -- the MBConv trunk's round32(C) maps
     with zero pad channels, which the output and the input gradient keep; otherwise the GroupNorm-route family (fd_batchnorm_sync_*; _bn_train_ok), whose
-    callers pass x [rows, C].  Everything behind the choice of the wrappers -- the collective, the handle, SYNC_TRACE, the deferred backward -- is the same."""
+    callers pass x [rows, C].  Everything behind the choice of the wrappers -- the collective, the handle, SYNC_TRACE, the deferred backward -- is the same.
+    f16 (wide only; _bn_f16_ok): x is read as an f16 map and syncbn_finish gives the f16-map node (_SyncBatchNormApplyH); the all-reduced buffer is the
+    same fp64 one."""
     import torch.distributed as dist
+    if f16 and not wide:
+        raise FdError("syncbn_begin(f16=True): the f16-map kernels are the any-width family's (wide=True)")
     h = _SyncHandle()
-    h.bn, h.act, h.defer, h.wide = bn, act, defer_backward, wide
+    h.bn, h.act, h.defer, h.wide, h.f16 = bn, act, defer_backward, wide, f16
     h.fwd, h.bwd, h.res_fwd = _SYNC_KERNELS[wide]          # (everything below calls these: `wide` itself is read nowhere else)
     h.group = bn.process_group if bn.process_group is not None else dist.group.WORLD
     with torch.no_grad():
-        xd = x.detach().float().contiguous()
+        xd = (_as_f16(x.detach()) if f16 else x.detach().float()).contiguous()
         rows, Cc = xd.shape[0], bn.num_features
         if xd.shape[1] < Cc or xd.shape[1] % 4:
             raise FdError(f"SyncBatchNorm({Cc}) on rows of shape {tuple(x.shape)}: rows of at least {Cc} channels (a multiple of 4) expected")
@@ -1228,7 +1247,8 @@ def syncbn_finish(h: "_SyncHandle", res: Optional[torch.Tensor] = None) -> torch
         bn.num_batches_tracked.add_(1)
     if res is not None and (h.res_fwd is None or h.defer):
         raise FdError("syncbn_finish(res=...): the residual form exists for the any-width kernels (wide=True) without a deferred backward")
-    return _SyncBatchNormApply.apply(h.x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, h.act, h)
+    node = _SyncBatchNormApplyH if h.f16 else _SyncBatchNormApply
+    return node.apply(h.x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, h.act, h)
 
 
 def _syncbn_backward(x, g, gm, bt, ws, buf, eps, act, group, defer, bwd):
@@ -1236,7 +1256,7 @@ def _syncbn_backward(x, g, gm, bt, ws, buf, eps, act, group, defer, bwd):
     and phase 2 -- run here, or left pending for the consuming conv node when `defer`.  bwd: the family's wrapper.  Returns (gx, dgamma, dbeta)."""
     import torch.distributed as dist
     Cc = gm.numel()
-    gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
+    gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=x.dtype, device=x.device)        # (the saved map's type: fp32, f16 in the `H` nodes)
     dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device)
     dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device)
     sums = torch.empty(2 * Cc + 1, dtype=torch.float64, device=x.device)       # [sum dz | sum dz * xhat | global row count]
@@ -1264,19 +1284,26 @@ def _syncbn_backward(x, g, gm, bt, ws, buf, eps, act, group, defer, bwd):
     return gx, dgamma, dbeta
 
 
+def _as_f16(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """An operand of an f16-map node as f16: taken as it is when its producer stored f16 (the case the bottleneck path arranges), else one conversion pass."""
+    return t if t is None or t.dtype == torch.float16 else t.to(torch.float16)
+
+
 def _bn_node_begin(x, gamma, beta, res):
-    """What the batch-statistics nodes' forwards start with: contiguous inputs, the C-channel views of x and of an output of x's width (a map held wider than
-    C keeps exactly-zero pad channels), detached affine parameters."""
+    """What the batch-statistics nodes' forwards start with: contiguous inputs, the C-channel views of x and of an output of x's width and element type (a map
+    held wider than C keeps exactly-zero pad channels), detached affine parameters."""
     x = x.contiguous()
     Cc = gamma.numel()
-    y = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
+    y = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=x.dtype, device=x.device)
     return x, y, Rows(x, 0, Cc), Rows(y, 0, Cc), (_r(res.contiguous()) if res is not None else None), gamma.detach().contiguous(), beta.detach().contiguous()
 
 
-def _bn_node_grad(gy, y):
-    """The incoming gradient of a batch-statistics node, finished and contiguous; y (the saved output of a residual form with ReLU): times [y > 0], which is
-    the residual's gradient AND the dz of a BatchNorm without activation."""
+def _bn_node_grad(gy, y, st=torch.float32):
+    """The incoming gradient of a batch-statistics node, finished and contiguous, in the node's map type `st`; y (the saved output of a residual form with
+    ReLU): times [y > 0], which is the residual's gradient AND the dz of a BatchNorm without activation."""
     g = resolve_pending(gy).contiguous()
+    if g.dtype != st:
+        g = g.to(st)
     return g if y is None else relu_mask(g, y)
 
 
@@ -1290,25 +1317,50 @@ class _SyncBatchNormApply(torch.autograd.Function):
     @staticmethod
     @_fwd32
     def forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act, h):
-        x, y, xr, yr, rr, gm, bt = _bn_node_begin(x, gamma, beta, res)
-        SYNC_TRACE.append(("fwd", ops.LAUNCHES[0] - h.launches_at_issue))
-        h.work.wait()
-        # statistics, running statistics (global count from buf[2C] on the device) and apply in one call
-        if rr is None:
-            h.fwd(2, xr, h.buf, gm, bt, yr, eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
-        else:
-            h.res_fwd(2, xr, h.buf, gm, bt, rr, yr, eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
-        ctx.save_for_backward(x, gm, bt, h.ws, h.buf, y if rr is not None and act == ACT_RELU else None)
-        ctx.geom = (eps, act if rr is None else ACT_NONE, h.group, h.defer, h.bwd)
-        return y
+        return _syncbn_apply_forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act, h)
 
     @staticmethod
     @_bwd
     def backward(ctx, gy):
-        x, gm, bt, ws, buf, y = ctx.saved_tensors
-        g = _bn_node_grad(gy, y)
-        gx, dgamma, dbeta = _syncbn_backward(x, g, gm, bt, ws, buf, *ctx.geom)
-        return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None, None
+        return _syncbn_apply_backward(ctx, gy)
+
+
+def _syncbn_apply_forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act, h):
+    """The forward of _SyncBatchNormApply and, on f16 maps, _SyncBatchNormApplyH (the wrappers pick the entry point by the maps' type)."""
+    x, y, xr, yr, rr, gm, bt = _bn_node_begin(x, gamma, beta, res)
+    SYNC_TRACE.append(("fwd", ops.LAUNCHES[0] - h.launches_at_issue))
+    h.work.wait()
+    # statistics, running statistics (global count from buf[2C] on the device) and apply in one call
+    if rr is None:
+        h.fwd(2, xr, h.buf, gm, bt, yr, eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
+    else:
+        h.res_fwd(2, xr, h.buf, gm, bt, rr, yr, eps, act, -1.0, momentum, rmean, rvar, ws=h.ws)
+    ctx.save_for_backward(x, gm, bt, h.ws, h.buf, y if rr is not None and act == ACT_RELU else None)
+    ctx.geom = (eps, act if rr is None else ACT_NONE, h.group, h.defer, h.bwd)
+    return y
+
+
+def _syncbn_apply_backward(ctx, gy):
+    x, gm, bt, ws, buf, y = ctx.saved_tensors
+    g = _bn_node_grad(gy, y, x.dtype)
+    gx, dgamma, dbeta = _syncbn_backward(x, g, gm, bt, ws, buf, *ctx.geom)
+    return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None, None
+
+
+class _SyncBatchNormApplyH(torch.autograd.Function):
+    """_SyncBatchNormApply on f16 MAPS (fd_batchnorm_train_sync_*_nhwc_h; the bottleneck path's opt-in f16_maps under torch.autocast(float16)): no cast on
+    entry -- x, the residual and the output are f16, the incoming gradient is taken as f16, dx and the residual's gradient are f16; gamma / beta and their
+    gradients, the running statistics and the all-reduced fp64 sums are the fp32 node's.  The deferred backward works as there."""
+
+    @staticmethod
+    @_fwd_keep
+    def forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act, h):
+        return _syncbn_apply_forward(ctx, _as_f16(x), gamma, beta, _as_f16(res), rmean, rvar, momentum, eps, act, h)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        return _syncbn_apply_backward(ctx, gy)
 
 
 def _bn_momentum(bn: nn.Module):
@@ -1381,8 +1433,8 @@ def _bn_wide_backward(ctx, gy):
     x, gm, bt, ws, y = ctx.saved_tensors
     eps, act = ctx.geom
     Cc = gm.numel()
-    g = _bn_node_grad(gy, y)
-    gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=torch.float32, device=x.device)
+    g = _bn_node_grad(gy, y, x.dtype)
+    gx = (torch.zeros if x.shape[1] != Cc else torch.empty)(x.shape, dtype=x.dtype, device=x.device)
     dgamma, dbeta = ops.batchnorm_train_bwd(Rows(x, 0, Cc), Rows(g, 0, Cc), gm, bt, Rows(gx, 0, Cc), eps, act, ws)
     return g, gx, dgamma, dbeta
 
@@ -1404,11 +1456,40 @@ class _BatchNormWideRows(torch.autograd.Function):
         return gx, dgamma, dbeta, None, None, None, None, None
 
 
-def batchnorm_train_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) -> torch.Tensor:
+class _BatchNormWideRowsH(torch.autograd.Function):
+    """_BatchNormWideRows on f16 MAPS (fd_batchnorm_train_fwd_nhwc_h / _bwd_nhwc_h; the bottleneck path's opt-in f16_maps under torch.autocast(float16)): no
+    cast on entry -- the forward reads the f16 x, stores an f16 y and saves the f16 x; the backward takes an f16 gradient and returns an f16 dx.  The
+    arithmetic is the fp32 node's on the upcast map, rounded once at the store; dgamma / dbeta and the running statistics stay fp32."""
+
+    @staticmethod
+    @_fwd_keep
+    def forward(ctx, x, gamma, beta, rmean, rvar, momentum, eps, act):
+        return _bn_wide_forward(ctx, _as_f16(x), gamma, beta, None, rmean, rvar, momentum, eps, act)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        _, gx, dgamma, dbeta = _bn_wide_backward(ctx, gy)
+        return gx, dgamma, dbeta, None, None, None, None, None
+
+
+def _f16_maps_on(f16_maps: bool) -> bool:
+    """The bottleneck path's opt-in f16_maps takes effect: torch.autocast(float16) on nodes that store f16 maps (amp_prec, AMP_F16_STORE).  THE place."""
+    return f16_maps and AMP_F16_STORE and amp_prec() == _lib.PREC_F16
+
+
+def _bn_f16_ok(bn: nn.Module, f16_maps: bool) -> bool:
+    """`bn` (in training mode, covered by the any-width kernels) runs on f16 maps: _f16_maps_on and a float momentum -- the cumulative moving average
+    (momentum=None) has no f16 form and keeps the fp32 node."""
+    return _f16_maps_on(f16_maps) and bn.momentum is not None
+
+
+def batchnorm_train_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE, f16: bool = False) -> torch.Tensor:
     """act(bn(x)) with batch statistics on rows at any width C % 4 == 0 up to 4096 (check with _bn_train_wide_ok); x is [rows, C] or a map held at
     round32(C) with zero pad channels, which the output keeps.  Running statistics and num_batches_tracked move like nn.BatchNorm2d's.  This is the
     UNSYNCHRONISED entry point: an nn.SyncBatchNorm spanning more than one rank raises here.  Its synchronised form is syncbn_begin(..., wide=True) /
-    syncbn_finish (fd_batchnorm_train_sync_*), which the callers pick through _bn_wide_rows before this function is reached."""
+    syncbn_finish (fd_batchnorm_train_sync_*), which the callers pick through _bn_wide_rows before this function is reached.  f16 (_bn_f16_ok): the f16-map
+    node, f16 in and out."""
     Cc = bn.num_features
     if _is_sync(bn):
         raise FdError(f"SyncBatchNorm({Cc}) over more than one rank: the batch-statistics kernels for widths outside C / 4 dividing 256, C <= 1024 "
@@ -1417,15 +1498,16 @@ def batchnorm_train_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NON
         raise FdError(f"batch-statistics BatchNorm({Cc}) on rows of shape {tuple(x.shape)}: at least 2 rows of at least {Cc} channels (a multiple of 4) expected")
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    return _BatchNormWideRows.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, act)
+    node = _BatchNormWideRowsH if f16 else _BatchNormWideRows
+    return node.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, act)
 
 
-def _bn_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE) -> torch.Tensor:
+def _bn_wide_rows(bn: nn.Module, x: torch.Tensor, act: int = ACT_NONE, f16: bool = False) -> torch.Tensor:
     """batchnorm_train_wide_rows, or for an nn.SyncBatchNorm spanning ranks its synchronised form in one shot (the MBConv chain is strictly sequential:
-    nothing independent exists to enqueue under the collective)."""
+    nothing independent exists to enqueue under the collective).  f16: on f16 maps."""
     if _is_sync(bn):
-        return syncbn_finish(syncbn_begin(bn, x, act, wide=True))
-    return batchnorm_train_wide_rows(bn, x, act)
+        return syncbn_finish(syncbn_begin(bn, x, act, wide=True, f16=f16))
+    return batchnorm_train_wide_rows(bn, x, act, f16)
 
 
 class _BatchNormResRows(torch.autograd.Function):
@@ -1446,10 +1528,27 @@ class _BatchNormResRows(torch.autograd.Function):
         return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None
 
 
-def batchnorm_train_res_rows(bn: nn.Module, x: torch.Tensor, res: torch.Tensor, act: int = ACT_RELU) -> torch.Tensor:
+class _BatchNormResRowsH(torch.autograd.Function):
+    """_BatchNormResRows on f16 MAPS (fd_batchnorm_train_res_fwd_nhwc_h, fd_batchnorm_train_bwd_nhwc_h): no cast on entry -- x, the residual and the output
+    are f16 and the f16 x and y are saved; the backward takes an f16 gradient, runs the mask pass on the f16 activation backward (fd_act_bwd_nhwc_h) and
+    returns an f16 dx and the f16 residual gradient; dgamma / dbeta stay fp32."""
+
+    @staticmethod
+    @_fwd_keep
+    def forward(ctx, x, gamma, beta, res, rmean, rvar, momentum, eps, act):
+        return _bn_wide_forward(ctx, _as_f16(x), gamma, beta, _as_f16(res), rmean, rvar, momentum, eps, act)
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, gy):
+        g, gx, dgamma, dbeta = _bn_wide_backward(ctx, gy)
+        return gx, dgamma, dbeta, (g if ctx.needs_input_grad[3] else None), None, None, None, None, None
+
+
+def batchnorm_train_res_rows(bn: nn.Module, x: torch.Tensor, res: torch.Tensor, act: int = ACT_RELU, f16: bool = False) -> torch.Tensor:
     """act(bn(x) + res) with batch statistics on [rows, C] maps, act NONE / ReLU, any width C % 4 == 0 up to 4096 (check with _bn_train_wide_ok): one-shot,
     and for an nn.SyncBatchNorm spanning ranks through its synchronised form.  Gradients for x, gamma, beta and res; running statistics and
-    num_batches_tracked move like nn.BatchNorm2d's."""
+    num_batches_tracked move like nn.BatchNorm2d's.  f16 (_bn_f16_ok): the f16-map nodes -- x, res and the output are f16."""
     Cc = getattr(bn, "num_features", 0)
     if act not in (ACT_NONE, ACT_RELU):
         raise FdError("batchnorm_train_res_rows differentiates ACT_NONE / ACT_RELU only (the backward takes its mask from the output)")
@@ -1460,12 +1559,13 @@ def batchnorm_train_res_rows(bn: nn.Module, x: torch.Tensor, res: torch.Tensor, 
         raise FdError(f"batchnorm_train_res_rows: BatchNorm({Cc}) on rows of shape {tuple(x.shape)} with a residual of shape {tuple(res.shape)}: "
                       f"two [rows, {Cc}] maps expected")
     if _is_sync(bn):
-        return syncbn_finish(syncbn_begin(bn, x, act, wide=True), res)
+        return syncbn_finish(syncbn_begin(bn, x, act, wide=True, f16=f16), res)
     if x.shape[0] < 2:
         raise FdError(f"batchnorm_train_res_rows: batch statistics need at least 2 rows (got {x.shape[0]})")
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
-    return _BatchNormResRows.apply(x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, act)
+    node = _BatchNormResRowsH if f16 else _BatchNormResRows
+    return node.apply(x, bn.weight, bn.bias, res, bn.running_mean, bn.running_var, _bn_momentum(bn), bn.eps, act)
 
 
 class _SampleScaleAddRows(torch.autograd.Function):
@@ -1560,17 +1660,19 @@ class NormHandle:
         self.y, self.sync = y, sync
 
 
-def conv_norm_begin(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, segs: Segs, act: int = ACT_NONE) -> Optional["NormHandle"]:
+def conv_norm_begin(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, segs: Segs, act: int = ACT_NONE,
+                    f16_maps: bool = False) -> Optional["NormHandle"]:
     """conv_norm_act_rows in two halves: everything up to and including the ISSUE of a SyncBatchNorm's statistics all-reduce.  The caller enqueues work
-    that does not need the normalised tensor, then calls conv_norm_finish.  (Any other layer kind is simply computed here.)"""
+    that does not need the normalised tensor, then calls conv_norm_finish.  (Any other layer kind is simply computed here.)  f16_maps: as there."""
     if bn is not None and not bn_is_frozen(bn) and _is_sync(bn):
         dense, dw, family = _dense_ok(m, x), _dw_ok(m, x), _bn_family(bn, x)
         if _STOCK or not (dense or dw) or family is None or (dw and m.bias is not None):
             return None
-        pre = conv_rows(m, x, segs, None, ACT_NONE) if dense else dw_rows(m, x, segs, None, ACT_NONE)
+        f16 = dense and _bn_f16_ok(bn, f16_maps)
+        pre = conv_rows(m, x, segs, None, ACT_NONE, out_f16=f16) if dense else dw_rows(m, x, segs, None, ACT_NONE)
         # the conv node just created is the only consumer of the BatchNorm's input gradient: its backward resolves the deferred second phase
-        return NormHandle(sync=syncbn_begin(bn, pre, act, defer_backward=True, wide=family == BN_WIDE))
-    y = conv_norm_act_rows(m, bn, x, segs, act)
+        return NormHandle(sync=syncbn_begin(bn, pre, act, defer_backward=True, wide=f16 or family == BN_WIDE, f16=f16))
+    y = conv_norm_act_rows(m, bn, x, segs, act, f16_maps)
     return None if y is None else NormHandle(y=y)
 
 
@@ -1580,15 +1682,21 @@ def conv_norm_finish(h: Optional["NormHandle"]) -> Optional[torch.Tensor]:
     return h.y if h.sync is None else syncbn_finish(h.sync)
 
 
-def conv_norm_act_rows(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, segs: Segs, act: int = ACT_NONE) -> Optional[torch.Tensor]:
+def conv_norm_act_rows(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, segs: Segs, act: int = ACT_NONE,
+                       f16_maps: bool = False) -> Optional[torch.Tensor]:
     """act(bn(m(x))) on single-level rows with every piece on the HIP kernels, whatever mode `bn` is in: a frozen BatchNorm folds
     into the conv epilogue (ReLU fused, SiLU one extra launch that keeps the pre-activation), a BatchNorm in training mode runs
-    on batch statistics (batchnorm_train_rows).  Returns None when a piece is not covered (the caller falls back)."""
+    on batch statistics (batchnorm_train_rows).  Returns None when a piece is not covered (the caller falls back).
+    f16_maps (the bottleneck path's opt-in; dense convs, act NONE / ReLU): under torch.autocast(float16) the output map is f16 -- a frozen BatchNorm's conv
+    stores f16, a BatchNorm in training mode with a float momentum runs on the any-width f16-map kernels at EVERY width, behind a raw conv that stores f16."""
     dense, dw = _dense_ok(m, x), _dw_ok(m, x)
     if _STOCK or not (dense or dw):
         return None
     conv = conv_rows if dense else (lambda mm, xx, sg, b=None, a=ACT_NONE: dw_rows(mm, xx, sg, b, a))
+    f16_maps = _f16_maps_on(f16_maps) and dense and act in (ACT_NONE, ACT_RELU)
     if bn is None or bn_is_frozen(bn):
+        if f16_maps:
+            return conv_rows(m, x, segs, bn, act, out_f16=True)
         if act in (ACT_NONE, ACT_RELU):
             return conv(m, x, segs, bn, act)
         return act_rows(conv(m, x, segs, bn, ACT_NONE), act)
@@ -1597,6 +1705,8 @@ def conv_norm_act_rows(m: nn.Conv2d, bn: Optional[nn.Module], x: torch.Tensor, s
     family = _bn_family(bn, x)
     if family is None:
         return None
+    if _bn_f16_ok(bn, f16_maps):
+        return _bn_wide_rows(bn, conv_rows(m, x, segs, None, ACT_NONE, out_f16=True), act, f16=True)
     return (batchnorm_train_rows if family == BN_NARROW else _bn_wide_rows)(bn, conv(m, x, segs, None, ACT_NONE), act)
 
 

@@ -6,8 +6,12 @@
                composed   ops.batchnorm_train_fwd with ACT_NONE, then ops.sample_scale_add with s = 1, then ops.act with ReLU
              with the bytes each moves over a [rows, C] fp32 map (fused: x twice, res, y = 4 passes; composed: 6 passes) and the fraction of the HBM peak
              (8.0 TB/s spec) its time corresponds to
+  launches_f16   the f16-map forms against their fp32 twins at the same four shapes, again ALTERNATING in every repetition: the residual forward
+             (fd_batchnorm_train_res_fwd_nhwc_h vs fd_batchnorm_train_res_fwd_nhwc: 4 map passes) and the backward (fd_batchnorm_train_bwd_nhwc_h vs
+             fd_batchnorm_train_bwd_nhwc: x and dy twice, dx = 5 map passes), bytes at 2 resp. 4 per element, the HBM fraction of each and the ratio
   step       the whole HISFCOS-R50 training step (forward, targets, loss, backward, SGD) at 16 x 512 x 512, fp32 and under autocast(float16) + GradScaler:
                switch_on   bn_freeze=False, enable_stem_training().enable_trunk_batch_stats(): the trunk's BatchNorms on the HIP batch-statistics nodes
+               switch_on_f16   the same with enable_trunk_batch_stats(f16_maps=True): f16 maps on those nodes (autocast only)
                switch_off  bn_freeze=False as it is without the switch: convs on HIP, stock nn.BatchNorm2d behind them, stock stem (strict mode off)
                frozen      the default model: frozen BatchNorm folded into the conv epilogues
 
@@ -65,9 +69,9 @@ def _time_alternating(fns, reps, n=50):
     return runs
 
 
-def _row(name, form, C, rows, runs, passes):
+def _row(name, form, C, rows, runs, passes, elt=4):
     us = statistics.median(runs)
-    nbytes = passes * rows * C * 4
+    nbytes = passes * rows * C * elt
     return {"layer": name, "form": form, "C": C, "rows": rows, "us": round(us, 2), "us_min": round(min(runs), 2), "us_max": round(max(runs), 2),
             "map_passes": passes, "bytes": nbytes, "bound_us_at_hbm_peak": round(nbytes / HBM_PEAK * 1e6, 2),
             "hbm_peak_fraction": round(nbytes / (us * 1e-6) / HBM_PEAK, 4)}
@@ -105,6 +109,39 @@ def time_launches(reps):
     return res
 
 
+def time_launches_f16(reps):
+    """The `_h` residual forward and backward against the fp32 launches, alternating."""
+    res = []
+    for name, C, H in SHAPES:
+        rows = B * H * H
+        gm, bt = torch.rand(C, device=DEV) + 0.5, torch.randn(C, device=DEV)
+        rm, rv = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
+        maps = {}
+        for half in (False, True):
+            dt = torch.float16 if half else torch.float32
+            g = torch.Generator(device=DEV).manual_seed(C)
+            x, r, dy = (torch.randn(rows, C, device=DEV, generator=g).to(dt) for _ in range(3))
+            maps[half] = tuple(ops.Rows(v) for v in (x, r, dy, torch.empty_like(x), torch.empty_like(x)))
+        ws = {half: (ops.batchnorm_train_workspace(rows, C, DEV), ops.batchnorm_train_workspace(rows, C, DEV)) for half in (False, True)}
+
+        def fwd(half):
+            xr, rr, _, yr, _ = maps[half]
+            return lambda: ops.batchnorm_train_res_fwd(xr, gm, bt, rr, yr, 1e-5, ops.ACT_RELU, 0.1, rm, rv, ws[half][0])
+
+        def bwd(half):
+            xr, _, gr, _, dxr = maps[half]
+            return lambda: ops.batchnorm_train_bwd(xr, gr, gm, bt, dxr, 1e-5, ops.ACT_NONE, ws[half][0], ws[half][1])
+
+        for form, make, passes in (("res_fwd", fwd, 4), ("bwd", bwd, 5)):
+            fns = (make(False), make(True))
+            r32, r16 = _time_alternating(fns, reps)
+            a, b = _row(name, form + " fp32", C, rows, r32, passes, 4), _row(name, form + " f16", C, rows, r16, passes, 2)
+            b["fp32_over_f16"] = round(a["us"] / b["us"], 3)
+            b["not_slower_than_fp32"] = b["us"] <= a["us"]
+            res += [a, b]
+    return res
+
+
 def batch():
     g = torch.Generator(device=DEV).manual_seed(7)
     x = torch.randn(B, 3, S, S, device=DEV, generator=g)
@@ -118,8 +155,8 @@ def batch():
 def time_step(form, amp, reps, steps=3):
     torch.manual_seed(0)
     model = HalfInvertedStageFCOS([512, 1024, 2048], 20, 256, bn_freeze=form == "frozen")
-    if form == "switch_on":
-        model.enable_stem_training().enable_trunk_batch_stats()
+    if form in ("switch_on", "switch_on_f16"):
+        model.enable_stem_training().enable_trunk_batch_stats(f16_maps=form == "switch_on_f16")
     model.to(DEV).train()
     x, gt, labels = batch()
     gen = FCOSGenTargets([8, 16, 32, 64, 128], [[-1, 32], [32, 96], [96, 192], [192, 384], [384, 9999999]])
@@ -163,10 +200,13 @@ def main():
     res = {"tool": "time_resnet_bn_train", "device": torch.cuda.get_device_name(0), "model": "HISFCOS-R50", "batch": B, "input": S, "reps": args.reps,
            "clocks_before": clocks()}
     res["launches"] = time_launches(args.reps)
+    res["launches_f16"] = time_launches_f16(args.reps)
     if not args.launches_only:
         train_ops.STRICT = False        # the switch_off form runs stock BatchNorm behind the HIP convs: a counted fallback, an error under strict mode
-        for form in ("switch_on", "switch_off", "frozen"):
+        for form in ("switch_on", "switch_on_f16", "switch_off", "frozen"):
             for amp in (False, True):
+                if form == "switch_on_f16" and not amp:
+                    continue                # (without autocast the flag changes nothing: tests/test_resnet_bn_f16_gpu.py holds that bit for bit)
                 res[f"step_{form}_{'amp' if amp else 'fp32'}"] = time_step(form, amp, args.reps)
                 torch.cuda.empty_cache()
     res["clocks_after"] = clocks()
