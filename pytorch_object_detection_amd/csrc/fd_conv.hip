@@ -24,7 +24,9 @@
 // folded into its epilogue (HISFcos.py:155-165, Fcos.py:77-91) -- the upsample-add pass over the finer map disappears.
 template <int WGM, int WGN, int TM, int TN, bool STEM, bool SB, int TAG, bool SPLIT, bool GATE = false, bool GNS = false, bool H1 = false, bool GEMM = false, bool DUAL = false,
           bool RUP = false>
-__global__ __launch_bounds__(WGM * WGN * 64, (TM * TN == 4) ? ((SPLIT || WGM * WGN == 8) ? 2 : (SB ? 3 : 1)) : 1)
+// (the two-sub-tile fp32 kernels are held at the four workgroups per CU they have had: 128 registers, which the straight-line epilogue copies otherwise exceed by four;
+// the row-statistics kernels and the gated 128 x 64 tile never fitted them and would spill)
+__global__ __launch_bounds__(WGM * WGN * 64, (TM * TN == 4) ? ((SPLIT || WGM * WGN == 8) ? 2 : (SB ? 3 : 1)) : ((TM * TN == 2 && !SPLIT && !GNS && !(GATE && TM == 2)) ? 4 : 1))
 void conv_igemm_kernel(ConvArgs a) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
     constexpr int NT = WGM * WGN * 64;         // threads: 4 waves (256) or 8 waves (512: the 256x128 tile)
@@ -403,6 +405,7 @@ static int launch_conv(const ConvArgs& a, hipStream_t stream) {
     ConvArgs b = a;
     b.mtiles = (a.M + BM - 1) / BM;
     b.ntiles = (a.Cout + BN - 1) / BN;
+    fd_conv_epi_extents(b);
     auto kern = conv_igemm_kernel<WGM, WGN, TM, TN, STEM, SB, TAG, SPLIT, GATE, GNS, H1, GEMM, DUAL, RUP>;
     static std::atomic<unsigned> attr_mask{0};       // per kernel instantiation, one bit per device
     fd_set_max_lds_once(attr_mask, reinterpret_cast<const void*>(kern), lds);
@@ -578,6 +581,7 @@ extern "C" int32_t fd_conv2d_nhwc_f32(const fd_conv_params* p, fd_stream_t strea
 
     ConvArgs a;
     a.x16 = a.y16 = a.res16 = 0;
+    a.y_bytes = a.res_bytes = 0;     // (set per launch: fd_conv_epi_extents)
     a.x = p->x; a.w = p->w; a.scale = p->scale; a.shift = p->shift; a.res = p->res; a.y = p->y;
     a.x_cs = p->x_cs; a.x_co = p->x_co; a.res_cs = p->res_cs; a.res_co = p->res_co; a.y_cs = p->y_cs; a.y_co = p->y_co;
     a.Cin = p->Cin; a.Cout = p->Cout; a.KW = p->KW; a.stride = p->stride; a.pad = p->pad; a.dil = p->dil;

@@ -1,6 +1,7 @@
 // fd_conv_common.h -- what the implicit-GEMM conv kernels share: argument block, LDS swizzles, the fused epilogue.
 #pragma once
 #include "fd_common.h"
+#include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -41,7 +42,25 @@ struct ConvArgs {
     // FD_PREC_F16 (H1 kernels) only -- activations stored as f16 in HBM (fd_conv_params.io_f16): x / y / res hold _Float16 elements; views stay in ELEMENTS
     int x16, y16, res16;
     int wide8;     // FD_TILE_F16K64: the f16 output / residual views allow 16-byte (eight-channel) accesses
+    // fd_conv_epilogue.inc: extents of the output VIEW (of one split-K slab) / the residual view, ((rows - 1) * cs + co + Cout_epi) * 4 bytes, for the epilogue's raw
+    // buffer descriptors; 0 = 64-bit pointers (fd_conv_epi_extents below)
+    unsigned y_bytes, res_bytes;
 };
+
+// The epilogue of conv_igemm_kernel / conv3x3_patch_kernel addresses fp32 views with rows at a fixed stride through raw buffer descriptors when every byte offset it
+// forms fits 32 bits: the views inside the 3 GiB rule of the operand buffers, and the rows a tile addresses past M (up to 256, dropped / read as zero by the range
+// check) not wrapping -- also from the out-of-range offset 0xC0000000.  Otherwise (and for scatter launches and f16 maps) both fields are 0: today's pointer code.
+// Call it on the argument block that is launched (M, Cout_epi, the views and res_up final).
+static inline void fd_conv_epi_extents(ConvArgs& b) {
+    b.y_bytes = b.res_bytes = 0;
+    if (!b.vec_epi || b.sc_on || b.y16 || b.res16) return;
+    const bool res = b.res && !b.res_up;      // (the half-resolution addend keeps its pointer loads)
+    const long yb = ((long)(b.M - 1) * b.y_cs + b.y_co + b.Cout_epi) * 4;
+    const long rb = res ? ((long)(b.M - 1) * b.res_cs + b.res_co + b.Cout_epi) * 4 : 0;
+    const long over = 256L * 4 * (res && b.res_cs > b.y_cs ? b.res_cs : b.y_cs);
+    if (yb >= 0xC0000000L || rb >= 0xC0000000L || over >= (1L << 30)) return;
+    b.y_bytes = (unsigned)yb; b.res_bytes = (unsigned)rb;
+}
 
 // four fp32 values <-> four consecutive f16 (8 bytes), round to nearest even -- the storage form of AMP activations
 __device__ __forceinline__ float4 fd_ld_h4(const void* p) {

@@ -7,34 +7,7 @@
 //   stored output, fd_gn_rowstats -- compiled into dedicated instantiations only: inside the four-sub-tile kernels it pushes the
 //   accumulators into scratch).
 #ifndef FD_EPI_RES_PREFETCHED
-    // residual tile prefetch (vector epilogue): all 16-byte loads of the wave's tile issued back to back right after the K loop (they fly while the first sub-tile is staged)
-    float4 rres[SPLIT ? 1 : TM][SPLIT ? 1 : TN][4];
-    if (!SPLIT && a.res && a.vec_epi) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const int m = m0 + (wm * TM + i) * 32 + (lane >> 3) + 8 * p;
-                    const int nn = n0 + (wn * TN + j) * 32 + (lane & 7) * 4;
-                    const size_t ro_ = (size_t)(RUP ? res_row_up(a, m) : out_row(a, m)) * a.res_cs + a.res_co + nn;
-                    if (H1 && a.res16)
-                        rres[i][j][p] = (m < a.M && nn < a.Cout_epi) ? fd_ld_h4(reinterpret_cast<const _Float16*>(a.res) + ro_) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    else
-                    rres[i][j][p] = (m < a.M && nn < a.Cout_epi) ? *reinterpret_cast<const float4*>(a.res + ro_) : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-    }
-    // per-channel scale / shift of this lane's output columns, requested with the residual (their L2 latency used to sit at the head of every
-    // sub-tile column of the epilogue)
-    float esc[TN], esf[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int n = n0 + (wn * TN + j) * 32 + (lane & 31);
-        const bool n_ok = n < a.Cout_epi;
-        esc[j] = (a.scale && n_ok) ? a.scale[n] : 1.0f;
-        esf[j] = (a.shift && n_ok) ? a.shift[n] : 0.0f;
-    }
+#include "fd_conv_res_prefetch.inc"     // (kernels without a peeled last K-tile: the same prefetch, at the head of the epilogue)
 #endif
     // ---- epilogue: acc reg e of lane l is C[row = (e&3) + 8*(e>>2) + 4*(l>>5)][col = l&31] ----
     // Vector path: each 32x32 sub-tile is transposed through a per-wave LDS stage so that a lane owns 4 consecutive
@@ -50,9 +23,84 @@
     // The WHOLE wave tile on the fast path (full sub-tiles inside the output, rows at a fixed stride, no activation or ReLU / SiLU on every channel): a loop of its
     // own -- the four sub-tiles' ~100 instructions each then lie next to each other instead of ~7 000 instructions (the general and the scalar path) apart
     // (DESIGN 4.1n: instruction fetch; strided 3x3 layers -9 ... -10 %, the 1x1 layers -2 ... -4 %).
-    const bool wave_fast = !SPLIT && a.vec_epi && !a.sc_on && m0 + (wm * TM + TM) * 32 <= a.M && n0 + (wn * TN + TN) * 32 <= a.Cout_epi &&
+    // epi_buf (uniform; host: fd_conv_epi_extents): the output view fits 32-bit byte offsets -- the fast loop stores through a raw buffer descriptor over the view
+    // (of this split-K slice).  Rows past M then lie behind the descriptor's extent and are dropped by the range check, so the ragged last M tile is on the fast
+    // path too; the column condition stays (channels past Cout_epi lie inside a view's row).  GNS keeps the row condition: its statistics store wants the predicate.
+    const bool epi_buf = !SPLIT && a.y_bytes != 0;
+    const bool wave_fast = !SPLIT && a.vec_epi && !a.sc_on && ((!GNS && epi_buf) || m0 + (wm * TM + TM) * 32 <= a.M) && n0 + (wn * TN + TN) * 32 <= a.Cout_epi &&
                            (a.act == FD_ACT_NONE || (a.act_c0 <= n0 + wn * TN * 32 && (a.act == FD_ACT_RELU || a.act == FD_ACT_SILU)));
-    if (wave_fast) {
+    if (wave_fast && epi_buf) {
+        // ONE uniform decision per wave, outside the j / i / p loops: {no residual, add, mask} x {none, ReLU, SiLU}, each a straight-line copy of the store loop
+        // (between two stores: the residual, the activation, one 32-bit add, the store -- no branch, no 64-bit address arithmetic).  A launch runs one copy, so the executed
+        // footprint shrinks (DESIGN 4.1n) although the kernel grows.  The four ds_read_b128 of a sub-tile are issued together and waited for once.
+        const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)ybase, (short)0, (int)a.y_bytes, 0x00020000);
+        const int c4 = (lane & 7) * 4;
+        const int mw = m0 + wm * TM * 32 + (lane >> 3), nw = n0 + wn * TN * 32 + c4;          // this lane's first row / channel of the wave tile
+        const unsigned y_off = ((unsigned)mw * (unsigned)a.y_cs + (unsigned)(a.y_co + nw)) * 4u;
+        const int ystep8 = a.y_cs * 32;                                                       // bytes between rows r and r + 8
+        const float* sp = stage + (lane >> 3) * 32 + c4;
+        auto store_wave_tile = [&](auto res_c, auto act_c) {
+            constexpr int RES = (RUP && decltype(res_c)::value == 2) ? 1 : decltype(res_c)::value;   // 0 none, 1 addend, 2 ReLU mask (the upsampled map of RUP is always an addend)
+            constexpr int ACT = decltype(act_c)::value;
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const float sc = esc[j], sf = esf[j];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)
+                        stage[((e & 3) + 8 * (e >> 2) + 4 * lh) * 32 + l31] = acc[i][j][e] * sc + sf;
+                    wave_lds_sync();
+                    float4 vv[4];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) vv[p] = *reinterpret_cast<const float4*>(sp + p * 256);
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        float4 v = vv[p];
+                        if constexpr (RES != 0 && !RUP) {
+                            const float4 r = rres[SPLIT ? 0 : i][SPLIT ? 0 : j][p];
+                            if constexpr (RES == 2) {
+                                v.x = r.x > 0.f ? v.x : 0.f; v.y = r.y > 0.f ? v.y : 0.f;
+                                v.z = r.z > 0.f ? v.z : 0.f; v.w = r.w > 0.f ? v.w : 0.f;
+                            } else {
+                                v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
+                            }
+                        }
+                        if constexpr (ACT == FD_ACT_RELU) {
+                            v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                        } else if constexpr (ACT == FD_ACT_SILU) {
+                            v.x = fd_act(v.x, FD_ACT_SILU, 0.f); v.y = fd_act(v.y, FD_ACT_SILU, 0.f);
+                            v.z = fd_act(v.z, FD_ACT_SILU, 0.f); v.w = fd_act(v.w, FD_ACT_SILU, 0.f);
+                        }
+                        if constexpr (RES != 0 && RUP) {          // the upsampled map joins AFTER the activation (HISFcos.py:155-165: relu(gn(tf(c))) + Up_sample(...))
+                            const float4 r = rres[SPLIT ? 0 : i][SPLIT ? 0 : j][p];
+                            v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
+                        }
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(f32x4, v), yrsrc, (int)(y_off + (unsigned)((4 * i + p) * ystep8) + 128u * j), 0, 0);
+                        // (row step: one add of a scalar; column block: the immediate offset.  NOT the instruction's scalar offset: the compiler's hazard table
+                        // exempts a 16-byte buffer store with an SGPR offset from "VALU write of the store's data registers", and on gfx950 such a store
+                        // followed two instructions later by the next sub-tile's staging multiply-add in one of its data registers stored the NEW value --
+                        // seen in the copies without a residual, where nothing else stands between.  With the immediate 0 the compiler inserts the wait states.)
+                        if constexpr (GNS) fd_gn_rowstats(a.gn_stats, a.gn_G, a.gn_cg, v, (size_t)(mw + 32 * i + 8 * p), nw + 32 * j, lane, true);
+                    }
+                    wave_lds_sync();
+                }
+            }
+        };
+        using std::integral_constant;
+        switch ((a.res ? (a.res_mask ? 2 : 1) : 0) * 3 + a.act) {      // (wave_fast: a.act is NONE = 0, RELU = 1 or SILU = 2)
+            case 0: store_wave_tile(integral_constant<int, 0>{}, integral_constant<int, FD_ACT_NONE>{}); break;
+            case 1: store_wave_tile(integral_constant<int, 0>{}, integral_constant<int, FD_ACT_RELU>{}); break;
+            case 2: store_wave_tile(integral_constant<int, 0>{}, integral_constant<int, FD_ACT_SILU>{}); break;
+            case 3: store_wave_tile(integral_constant<int, 1>{}, integral_constant<int, FD_ACT_NONE>{}); break;
+            case 4: store_wave_tile(integral_constant<int, 1>{}, integral_constant<int, FD_ACT_RELU>{}); break;
+            case 5: store_wave_tile(integral_constant<int, 1>{}, integral_constant<int, FD_ACT_SILU>{}); break;
+            case 6: store_wave_tile(integral_constant<int, 2>{}, integral_constant<int, FD_ACT_NONE>{}); break;
+            case 7: store_wave_tile(integral_constant<int, 2>{}, integral_constant<int, FD_ACT_RELU>{}); break;
+            default: store_wave_tile(integral_constant<int, 2>{}, integral_constant<int, FD_ACT_SILU>{}); break;
+        }
+    } else if (wave_fast) {
+        // the same wave tile with 64-bit pointers and the variants behind uniform branches: views too large for 32-bit byte offsets, and the last-but-ragged tiles of GNS
         const int act_u = a.act;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {

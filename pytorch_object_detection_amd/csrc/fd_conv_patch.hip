@@ -251,6 +251,7 @@ static int launch_patch(const ConvArgs& a, hipStream_t stream) {
     ConvArgs b = a;
     b.mtiles = (a.M + FD_PATCH_BM - 1) / FD_PATCH_BM;
     b.ntiles = (a.Cout + 127) / 128;
+    fd_conv_epi_extents(b);
     auto kern = conv3x3_patch_kernel<TAG, SPLIT>;
     static std::atomic<unsigned> attr_mask{0};
     fd_set_max_lds_once(attr_mask, reinterpret_cast<const void*>(kern), lds);
