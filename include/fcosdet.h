@@ -1303,6 +1303,108 @@ typedef struct fd_avg_copy_chunk {
  * with nbytes > 0. */
 int32_t fd_avg_copy_bytes(const fd_avg_copy_chunk* chunk, const fd_avg_state* state, fd_stream_t stream);
 
+/* Baseline JPEG decoding (the reference's Image.open(path).convert('RGB'), dataset/voc.py:69, dataset/pascalvoc.py:28,
+ * data/dataload.py:35).  The serial half stays on the host: fd_jpeg_parse reads the markers up to SOS,
+ * fd_jpeg_entropy_decode undoes the Huffman coding into dense quantised coefficients.  The data-parallel half is two launches
+ * per batch: fd_jpeg_idct_u8 (dequantise + libjpeg's jpeg_idct_islow, one job per image component) and fd_jpeg_color_u8
+ * (libjpeg-turbo's fancy chroma upsampling + YCbCr -> RGB, one job per image).  Integer arithmetic throughout; the result is
+ * bit for bit what Pillow returns.
+ *
+ * The two host functions touch no GPU, keep no state between calls, never set the fd_last_error text and may run on any number
+ * of threads at once: what went wrong is their return value (FD_JPEG_E_*), what is merely not handled is info->reason. */
+#define FD_JPEG_MAX_COMP 3
+
+/* info->reason when info->supported == 0: a well-formed stream this decoder does not take */
+#define FD_JPEG_R_NONE 0
+#define FD_JPEG_R_PROGRESSIVE 1 /* SOF2 (and every other frame type but SOF0 / SOF1 / the arithmetic ones) */
+#define FD_JPEG_R_ARITHMETIC 2  /* SOF9 .. SOF15 */
+#define FD_JPEG_R_PRECISION 3   /* 12-bit samples, or 16-bit quantisation tables */
+#define FD_JPEG_R_COMPONENTS 4  /* a component count other than 1 or 3 (CMYK / YCCK) */
+#define FD_JPEG_R_RGB 5         /* Adobe transform 0, or component ids 'R','G','B': no YCbCr -> RGB step applies */
+#define FD_JPEG_R_SAMPLING 6    /* luma not 1x1 / 2x1 / 2x2, or chroma not 1x1 */
+#define FD_JPEG_R_MULTISCAN 7   /* the first scan does not hold every component of the frame */
+#define FD_JPEG_R_DNL 8         /* height 0 in the frame header: the height follows in a DNL segment */
+
+/* return codes of the two host functions: FD_OK, or what is wrong with the stream / the call */
+#define FD_JPEG_E_TRUNCATED (-16)  /* the stream ends (or a marker interrupts the scan) before the data does */
+#define FD_JPEG_E_MARKER (-17)     /* no SOI, a malformed segment, SOS before SOF, a missing or wrong RSTn */
+#define FD_JPEG_E_HUFFMAN (-18)    /* bits that match no code of the table, or an impossible table */
+#define FD_JPEG_E_COEF_INDEX (-19) /* a run that carries the coefficient index past 63 */
+#define FD_JPEG_E_TABLE (-20)      /* the scan names a Huffman or quantisation table nothing defines */
+#define FD_JPEG_E_BUFFER (-21)     /* coef_bytes below info->coef_bytes, or a null argument */
+#define FD_JPEG_E_UNSUPPORTED (-22) /* fd_jpeg_entropy_decode on an info with supported == 0 */
+
+typedef struct fd_jpeg_info {
+    int32_t width, height;
+    int32_t ncomp;            /* 1 or 3 when supported */
+    int32_t supported;        /* 1: fd_jpeg_entropy_decode and the two launches take this stream */
+    int32_t reason;           /* FD_JPEG_R_* */
+    int32_t restart_interval; /* MCUs between RSTn markers, 0: none */
+    int32_t h_samp[FD_JPEG_MAX_COMP], v_samp[FD_JPEG_MAX_COMP]; /* a single component counts as 1 x 1, as its scan does */
+    int32_t h_max, v_max;
+    int32_t mcus_x, mcus_y;
+    int32_t bw[FD_JPEG_MAX_COMP], bh[FD_JPEG_MAX_COMP]; /* 8 x 8 blocks per row / column, padded to whole MCUs */
+    int32_t dc_tab[FD_JPEG_MAX_COMP], ac_tab[FD_JPEG_MAX_COMP]; /* Huffman table selectors of the scan */
+    int32_t reserved0[2]; /* up to a multiple of 8 bytes */
+    int64_t scan_offset;  /* first entropy-coded byte */
+    int64_t coef_bytes;  /* sum over components of bh * bw * 64 * sizeof(int16_t) */
+    uint16_t qt[FD_JPEG_MAX_COMP][64]; /* the quantisation table OF EACH COMPONENT, natural (row-major) order */
+    uint8_t huff_defined[2][4];        /* [0]: DC, [1]: AC */
+    uint8_t huff_bits[2][4][16];       /* codes of length 1 .. 16 */
+    uint8_t huff_vals[2][4][256];
+} fd_jpeg_info;
+
+/* Reads data[0 .. n) up to and including the SOS header.  FD_OK with info->supported == 0 and a reason for a well-formed
+ * stream of another kind; FD_JPEG_E_* for a stream that is not well formed that far.  Never reads outside data[0 .. n). */
+int32_t fd_jpeg_parse(const uint8_t* data, int64_t n, fd_jpeg_info* info);
+
+/* Huffman-decodes the scan of a parsed, supported stream into coefs: component c at element offset
+ * sum over c' < c of bh[c'] * bw[c'] * 64, as [bh][bw][64] int16 in natural order, zero where the stream codes nothing.
+ * Byte stuffing and RSTn (byte alignment, DC predictors back to 0) are undone; the DC predictor is 32 bits wide and the stored
+ * value its low 16 bits, libjpeg's JCOEF.  Writes coefs[0 .. info->coef_bytes / 2) and nothing else; on an error the contents
+ * are unspecified.  Never reads outside data[0 .. n). */
+int32_t fd_jpeg_entropy_decode(const uint8_t* data, int64_t n, const fd_jpeg_info* info, int16_t* coefs, int64_t coef_bytes);
+
+typedef struct fd_jpeg_idct_job {
+    int64_t coef_off;  /* int16 elements into coefs: the component's [bh][bw][64] */
+    int64_t plane_off; /* bytes into planes, a multiple of 8: the component's uint8 [8 * bh][8 * bw] */
+    int32_t bw, bh;
+    int32_t qt;        /* which 64-entry table of qtabs */
+    int32_t reserved0;
+} fd_jpeg_idct_job;
+
+/* ONE launch for every component of every image of a batch.  The job table exists twice with the same contents: jobs_host
+ * is validated here before anything is enqueued, jobs_dev (device memory) is what the kernel reads.  coefs: device int16
+ * [coef_elems]; qtabs: device uint16 [n_qtabs][64]; planes: device uint8 [planes_bytes].
+ * blockIdx.y = job; eight lanes per 8 x 8 block (one column, then one row each, transposed through LDS), 32 blocks per
+ * workgroup.  out = range_limit(DESCALE(row pass(DESCALE(column pass(coef * q), 11)), 18)), 64-bit intermediates.
+ * FD_E_INVAL: a null pointer, n_jobs outside [1, 65535], a job whose grid is empty or above 8192 blocks a side, whose
+ * coefficients, table or plane lie outside the three buffers, or whose plane_off is not a multiple of 8. */
+int32_t fd_jpeg_idct_u8(const fd_jpeg_idct_job* jobs_host, const fd_jpeg_idct_job* jobs_dev, int32_t n_jobs, const int16_t* coefs,
+                        int64_t coef_elems, const uint16_t* qtabs, int32_t n_qtabs, uint8_t* planes, int64_t planes_bytes,
+                        fd_stream_t stream);
+
+typedef struct fd_jpeg_color_job {
+    uint8_t* out;                        /* device uint8 [height][width][3], 4-byte aligned */
+    int64_t plane_off[FD_JPEG_MAX_COMP]; /* bytes into planes */
+    int32_t stride[FD_JPEG_MAX_COMP];    /* bytes per plane row (8 * bw) */
+    int32_t rows[FD_JPEG_MAX_COMP];      /* plane rows (8 * bh) */
+    int32_t width, height;
+    int32_t ncomp;          /* 1: the plane three times; 3: Y, Cb, Cr */
+    int32_t h_samp, v_samp; /* of the luma: 1 x 1, 2 x 1 or 2 x 2; the chroma is 1 x 1 */
+    int32_t reserved0;
+} fd_jpeg_color_job;
+
+/* ONE launch for every image of a batch, blockIdx.z = job; a lane produces four consecutive pixels of the [h * w] pixel
+ * sequence, 12 contiguous bytes.  Chroma of true size dw x dh = ceil(w / h_samp) x ceil(h / v_samp): libjpeg-turbo's fancy
+ * (triangle) upsampling for dw > 2, plain replication for dw <= 2; then libjpeg's 16.16 YCbCr -> RGB and a clamp to
+ * [0, 255].  Only bytes of [h][w][3] are written; a plane sample is read only after its row and column passed
+ * (unsigned) < dh / dw.  jobs_host / jobs_dev as above.
+ * FD_E_INVAL: a null pointer, n_jobs outside [1, 65535], a job with a null or unaligned out, sides outside [1, 65535],
+ * ncomp not 1 or 3, sampling outside the three, a plane smaller than dw x dh or outside planes[0 .. planes_bytes). */
+int32_t fd_jpeg_color_u8(const fd_jpeg_color_job* jobs_host, const fd_jpeg_color_job* jobs_dev, int32_t n_jobs, const uint8_t* planes,
+                         int64_t planes_bytes, fd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -181,6 +181,40 @@ class AvgCopyChunk(C.Structure):
     _fields_ = [("n", C.c_int32), ("reserved0", C.c_int32), ("dst", C.c_void_p * OPTIM_MAX_TENSORS), ("src", C.c_void_p * OPTIM_MAX_TENSORS),
                 ("nbytes", C.c_int64 * OPTIM_MAX_TENSORS)]
 
+
+JPEG_MAX_COMP = 3                                                         # include/fcosdet.h FD_JPEG_*
+JPEG_R_NONE, JPEG_R_PROGRESSIVE, JPEG_R_ARITHMETIC, JPEG_R_PRECISION, JPEG_R_COMPONENTS, JPEG_R_RGB, JPEG_R_SAMPLING, JPEG_R_MULTISCAN, JPEG_R_DNL = range(9)
+JPEG_REASONS = {JPEG_R_NONE: "supported", JPEG_R_PROGRESSIVE: "progressive (or another non-baseline) frame", JPEG_R_ARITHMETIC: "arithmetic coding",
+                JPEG_R_PRECISION: "12-bit samples or 16-bit quantisation tables", JPEG_R_COMPONENTS: "a component count other than 1 or 3",
+                JPEG_R_RGB: "an RGB stream (Adobe transform 0 or 'R','G','B' component ids)", JPEG_R_SAMPLING: "a sampling other than 4:4:4, 4:2:2, 4:2:0",
+                JPEG_R_MULTISCAN: "several scans", JPEG_R_DNL: "height 0 (DNL)"}
+JPEG_E_TRUNCATED, JPEG_E_MARKER, JPEG_E_HUFFMAN, JPEG_E_COEF_INDEX, JPEG_E_TABLE, JPEG_E_BUFFER, JPEG_E_UNSUPPORTED = -16, -17, -18, -19, -20, -21, -22
+JPEG_ERRORS = {JPEG_E_TRUNCATED: "truncated stream", JPEG_E_MARKER: "malformed marker segment or restart marker", JPEG_E_HUFFMAN: "bits that match no Huffman code",
+               JPEG_E_COEF_INDEX: "coefficient index past 63", JPEG_E_TABLE: "the scan names a table nothing defines", JPEG_E_BUFFER: "coefficient buffer too small",
+               JPEG_E_UNSUPPORTED: "unsupported stream"}
+
+
+class JpegInfo(C.Structure):
+    """fd_jpeg_info: what fd_jpeg_parse reads from the headers of one stream."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("supported", C.c_int32), ("reason", C.c_int32),
+                ("restart_interval", C.c_int32), ("h_samp", C.c_int32 * JPEG_MAX_COMP), ("v_samp", C.c_int32 * JPEG_MAX_COMP),
+                ("h_max", C.c_int32), ("v_max", C.c_int32), ("mcus_x", C.c_int32), ("mcus_y", C.c_int32),
+                ("bw", C.c_int32 * JPEG_MAX_COMP), ("bh", C.c_int32 * JPEG_MAX_COMP), ("dc_tab", C.c_int32 * JPEG_MAX_COMP), ("ac_tab", C.c_int32 * JPEG_MAX_COMP),
+                ("reserved0", C.c_int32 * 2), ("scan_offset", C.c_int64), ("coef_bytes", C.c_int64), ("qt", C.c_uint16 * 64 * JPEG_MAX_COMP),
+                ("huff_defined", C.c_uint8 * 4 * 2), ("huff_bits", C.c_uint8 * 16 * 4 * 2), ("huff_vals", C.c_uint8 * 256 * 4 * 2)]
+
+
+class JpegIdctJob(C.Structure):
+    """fd_jpeg_idct_job: one image component of the IDCT launch."""
+    _fields_ = [("coef_off", C.c_int64), ("plane_off", C.c_int64), ("bw", C.c_int32), ("bh", C.c_int32), ("qt", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class JpegColorJob(C.Structure):
+    """fd_jpeg_color_job: one image of the upsampling + colour launch."""
+    _fields_ = [("out", C.c_void_p), ("plane_off", C.c_int64 * JPEG_MAX_COMP), ("stride", C.c_int32 * JPEG_MAX_COMP), ("rows", C.c_int32 * JPEG_MAX_COMP),
+                ("width", C.c_int32), ("height", C.c_int32), ("ncomp", C.c_int32), ("h_samp", C.c_int32), ("v_samp", C.c_int32), ("reserved0", C.c_int32)]
+
+
 _lib = None
 
 _P, _I, _F, _D, _L = C.c_void_p, C.c_int32, C.c_float, C.c_double, C.c_int64
@@ -324,6 +358,10 @@ _SIGS = {
     "fd_avg_begin": (_I, [_P, _P, _P, _P, C.POINTER(AvgBeginParams), _P]),
     "fd_avg_update_f32": (_I, [C.POINTER(AvgChunk), _P, _P]),
     "fd_avg_copy_bytes": (_I, [C.POINTER(AvgCopyChunk), _P, _P]),
+    "fd_jpeg_parse": (_I, [_P, _L, C.POINTER(JpegInfo)]),
+    "fd_jpeg_entropy_decode": (_I, [_P, _L, C.POINTER(JpegInfo), _P, _L]),
+    "fd_jpeg_idct_u8": (_I, [_P, _P, _I, _P, _L, _P, _I, _P, _L, _P]),
+    "fd_jpeg_color_u8": (_I, [_P, _P, _I, _P, _L, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -2419,3 +2419,79 @@ def avg_copy(dst: Sequence[int], src: Sequence[int], nbytes: Sequence[int], stat
         check(fn(C.byref(c), st, _stream()), "fd_avg_copy_bytes")
         launches += 1
     return launches
+
+
+# ------------------------------------------------------------------------------ baseline JPEG decoding
+def _jpeg_stream(data) -> np.ndarray:
+    """bytes / bytearray / memoryview / uint8 array -> contiguous uint8 array over the same memory where possible."""
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8 or data.ndim != 1:
+            raise FdError("jpeg: a stream given as an array must be one-dimensional uint8")
+        return np.ascontiguousarray(data)
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(data, dtype=np.uint8)
+    raise FdError(f"jpeg: a stream must be bytes or a uint8 array, not {type(data).__name__}")
+
+
+def jpeg_error(rc: int, what: str) -> FdError:
+    return FdError(f"{what} failed ({rc}): {_lib.JPEG_ERRORS.get(int(rc), 'unknown error')}", rc=int(rc))
+
+
+def jpeg_parse(data) -> _lib.JpegInfo:
+    """fd_jpeg_parse: the headers of one JPEG stream up to SOS (host only).  -> JpegInfo; info.supported == 0 with info.reason (_lib.JPEG_R_*) for a
+    well-formed stream the decoder does not take.  A stream that is not well formed raises FdError with rc = _lib.JPEG_E_*."""
+    buf = _jpeg_stream(data)
+    info = _lib.JpegInfo()
+    rc = _lib.lib().fd_jpeg_parse(buf.ctypes.data, buf.size, C.byref(info))
+    if rc != 0:
+        raise jpeg_error(rc, "fd_jpeg_parse")
+    return info
+
+
+def jpeg_entropy_decode(data, info: _lib.JpegInfo, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """fd_jpeg_entropy_decode: the scan of a parsed, supported stream -> dense quantised coefficients, int16 [info.coef_bytes / 2] (component after component,
+    [bh][bw][64] in natural order).  out: a writable contiguous int16 array of at least that many elements (a slice of a staging buffer); the ctypes call
+    releases the GIL, so several threads may decode different streams at once.  Host only."""
+    buf = _jpeg_stream(data)
+    elems = int(info.coef_bytes) // 2
+    if out is None:
+        out = np.empty(elems, np.int16)
+    elif not isinstance(out, np.ndarray) or out.dtype != np.int16 or out.ndim != 1 or not out.flags.c_contiguous or not out.flags.writeable or out.size < elems:
+        raise FdError("jpeg_entropy_decode: out must be a writable contiguous int16 array of at least info.coef_bytes / 2 elements")
+    rc = _lib.lib().fd_jpeg_entropy_decode(buf.ctypes.data, buf.size, C.byref(info), out.ctypes.data, out.size * 2)
+    if rc != 0:
+        raise jpeg_error(rc, "fd_jpeg_entropy_decode")
+    return out[:elems]
+
+
+def _jpeg_jobs(who: str, jobs_host, cls, jobs_dev: torch.Tensor) -> int:
+    if not isinstance(jobs_host, C.Array) or jobs_host._type_ is not cls or len(jobs_host) < 1:
+        raise FdError(f"{who}: jobs_host must be a non-empty ctypes array of {cls.__name__}")
+    n = len(jobs_host)
+    if jobs_dev.dtype != torch.uint8 or not jobs_dev.is_contiguous() or jobs_dev.numel() < n * C.sizeof(cls):
+        raise FdError(f"{who}: jobs_dev must be a contiguous CUDA uint8 tensor holding the {n} job records")
+    return n
+
+
+def jpeg_idct_u8(jobs_host, jobs_dev: torch.Tensor, coefs: torch.Tensor, qtabs: torch.Tensor, planes: torch.Tensor) -> None:
+    """fd_jpeg_idct_u8: dequantise + jpeg_idct_islow for every (image, component) job in ONE launch.  jobs_host: ctypes array of _lib.JpegIdctJob (validated
+    before the launch); jobs_dev: the same bytes on the device (uint8); coefs: CUDA int16 [elements]; qtabs: CUDA int16 [n, 64] (the uint16 tables' bits);
+    planes: CUDA uint8 [bytes], written at each job's plane_off as [8 * bh][8 * bw].  Does not synchronise."""
+    _need_gpu(jobs_dev, coefs, qtabs, planes)
+    n = _jpeg_jobs("jpeg_idct_u8", jobs_host, _lib.JpegIdctJob, jobs_dev)
+    if coefs.dtype != torch.int16 or not coefs.is_contiguous() or qtabs.dtype != torch.int16 or not qtabs.is_contiguous() or qtabs.dim() != 2 or qtabs.shape[1] != 64:
+        raise FdError("jpeg_idct_u8: coefs must be contiguous int16 and qtabs contiguous int16 [n, 64]")
+    if planes.dtype != torch.uint8 or not planes.is_contiguous():
+        raise FdError("jpeg_idct_u8: planes must be a contiguous uint8 tensor")
+    check(_lib.lib().fd_jpeg_idct_u8(C.addressof(jobs_host), jobs_dev.data_ptr(), n, coefs.data_ptr(), coefs.numel(), qtabs.data_ptr(), int(qtabs.shape[0]),
+                                     planes.data_ptr(), planes.numel(), _stream()), "fd_jpeg_idct_u8")
+
+
+def jpeg_color_u8(jobs_host, jobs_dev: torch.Tensor, planes: torch.Tensor) -> None:
+    """fd_jpeg_color_u8: chroma upsampling + YCbCr -> RGB for every image job in ONE launch, each into its job's `out` (CUDA uint8 [h, w, 3], kept alive by the
+    caller).  jobs_host: ctypes array of _lib.JpegColorJob; jobs_dev: the same bytes on the device; planes: what jpeg_idct_u8 wrote.  Does not synchronise."""
+    _need_gpu(jobs_dev, planes)
+    n = _jpeg_jobs("jpeg_color_u8", jobs_host, _lib.JpegColorJob, jobs_dev)
+    if planes.dtype != torch.uint8 or not planes.is_contiguous():
+        raise FdError("jpeg_color_u8: planes must be a contiguous uint8 tensor")
+    check(_lib.lib().fd_jpeg_color_u8(C.addressof(jobs_host), jobs_dev.data_ptr(), n, planes.data_ptr(), planes.numel(), _stream()), "fd_jpeg_color_u8")
