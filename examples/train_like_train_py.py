@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's train.py:97-181 loop on the MI355X path, with synthetic VOC-shaped batches.
 
-    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-bn-f16] [--hip-optim] [--ema 0.999] [--update-bn 8]
+    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-bn-f16] [--hip-optim] [--ema 0.999] [--update-bn 8] [--assigner atss]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_like_train_py.py   # DDP / RCCL
 
 Same objects and call order as the reference: HalfInvertedStageFCOS([512, 1024, 2048], 20, 256), FCOSGenTargets,
@@ -20,7 +20,8 @@ instead of the host lines below.  --ema DECAY (with --hip-optim) keeps an expone
 device after every scaler.step(optimizer) -- a step GradScaler skips leaves it untouched -- and runs the averaged copy, avg.module, in eval mode at the end.
 --update-bn N (with --ema) first runs optim.update_bn over N synthetic batches: the averaged copy holds averaged weights but only copied running
 statistics, and its FPN BatchNorms run on batch statistics; update_bn recomputes exactly those on the HIP kernels (every rank passes its own batches under
-DDP: the statistics are global) and leaves the frozen backbone's alone.
+DDP: the statistics are global) and leaves the frozen backbone's alone.  --assigner atss replaces the one line train.py:98 by ATSSGenTargets(strides):
+Adaptive Training Sample Selection on the device (fd_atss_gen_targets) instead of the scale ranges and the centre radius; nothing else changes.
 """
 import argparse
 import os
@@ -33,7 +34,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_object_detection_amd import optim  # noqa: E402
 from pytorch_object_detection_amd.model.loss import FCOSLoss  # noqa: E402
-from pytorch_object_detection_amd.model.modules.head import FCOSGenTargets  # noqa: E402
+from pytorch_object_detection_amd.model.modules.head import ATSSGenTargets, FCOSGenTargets  # noqa: E402
 from pytorch_object_detection_amd.model.od import MNFCOS, HalfInvertedStageFCOS  # noqa: E402
 
 
@@ -50,6 +51,7 @@ def main():
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="average the weights on the device (optim.AveragedModel); needs --hip-optim")
     ap.add_argument("--update-bn", type=int, default=0, metavar="N",
                     help="recompute the averaged copy's batch-statistics BatchNorms over N batches before its eval forward (optim.update_bn); needs --ema")
+    ap.add_argument("--assigner", choices=["fcos", "atss"], default="fcos", help="target assignment: FCOSGenTargets (train.py:98) or ATSSGenTargets")
     args = ap.parse_args()
     if args.ema is not None and not args.hip_optim:
         ap.error("--ema gates on the HIP optimizer's skip flag: pass --hip-optim as well")
@@ -76,6 +78,8 @@ def main():
             model.enable_stem_training()
     gen_target = FCOSGenTargets(strides=[8, 16, 32, 64, 128],
                                 limit_range=[[-1, 64], [64, 128], [128, 256], [256, 512], [512, 999999]])   # train.py:98
+    if args.assigner == "atss":
+        gen_target = ATSSGenTargets(strides=[8, 16, 32, 64, 128])
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, find_unused_parameters=True)       # train.py:101
         model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)                                 # train.py:103

@@ -1034,6 +1034,25 @@ int32_t fd_fcos_gen_targets(const float* gt_boxes, const int64_t* labels, int32_
                             const int32_t* strides, const int32_t* range_lo, const int32_t* range_hi, float radius_ratio,
                             int64_t* cls_target, float* cnt_target, float* reg_target, fd_stream_t stream);
 
+/* ATSS target assignment (Adaptive Training Sample Selection, Zhang et al., CVPR 2020) on the level table,
+ * location order and outputs of fd_fcos_gen_targets.  A row is valid when label >= 0, its coordinates are finite and
+ * x2 > x1, y2 > y1; M == 0 is accepted with NULL gt_boxes / labels.  Per valid row, fp32 without FMA contraction:
+ *   candidates  per level the min(topk, H*W) locations with the smallest (d2, pix), d2 the squared distance of the
+ *               location centre (px*s + s/2, py*s + s/2) to the box centre ((x1+x2)/2, (y1+y2)/2); equal d2: lower pix
+ *   iou         fd_pairwise_iou(plus_one = 0) of the square anchor centre -/+ (anchor_scale * s) / 2 and the box
+ *   thr         mean + sample standard deviation of the candidates' iou, in fp64, summed in candidate order
+ *   positive    (double)iou >= thr and min(cx-x1, cy-y1, x2-cx, y2-cy) > inside_eps
+ * A location positive for several rows goes to the largest iou, then to the lowest row.  gt_thr [B][M] (thr, NaN for
+ * padding) and gt_npos [B][M] (positives of the row before the contest) are optional (NULL).  workspace:
+ * fd_atss_workspace_bytes(B, L) bytes, 8-byte aligned; gt_boxes / reg_target 16-byte aligned.  One memset and two
+ * launches, no host synchronisation.  topk > FD_ATSS_MAX_TOPK: FD_E_UNSUPPORTED; other bad arguments: FD_E_INVAL. */
+#define FD_ATSS_MAX_TOPK 16
+int64_t fd_atss_workspace_bytes(int32_t B, int32_t L);
+int32_t fd_atss_gen_targets(const float* gt_boxes, const int64_t* labels, int32_t M, const fd_segs* segs,
+                            const int32_t* strides, int32_t topk, float anchor_scale, float inside_eps,
+                            int64_t* cls_target, float* cnt_target, float* reg_target, double* gt_thr, int32_t* gt_npos,
+                            void* workspace, fd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------- */
 /* Anchor targets and detections (DataEncoder.encode / decode, utill/utills.py:100-199).
  *

@@ -129,3 +129,22 @@ class FCOSGenTargets(nn.Module):
         assert len(self.stride) == len(cls_logit)
         level_hw = [(int(t.shape[2]), int(t.shape[3])) for t in cls_logit]
         return ops.fcos_gen_targets(gt_box, labels, level_hw, self.stride, self.lim_range, 1.5)
+
+
+class ATSSGenTargets(nn.Module):
+    """ATSSGenTargets(strides, topk=9, anchor_scale=8.0, inside_eps=0.01)([out, gt_boxes, classes]) -> the triple of
+    FCOSGenTargets, assigned by Adaptive Training Sample Selection (Zhang et al., CVPR 2020) instead of the scale ranges and
+    the centre radius: per GT box the `topk` locations of every level nearest to its centre are candidates, and those whose
+    anchor IoU (one square anchor of side anchor_scale * stride per location) reaches mean + std of the candidates' IoUs and
+    whose centre lies more than inside_eps inside the box are positive (fd_atss_gen_targets; DESIGN 4.3o states the rule)."""
+
+    def __init__(self, strides: List[int], topk: int = 9, anchor_scale: float = 8.0, inside_eps: float = 0.01):
+        super().__init__()
+        self.stride, self.topk, self.anchor_scale, self.inside_eps = strides, topk, anchor_scale, inside_eps
+
+    def forward(self, x):
+        cls_logit = x[0][0]
+        gt_box, labels = x[1], x[2]
+        assert len(self.stride) == len(cls_logit)
+        level_hw = [(int(t.shape[2]), int(t.shape[3])) for t in cls_logit]
+        return ops.atss_gen_targets(gt_box, labels, level_hw, self.stride, self.topk, self.anchor_scale, self.inside_eps)

@@ -2095,6 +2095,38 @@ def fcos_gen_targets(gt_boxes: torch.Tensor, labels: torch.Tensor, level_hw, str
     return cls, cnt, reg
 
 
+ATSS_MAX_TOPK = 16      # include/fcosdet.h FD_ATSS_MAX_TOPK
+
+
+def atss_gen_targets(gt_boxes: torch.Tensor, labels: torch.Tensor, level_hw, strides, topk: int = 9, anchor_scale: float = 8.0,
+                     inside_eps: float = 0.01, return_stats: bool = False):
+    """ATSS assignment (fd_atss_gen_targets) on the contract of fcos_gen_targets: gt_boxes [B,M,4] f32, labels [B,M]
+    int64 (M may be 0) -> (cls [B,L,1] int64, cnt [B,L,1] f32, reg [B,L,4] f32); with return_stats also thr [B,M] f64 (mean + std
+    of a row's candidate IoUs, NaN for padding) and npos [B,M] int32 (its positives before locations are contested)."""
+    _need_gpu(gt_boxes, labels)
+    B, M = labels.shape
+    if len(strides) != len(level_hw) or tuple(gt_boxes.shape) != (B, M, 4):
+        raise FdError(f"atss_gen_targets: {len(level_hw)} levels, {len(strides)} strides, gt_boxes {tuple(gt_boxes.shape)}, labels {tuple(labels.shape)}")
+    segs = Segs.make(B, list(level_hw))
+    L = sum(h * w for h, w in level_hw)
+    dev = gt_boxes.device
+    cls = torch.empty(B, L, 1, dtype=torch.int64, device=dev)
+    cnt = torch.empty(B, L, 1, dtype=torch.float32, device=dev)
+    reg = torch.empty(B, L, 4, dtype=torch.float32, device=dev)
+    thr =torch.empty(B, M, dtype=torch.float64, device=dev) if return_stats else None
+    npos = torch.empty(B, M, dtype=torch.int32, device=dev) if return_stats else None
+    ws = torch.empty(max(_lib.lib().fd_atss_workspace_bytes(B, L), 0) // 8, dtype=torch.int64, device=dev)
+    n = len(level_hw)
+    st = (C.c_int32 * n)(*[int(s) for s in strides])
+    gb = gt_boxes.contiguous().float()
+    lb = labels.contiguous().to(torch.int64)
+    check(_lib.lib().fd_atss_gen_targets(gb.data_ptr() if M else None, lb.data_ptr() if M else None, M, C.byref(segs), st, int(topk),
+                                         float(anchor_scale), float(inside_eps), cls.data_ptr(), cnt.data_ptr(), reg.data_ptr(),
+                                         thr.data_ptr() if return_stats and M else None, npos.data_ptr() if return_stats and M else None,
+                                         ws.data_ptr(), _stream()), "fd_atss_gen_targets")
+    return (cls, cnt, reg, thr, npos) if return_stats else (cls, cnt, reg)
+
+
 # ---------------------------------------------------------------------------------------------------- anchors (DataEncoder)
 ANCHOR_LEVELS, ANCHOR_PER_CELL = 5, 9
 
