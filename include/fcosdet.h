@@ -628,6 +628,35 @@ int32_t fd_jitter_l_sums(const uint8_t* const* images_dev, int32_t* recs_dev, ui
 int32_t fd_color_jitter_u8(const uint8_t* x, int32_t h, int32_t w, uint8_t* y, const int32_t* rec_dev, fd_stream_t stream);
 int32_t fd_rotate_u8(const uint8_t* x, int32_t h, int32_t w, uint8_t* y, const int32_t* fixed6, fd_stream_t stream);
 
+/* Mosaic on the device: four augmented sources tiled around a centre on one H x W canvas per output, ONE launch
+ * per batch, nothing allocated.  images_dev: DEVICE array of 4*N device pointers, tile t of output n at [4n + t] (a source
+ * used several times is simply repeated); recs_dev: DEVICE int32 [4*N][FD_AUG_WORDS], the record above, one per tile;
+ * place_dev: DEVICE int32 [N][FD_MOSAIC_WORDS]:
+ *
+ *   FD_MOSAIC_XC, FD_MOSAIC_YC    the centre: canvas pixel (dy, dx) belongs to tile t = 2 * (dy >= YC) + (dx >= XC)
+ *                                 (0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right)
+ *   FD_MOSAIC_FILL                the level of pixels no tile covers, packed 0x00BBGGRR
+ *   FD_MOSAIC_PX0 + 2t, + 2t + 1  (PXt, PYt): canvas position of tile t's pixel (0, 0); may be negative
+ *   last word                     reserved, zero
+ *
+ * With ly = dy - PYt, lx = dx - PXt: when 0 <= ly < NH and 0 <= lx < NW of record 4n + t (and its H, W, CROP_W, CROP_H are
+ * >= 1) the pixel is exactly what fd_augment_resize_collate_u8 produces at (ly, lx) for that record and source -- the same
+ * taps, weights, crop / rotation / mirror maps, colour chain, blend and rounding (one shared device function); otherwise it is
+ * FILL.  Then the same Normalize expression.  y: PLANAR fp32 [N][3][H][W].  A record's FD_AUG_MEAN_L is filled in by
+ * fd_jitter_l_sums run on the same 4*N pointers and records.  Refused with FD_E_INVAL: a null pointer, y / records /
+ * placements not 4-byte or the pointer table not 8-byte aligned, N outside 1 .. FD_MOSAIC_MAX_N (4*N must fit fd_jitter_l_sums),
+ * canvas sides outside 1 .. 65536 or H*W >= 2^31, a zero std.  The tables cannot be read by the host; whatever they hold, a tap
+ * is loaded only after its final (row, column) has been checked against the record's [h][w], only canvas pixels are written,
+ * and XC, YC, PX, PY are only compared and subtracted in 64 bits.  mean3 / std3 are HOST pointers. */
+#define FD_MOSAIC_WORDS 12
+#define FD_MOSAIC_XC 0
+#define FD_MOSAIC_YC 1
+#define FD_MOSAIC_FILL 2
+#define FD_MOSAIC_PX0 3
+#define FD_MOSAIC_MAX_N 16383
+int32_t fd_mosaic_collate_u8(const uint8_t* const* images_dev, const int32_t* recs_dev, const int32_t* place_dev, float* y,
+                             int32_t N, int32_t H, int32_t W, const float* mean3, const float* std3, fd_stream_t stream);
+
 /* GroupNorm(G, C) + activation (nn.GroupNorm in HISFCOSHead / HeadFCOS, HISFcos.py:190-204, Fcos.py:102-109).
  * Two launches: partial moments (fp64 accumulation, fixed order) then normalise+affine+act.
  * workspace: fd_groupnorm_workspace_bytes(segs, G). x and y may alias. */

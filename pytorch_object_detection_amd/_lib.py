@@ -266,6 +266,7 @@ _SIGS = {
     "fd_resize_collate_u8_nhwc4": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),
     "fd_boxes_scale_batch": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "fd_augment_resize_collate_u8": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),
+    "fd_mosaic_collate_u8": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),
     "fd_jitter_l_sums": (_I, [_P, _P, _P, _I, _L, _P]),
     "fd_color_jitter_u8": (_I, [_P, _I, _I, _P, _P, _P]),
     "fd_rotate_u8": (_I, [_P, _I, _I, _P, C.POINTER(_I), _P]),

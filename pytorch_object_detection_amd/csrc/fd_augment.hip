@@ -8,6 +8,8 @@
 //   * Colour: PIL's ImageEnhance Brightness / Contrast / Color, clip(trunc(deg + f * (pix - deg))) in fp32, and the HSV hue
 //     shift; exact against PIL (tests/augment_ref.py restates all of it in numpy).  Compiled with -ffp-contract=off.
 //   * Contrast needs int(mean(L) + 0.5) of the image at that point of the chain: fd_jitter_l_sums reduces it in integers.
+//   * Mosaic: fd_mosaic_collate_u8 tiles four such images around a centre per output; per canvas pixel it picks
+//     the tile, then runs the same per-pixel function (aug_pixel) as the fused launch.
 // Whatever a record holds, a tap is read only after its final (row, column) has been checked against [h][w], and only
 // canvas pixels are written.
 #include "fd_resize_taps.h"
@@ -83,6 +85,42 @@ __device__ __forceinline__ void aug_rot_map(const int* __restrict__ fx, int y, i
     sy = (qy < -1 || qy > 0x7fffffff) ? -1 : (int)qy;
 }
 
+// One resized pixel (ly, lx) of the record's NH x NW image: the four taps of the CROP_H x CROP_W -> NH x NW resize, each through
+// crop offset -> rotation map -> mirrored column -> raw bytes -> colour chain, blended.  The caller has checked 0 <= ly < nh,
+// 0 <= lx < nw and h, w, cw, ch >= 1.  Shared by the fused launch and the mosaic launch so that there is one definition.
+__device__ __forceinline__ void aug_pixel(const int* __restrict__ rec, const unsigned char* __restrict__ img, int ly, int lx, int h, int w, int nh, int nw,
+                                          int cw, int ch, unsigned& r, unsigned& g, unsigned& b) {
+    const int cx = rec[FD_AUG_CROP_X], cy = rec[FD_AUG_CROP_Y], flip = rec[FD_AUG_FLIP], rot = rec[FD_AUG_ROT_ON];
+    const int nops = aug_chain_len(rec);
+    int y0, y1, x0, x1;
+    unsigned cy0, cy1, cx0, cx1;
+    resize_axis(ly, ch, nh, y0, y1, cy0, cy1);
+    resize_axis(lx, cw, nw, x0, x1, cx0, cx1);
+    unsigned ar = 0, ag = 0, ab = 0;
+#pragma unroll 1
+    for (int t = 0; t < 4; ++t) {
+        int sy = ((t & 2) ? y1 : y0) + cy, sx = ((t & 1) ? x1 : x0) + cx;
+        const unsigned wt = ((t & 2) ? cy1 : cy0) * ((t & 1) ? cx1 : cx0);
+        if (rot) {
+            const bool in_rot = (unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w;
+            aug_rot_map(rec + FD_AUG_ROT0, sy, sx, sy, sx);
+            if (!in_rot) sy = -1;
+        }
+        if (flip) sx = w - 1 - sx;
+        unsigned pr = 0, pg = 0, pb = 0;
+        if ((unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w) {      // the only gate in front of the loads
+            const unsigned char* p = img + ((long)sy * w + sx) * 3;
+            pr = p[0]; pg = p[1]; pb = p[2];
+            aug_chain(rec, nops, pr, pg, pb);
+        }
+        ar += pr * wt; ag += pg * wt; ab += pb * wt;
+    }
+    constexpr unsigned half = 1u << (2 * FD_RESIZE_COEF_BITS - 1);
+    r = (ar + half) >> (2 * FD_RESIZE_COEF_BITS);
+    g = (ag + half) >> (2 * FD_RESIZE_COEF_BITS);
+    b = (ab + half) >> (2 * FD_RESIZE_COEF_BITS);
+}
+
 // ------------------------------------------------------------------------------ the fused launch
 __global__ __launch_bounds__(256) void augment_resize_collate_u8_kernel(const unsigned char* const* __restrict__ src, const int* __restrict__ recs,
                                                                          float* __restrict__ y, int H, int W, float m0, float m1, float m2,
@@ -95,38 +133,7 @@ __global__ __launch_bounds__(256) void augment_resize_collate_u8_kernel(const un
     const int h = rec[FD_AUG_H], w = rec[FD_AUG_W], nh = rec[FD_AUG_NH], nw = rec[FD_AUG_NW];
     const int cw = rec[FD_AUG_CROP_W], ch = rec[FD_AUG_CROP_H];
     unsigned r = 0, g = 0, b = 0;
-    if ((int)dy < nh && (int)dx < nw && h >= 1 && w >= 1 && cw >= 1 && ch >= 1) {
-        const int cx = rec[FD_AUG_CROP_X], cy = rec[FD_AUG_CROP_Y], flip = rec[FD_AUG_FLIP], rot = rec[FD_AUG_ROT_ON];
-        const int nops = aug_chain_len(rec);
-        const unsigned char* __restrict__ img = src[n];
-        int y0, y1, x0, x1;
-        unsigned cy0, cy1, cx0, cx1;
-        resize_axis((int)dy, ch, nh, y0, y1, cy0, cy1);
-        resize_axis((int)dx, cw, nw, x0, x1, cx0, cx1);
-        unsigned ar = 0, ag = 0, ab = 0;
-#pragma unroll 1
-        for (int t = 0; t < 4; ++t) {
-            int sy = ((t & 2) ? y1 : y0) + cy, sx = ((t & 1) ? x1 : x0) + cx;
-            const unsigned wt = ((t & 2) ? cy1 : cy0) * ((t & 1) ? cx1 : cx0);
-            if (rot) {
-                const bool in_rot = (unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w;
-                aug_rot_map(rec + FD_AUG_ROT0, sy, sx, sy, sx);
-                if (!in_rot) sy = -1;
-            }
-            if (flip) sx = w - 1 - sx;
-            unsigned pr = 0, pg = 0, pb = 0;
-            if ((unsigned)sy < (unsigned)h && (unsigned)sx < (unsigned)w) {      // the only gate in front of the loads
-                const unsigned char* p = img + ((long)sy * w + sx) * 3;
-                pr = p[0]; pg = p[1]; pb = p[2];
-                aug_chain(rec, nops, pr, pg, pb);
-            }
-            ar += pr * wt; ag += pg * wt; ab += pb * wt;
-        }
-        constexpr unsigned half = 1u << (2 * FD_RESIZE_COEF_BITS - 1);
-        r = (ar + half) >> (2 * FD_RESIZE_COEF_BITS);
-        g = (ag + half) >> (2 * FD_RESIZE_COEF_BITS);
-        b = (ab + half) >> (2 * FD_RESIZE_COEF_BITS);
-    }
+    if ((int)dy < nh && (int)dx < nw && h >= 1 && w >= 1 && cw >= 1 && ch >= 1) aug_pixel(rec, src[n], (int)dy, (int)dx, h, w, nh, nw, cw, ch, r, g, b);
     const long per = (long)H * W;
     float* o = y + (long)n * 3 * per + i;
     o[0] = ((float)r / 255.0f - m0) / s0;
@@ -145,6 +152,51 @@ extern "C" int32_t fd_augment_resize_collate_u8(const uint8_t* const* images_dev
     hipLaunchKernelGGL(augment_resize_collate_u8_kernel, dim3((unsigned)((per + 255) / 256), 1, (unsigned)N), dim3(256), 0, (hipStream_t)stream,
                        images_dev, recs_dev, y, H, W, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
     FD_CHECK_LAUNCH("fd_augment_resize_collate_u8");
+    return FD_OK;
+}
+
+// ------------------------------------------------------------------------------ the mosaic launch
+// Four sources per output: canvas pixel (dy, dx) of output n belongs to tile t = 2 * (dy >= YC) + (dx >= XC) and is pixel
+// (dy - PYt, dx - PXt) of the NH x NW image of record 4n + t, or the FILL level when that lies outside it (or the record's sizes
+// are not positive).  XC, YC, PX, PY are only compared and subtracted in 64 bits: any 32-bit value is safe.  The record is chosen
+// per lane, so its words come through vector loads here; everything behind the choice is aug_pixel, the fused launch's arithmetic.
+__global__ __launch_bounds__(256) void mosaic_collate_u8_kernel(const unsigned char* const* __restrict__ src, const int* __restrict__ recs,
+                                                                 const int* __restrict__ place, float* __restrict__ y, int H, int W, float m0, float m1,
+                                                                 float m2, float s0, float s1, float s2) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (unsigned)H * (unsigned)W) return;
+    const int n = blockIdx.z;
+    const int* __restrict__ pl = place + (long)n * FD_MOSAIC_WORDS;
+    const unsigned dy = i / (unsigned)W, dx = i - dy * (unsigned)W;
+    const int t = ((int)dy >= pl[FD_MOSAIC_YC] ? 2 : 0) + ((int)dx >= pl[FD_MOSAIC_XC] ? 1 : 0);
+    const long slot = (long)n * 4 + t;
+    const int* __restrict__ rec = recs + slot * FD_AUG_WORDS;
+    const long ly = (long)dy - (long)pl[FD_MOSAIC_PX0 + 2 * t + 1], lx = (long)dx - (long)pl[FD_MOSAIC_PX0 + 2 * t];
+    const int h = rec[FD_AUG_H], w = rec[FD_AUG_W], nh = rec[FD_AUG_NH], nw = rec[FD_AUG_NW];
+    const int cw = rec[FD_AUG_CROP_W], ch = rec[FD_AUG_CROP_H];
+    const unsigned fill = (unsigned)pl[FD_MOSAIC_FILL];
+    unsigned r = fill & 255u, g = (fill >> 8) & 255u, b = (fill >> 16) & 255u;
+    if (ly >= 0 && ly < (long)nh && lx >= 0 && lx < (long)nw && h >= 1 && w >= 1 && cw >= 1 && ch >= 1)
+        aug_pixel(rec, src[slot], (int)ly, (int)lx, h, w, nh, nw, cw, ch, r, g, b);
+    const long per = (long)H * W;
+    float* o = y + (long)n * 3 * per + i;
+    o[0] = ((float)r / 255.0f - m0) / s0;
+    o[per] = ((float)g / 255.0f - m1) / s1;
+    o[2 * per] = ((float)b / 255.0f - m2) / s2;
+}
+
+extern "C" int32_t fd_mosaic_collate_u8(const uint8_t* const* images_dev, const int32_t* recs_dev, const int32_t* place_dev, float* y, int32_t N, int32_t H,
+                                        int32_t W, const float* mean3, const float* std3, fd_stream_t stream) {
+    FD_REQUIRE(images_dev && recs_dev && place_dev && y && mean3 && std3, FD_E_INVAL, "fd_mosaic_collate_u8: null pointer");
+    FD_REQUIRE(N >= 1 && N <= FD_MOSAIC_MAX_N && H >= 1 && W >= 1 && H <= FD_RESIZE_MAX_SIDE && W <= FD_RESIZE_MAX_SIDE && (long)H * W < (1l << 31), FD_E_INVAL,
+               "fd_mosaic_collate_u8: bad batch %d or canvas %d x %d", N, H, W);
+    FD_REQUIRE(((uintptr_t)y & 3) == 0 && ((uintptr_t)recs_dev & 3) == 0 && ((uintptr_t)place_dev & 3) == 0 && ((uintptr_t)images_dev & 7) == 0, FD_E_INVAL,
+               "fd_mosaic_collate_u8: y / records / placements not 4-byte or pointers not 8-byte aligned");
+    FD_REQUIRE(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, FD_E_INVAL, "fd_mosaic_collate_u8: zero std");
+    const long per = (long)H * W;
+    hipLaunchKernelGGL(mosaic_collate_u8_kernel, dim3((unsigned)((per + 255) / 256), 1, (unsigned)N), dim3(256), 0, (hipStream_t)stream, images_dev,
+                       recs_dev, place_dev, y, H, W, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    FD_CHECK_LAUNCH("fd_mosaic_collate_u8");
     return FD_OK;
 }
 

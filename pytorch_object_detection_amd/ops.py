@@ -1344,6 +1344,96 @@ def augment_resize_collate_u8(images: Sequence[torch.Tensor], params, H: int, W:
     return out.view(N, 3, H, W), (tab, sums, tuple(images))
 
 
+# mosaic: include/fcosdet.h FD_MOSAIC_*, the per-output placement record
+MOSAIC_WORDS = 12
+_MOSAIC_XC, _MOSAIC_YC, _MOSAIC_FILL, _MOSAIC_PX0 = 0, 1, 2, 3
+MOSAIC_MAX_N = 16383                             # 4 * N records must fit fd_jitter_l_sums
+MOSAIC_MAX_OFFSET = 65536
+
+
+def _pack_fill(fill, what: str) -> int:
+    try:
+        r, g, b = (int(v) for v in fill)
+    except (TypeError, ValueError):
+        raise FdError(f"{what}: fill must be three levels 0 .. 255 (got {fill!r})") from None
+    if not all(0 <= v <= 255 for v in (r, g, b)) or any(float(v) != int(v) for v in fill):
+        raise FdError(f"{what}: fill must be three levels 0 .. 255 (got {fill!r})")
+    return r | (g << 8) | (b << 16)
+
+
+def mosaic_collate_u8(images: Sequence[torch.Tensor], tiles, centres, H: int, W: int, mean, std, fill=(0, 0, 0), out: Optional[torch.Tensor] = None):
+    """Mosaic of RAW uint8 [h, w, 3] CUDA images: output n is an H x W canvas split at centres[n] = (xc, yc) into four quadrants
+    (tile 0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right); tiles[n][t] = dict(src=index into images, px=, py=, plus the
+    keywords of augment_record: flip=, chain=, d=, crop=, nh=, nw=) puts the augmented, nh x nw resized source with its pixel
+    (0, 0) at canvas (py, px), clipped to quadrant t; what no tile covers is `fill` (R, G, B).  Pixels inside a tile are exactly
+    those of augment_resize_collate_u8 for that record; then Normalize: the planar fp32 [N, 3, H, W] batch in ONE launch (plus the
+    L-sum launch over the 4 * N records when a chain holds contrast) after one table upload.  A source may be used in any number
+    of tiles and outputs.  Returns (batch, keep-alive tuple).  Does not synchronise."""
+    what = "mosaic_collate_u8"
+    images = list(images)
+    if len(images) < 1:
+        raise FdError(f"{what}: empty image list")
+    for t in images:
+        _check_raw_image(t, what)
+    tiles, centres = [list(q) for q in tiles], [tuple(c) for c in centres]
+    N = len(tiles)
+    if N < 1 or N > MOSAIC_MAX_N or len(centres) != N:
+        raise FdError(f"{what}: 1 .. {MOSAIC_MAX_N} outputs, one centre and four tiles each (got {N} tile sets, {len(centres)} centres)")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H > 65536 or W > 65536 or H * W >= 2 ** 31:
+        raise FdError(f"{what}: bad canvas {H} x {W}")
+    if any(float(v) == 0.0 for v in std):
+        raise FdError(f"{what}: zero std")
+    packed_fill = _pack_fill(fill, what)
+    recs, slots, place = [], [], []
+    for n, (quad, c) in enumerate(zip(tiles, centres)):
+        if len(quad) != 4 or len(c) != 2:
+            raise FdError(f"{what}: output {n} needs four tiles and a centre (xc, yc)")
+        xc, yc = int(c[0]), int(c[1])
+        if not (0 <= xc <= W and 0 <= yc <= H):
+            raise FdError(f"{what}: centre {(xc, yc)} of output {n} is outside 0 .. {W} / 0 .. {H}")
+        row = [xc, yc, packed_fill]
+        for tile in quad:
+            kw = dict(tile)
+            try:
+                src, px, py = int(kw.pop("src")), int(kw.pop("px")), int(kw.pop("py"))
+            except KeyError as e:
+                raise FdError(f"{what}: a tile needs src=, px= and py= (missing {e})") from None
+            if not 0 <= src < len(images):
+                raise FdError(f"{what}: tile source {src} is not an index into the {len(images)} images")
+            if abs(px) > MOSAIC_MAX_OFFSET or abs(py) > MOSAIC_MAX_OFFSET:
+                raise FdError(f"{what}: tile offset {(px, py)} beyond +-{MOSAIC_MAX_OFFSET}")
+            img = images[src]
+            rec = augment_record(int(img.shape[0]), int(img.shape[1]), what=what, **kw)
+            if rec[_AUG_NH] > 65536 or rec[_AUG_NW] > 65536:
+                raise FdError(f"{what}: resized tile {rec[_AUG_NH]} x {rec[_AUG_NW]} has a side above 65536")
+            recs.append(rec)
+            slots.append(img)
+            row += [px, py]
+        place.append(row + [0])
+    dev = images[0].device
+    if out is None:
+        out = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
+    elif not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != N * 3 * H * W:
+        raise FdError(f"{what}: out must be a contiguous CUDA fp32 tensor of N * 3 * H * W elements")
+    # one table, one copy: the 4N tile pointers (two int32 words each) in front, then the 4N records, then the N placements
+    S = 4 * N
+    table = np.empty(S * (AUG_WORDS + 2) + N * MOSAIC_WORDS, np.int32)
+    table[:2 * S] = np.array([t.data_ptr() for t in slots], np.int64).view(np.int32)
+    table[2 * S:S * (AUG_WORDS + 2)] = np.array(recs, np.int64).astype(np.int32).reshape(-1)
+    table[S * (AUG_WORDS + 2):] = np.array(place, np.int64).astype(np.int32).reshape(-1)
+    tab = torch.from_numpy(table).to(dev, non_blocking=True)
+    ptrs, recs_dev, place_dev = tab[:2 * S].view(torch.int64), tab[2 * S:S * (AUG_WORDS + 2)].view(S, AUG_WORDS), tab[S * (AUG_WORDS + 2):]
+    sums = None
+    if any(_has_contrast(r) for r in recs):
+        sums = jitter_l_sums(slots, recs_dev, ptrs)
+    m = (C.c_float * 3)(*[float(v) for v in mean])
+    s_ = (C.c_float * 3)(*[float(v) for v in std])
+    check(_lib.lib().fd_mosaic_collate_u8(ptrs.data_ptr(), recs_dev.data_ptr(), place_dev.data_ptr(), out.data_ptr(), N, H, W, m, s_, _stream()),
+          "fd_mosaic_collate_u8")
+    return out.view(N, 3, H, W), (tab, sums, tuple(images))
+
+
 def rotate_u8(img: torch.Tensor, d: float) -> torch.Tensor:
     """PIL's img.rotate(d) (NEAREST, no expand) of a raw uint8 [h, w, 3] CUDA image, exact: 16.16 fixed-point integer
     arithmetic on the device (random_rotation, data/augment.py:26-30).  d == 0 is the identity; |d| >= 90 is refused."""
