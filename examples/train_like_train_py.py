@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's train.py:97-181 loop on the MI355X path, with synthetic VOC-shaped batches.
 
-    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-bn-f16] [--hip-optim] [--ema 0.999] [--update-bn 8] [--assigner atss]
+    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-bn-f16] [--hip-optim] [--ema 0.999] [--update-bn 8] [--assigner atss|simota]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_like_train_py.py   # DDP / RCCL
 
 Same objects and call order as the reference: HalfInvertedStageFCOS([512, 1024, 2048], 20, 256), FCOSGenTargets,
@@ -21,7 +21,8 @@ device after every scaler.step(optimizer) -- a step GradScaler skips leaves it u
 --update-bn N (with --ema) first runs optim.update_bn over N synthetic batches: the averaged copy holds averaged weights but only copied running
 statistics, and its FPN BatchNorms run on batch statistics; update_bn recomputes exactly those on the HIP kernels (every rank passes its own batches under
 DDP: the statistics are global) and leaves the frozen backbone's alone.  --assigner atss replaces the one line train.py:98 by ATSSGenTargets(strides):
-Adaptive Training Sample Selection on the device (fd_atss_gen_targets) instead of the scale ranges and the centre radius; nothing else changes.
+Adaptive Training Sample Selection on the device (fd_atss_gen_targets) instead of the scale ranges and the centre radius; --assigner simota by SimOTAGenTargets(strides): SimOTA on the device (fd_simota_gen_targets),
+which ranks the locations inside a box by the score and the box the model currently predicts there; nothing else changes.
 """
 import argparse
 import os
@@ -34,7 +35,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_object_detection_amd import optim  # noqa: E402
 from pytorch_object_detection_amd.model.loss import FCOSLoss  # noqa: E402
-from pytorch_object_detection_amd.model.modules.head import ATSSGenTargets, FCOSGenTargets  # noqa: E402
+from pytorch_object_detection_amd.model.modules.head import ATSSGenTargets, FCOSGenTargets, SimOTAGenTargets  # noqa: E402
 from pytorch_object_detection_amd.model.od import MNFCOS, HalfInvertedStageFCOS  # noqa: E402
 
 
@@ -51,7 +52,8 @@ def main():
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="average the weights on the device (optim.AveragedModel); needs --hip-optim")
     ap.add_argument("--update-bn", type=int, default=0, metavar="N",
                     help="recompute the averaged copy's batch-statistics BatchNorms over N batches before its eval forward (optim.update_bn); needs --ema")
-    ap.add_argument("--assigner", choices=["fcos", "atss"], default="fcos", help="target assignment: FCOSGenTargets (train.py:98) or ATSSGenTargets")
+    ap.add_argument("--assigner", choices=["fcos", "atss", "simota"], default="fcos",
+                    help="target assignment: FCOSGenTargets (train.py:98), ATSSGenTargets or SimOTAGenTargets")
     args = ap.parse_args()
     if args.ema is not None and not args.hip_optim:
         ap.error("--ema gates on the HIP optimizer's skip flag: pass --hip-optim as well")
@@ -80,6 +82,8 @@ def main():
                                 limit_range=[[-1, 64], [64, 128], [128, 256], [256, 512], [512, 999999]])   # train.py:98
     if args.assigner == "atss":
         gen_target = ATSSGenTargets(strides=[8, 16, 32, 64, 128])
+    elif args.assigner == "simota":
+        gen_target = SimOTAGenTargets(strides=[8, 16, 32, 64, 128])
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, find_unused_parameters=True)       # train.py:101
         model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)                                 # train.py:103

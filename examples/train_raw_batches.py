@@ -3,7 +3,7 @@
 data.augment.collate_train_raw -- the reference's flip + Transforms + preprocess_img_boxes + collate_fn, the pixel work in one
 fused HIP launch -- and the triple it returns is what model / FCOSGenTargets / FCOSLoss take in train() mode.
 
-    python examples/train_raw_batches.py [--steps 10] [--batch 8] [--amp] [--min-side 512 --max-side 512] [--assigner atss]
+    python examples/train_raw_batches.py [--steps 10] [--batch 8] [--amp] [--min-side 512 --max-side 512] [--assigner atss|simota]
 
 The images here are synthetic (JPEG decoding stays on the host and is not part of this project); single GPU.
 """
@@ -19,7 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pytorch_object_detection_amd.data.augment import collate_train_raw  # noqa: E402
 from pytorch_object_detection_amd.model.loss import FCOSLoss  # noqa: E402
-from pytorch_object_detection_amd.model.modules.head import ATSSGenTargets, FCOSGenTargets  # noqa: E402
+from pytorch_object_detection_amd.model.modules.head import ATSSGenTargets, FCOSGenTargets, SimOTAGenTargets  # noqa: E402
 from pytorch_object_detection_amd.model.od import HalfInvertedStageFCOS  # noqa: E402
 
 
@@ -40,7 +40,8 @@ def main():
     ap.add_argument("--amp", action="store_true")
     ap.add_argument("--min-side", type=int, default=512)
     ap.add_argument("--max-side", type=int, default=512)
-    ap.add_argument("--assigner", choices=["fcos", "atss"], default="fcos", help="target assignment: FCOSGenTargets or ATSSGenTargets")
+    ap.add_argument("--assigner", choices=["fcos", "atss", "simota"], default="fcos",
+                    help="target assignment: FCOSGenTargets, ATSSGenTargets or SimOTAGenTargets")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -48,6 +49,8 @@ def main():
     gen_target = FCOSGenTargets(strides=[8, 16, 32, 64, 128], limit_range=[[-1, 64], [64, 128], [128, 256], [256, 512], [512, 999999]])
     if args.assigner == "atss":
         gen_target = ATSSGenTargets(strides=[8, 16, 32, 64, 128])
+    elif args.assigner == "simota":
+        gen_target = SimOTAGenTargets(strides=[8, 16, 32, 64, 128])
     LR_INIT, WARMUP_STEPS = 1e-3, 501
     optimizer = torch.optim.SGD([p for p in model.parameters() if p.requires_grad], lr=LR_INIT, momentum=0.9, weight_decay=1e-4)
     scaler = torch.amp.GradScaler("cuda", enabled=args.amp)

@@ -1082,6 +1082,35 @@ int32_t fd_atss_gen_targets(const float* gt_boxes, const int64_t* labels, int32_
                             int64_t* cls_target, float* cnt_target, float* reg_target, double* gt_thr, int32_t* gt_npos,
                             void* workspace, fd_stream_t stream);
 
+/* SimOTA target assignment (Ge et al., OTA, CVPR 2021; YOLOX) on the level table, location order and outputs
+ * of fd_fcos_gen_targets, ranked by the current predictions: cls_logits [B][L][C], cnt_logits [B][L], reg_pred [B][L][4]
+ * (l, t, r, b) distances in pixels, all fp32.  A row is valid when 1 <= label <= C (its class is column label - 1), its
+ * coordinates are finite and x2 > x1, y2 > y1; M == 0 is accepted with NULL gt_boxes / labels.  fp32 without FMA
+ * contraction; c = (px*s + s/2, py*s + s/2) the centre of location p, nl(x) = -logf(x) where that is < 100, else 100:
+ *   per location  q_c = sqrtf(sigmoid(cls_c) * sigmoid(cnt)); N = sum_c nl(1 - q_c), sequentially, c ascending
+ *   candidate     min(cx-x1, cy-y1, x2-cx, y2-cy) > inside_eps
+ *   preferred     a candidate with max(|cx-gx|, |cy-gy|) < centre_radius * (float)s, g = ((x1+x2)/2, (y1+y2)/2)
+ *   iou           fd_pairwise_iou(plus_one = 0) of (cx-l, cy-t, cx+r, cy+b) and the row; !(iou > 0) -> 0, iou > 1 -> 1
+ *   cost          ((N - nl(1 - q_g)) + nl(q_g)) + iou_weight * (0.0f - logf(iou + 1e-8f)), g the row's class;
+ *                 !(cost < FLT_MAX) -> FLT_MAX
+ *   k             n = number of candidates; sum of the min(top_q, n) largest iou, descending; k = min(max((int)sum, 1), n)
+ *   positive      the k candidates with the smallest (not preferred, cost, p), p the location index in [0, L)
+ * A location positive for several rows goes to the smallest (not preferred, cost, row).  cnt_target is the centre-ness
+ * of fd_fcos_gen_targets (quality 0) or the winning pair's iou (quality 1).  Optional (NULL): pair_iou / pair_cost
+ * [B][M][L] (0 / +inf for non-candidates and padding rows), gt_k / gt_ncand [B][M] (k and n, 0 for padding).
+ * workspace: fd_simota_workspace_bytes(B, M, L) bytes, 8-byte aligned; gt_boxes / reg_pred / reg_target 16-byte
+ * aligned; it may hold anything.  Three launches (M == 0: one), no memset, no host synchronisation.  top_q > FD_SIMOTA_MAX_TOPQ or
+ * M > FD_SIMOTA_MAX_GT: FD_E_UNSUPPORTED; other bad arguments: FD_E_INVAL. */
+#define FD_SIMOTA_MAX_TOPQ 16
+#define FD_SIMOTA_MAX_GT 256
+int64_t fd_simota_workspace_bytes(int32_t B, int32_t M, int32_t L);
+int32_t fd_simota_gen_targets(const float* cls_logits, const float* cnt_logits, const float* reg_pred, int32_t C,
+                              const float* gt_boxes, const int64_t* labels, int32_t M, const fd_segs* segs,
+                              const int32_t* strides, int32_t top_q, float centre_radius, float iou_weight,
+                              float inside_eps, int32_t quality, int64_t* cls_target, float* cnt_target,
+                              float* reg_target, float* pair_iou, float* pair_cost, int32_t* gt_k, int32_t* gt_ncand,
+                              void* workspace, fd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------- */
 /* Anchor targets and detections (DataEncoder.encode / decode, utill/utills.py:100-199).
  *

@@ -347,6 +347,8 @@ _SIGS = {
     "fd_fcos_gen_targets": (_I, [_P, _P, _I, C.POINTER(Segs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), _F, _P, _P, _P, _P]),
     "fd_atss_workspace_bytes": (_L, [_I, _I]),
     "fd_atss_gen_targets": (_I, [_P, _P, _I, C.POINTER(Segs), C.POINTER(_I), _I, _F, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "fd_simota_workspace_bytes": (_L, [_I, _I, _I]),
+    "fd_simota_gen_targets": (_I, [_P, _P, _P, _I, _P, _P, _I, C.POINTER(Segs), C.POINTER(_I), _I, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fd_anchor_boxes": (_I, [C.POINTER(AnchorParams), _P, _I, _P]),
     "fd_anchor_encode": (_I, [C.POINTER(AnchorParams), _P, _P, _I, _I, _I, _P, _P, _P]),
     "fd_anchor_decode_workspace_bytes": (_L, [_I, _I, _I]),

@@ -10,6 +10,7 @@ import torch.nn as nn
 from ... import ops
 from ..._lib import FdError, Segs
 from ...ops import Rows
+from ..loss import flatten_levels
 
 
 def _as_pyramid(levels, nlev: int) -> Tuple[Rows, Segs]:
@@ -148,3 +149,30 @@ class ATSSGenTargets(nn.Module):
         assert len(self.stride) == len(cls_logit)
         level_hw = [(int(t.shape[2]), int(t.shape[3])) for t in cls_logit]
         return ops.atss_gen_targets(gt_box, labels, level_hw, self.stride, self.topk, self.anchor_scale, self.inside_eps)
+
+
+class SimOTAGenTargets(nn.Module):
+    """SimOTAGenTargets(strides, top_q=10, centre_radius=2.5, iou_weight=3.0, inside_eps=0.01, quality="centerness")([out,
+    gt_boxes, classes]) -> the triple of FCOSGenTargets, assigned by SimOTA (Ge et al., OTA, CVPR 2021; YOLOX): unlike
+    FCOSGenTargets and ATSSGenTargets it reads the predictions in `out` = (cls_logits, cnt_logits, reg_preds), lists of NCHW maps.
+    Per GT box the locations inside it are ranked by a cost of the current detection score sqrt(sigmoid(cls) * sigmoid(cnt)) and
+    the IoU of the currently predicted box, locations within centre_radius strides of the box centre first; the number of positives
+    is the sum of the top_q best IoUs, and a contested location goes to the cheapest box (fd_simota_gen_targets; DESIGN 4.3p states
+    the rule).  quality: cnt_target is the centre-ness ("centerness") or that IoU ("iou").  The maps are detached and read as fp32:
+    no gradient flows through the assignment."""
+
+    def __init__(self, strides: List[int], top_q: int = 10, centre_radius: float = 2.5, iou_weight: float = 3.0, inside_eps: float = 0.01,
+                 quality: str = "centerness"):
+        super().__init__()
+        self.stride, self.top_q, self.centre_radius, self.iou_weight = strides, top_q, centre_radius, iou_weight
+        self.inside_eps, self.quality = inside_eps, quality
+
+    @torch.no_grad()
+    def forward(self, x):
+        cls_logit, cnt_logit, reg_pred = x[0]
+        gt_box, labels = x[1], x[2]
+        assert len(self.stride) == len(cls_logit)
+        level_hw = [(int(t.shape[2]), int(t.shape[3])) for t in cls_logit]
+        cl, cn, rp = (flatten_levels([t.detach() for t in maps]).float() for maps in (cls_logit, cnt_logit, reg_pred))
+        return ops.simota_gen_targets(cl, cn, rp, gt_box, labels, level_hw, self.stride, self.top_q, self.centre_radius, self.iou_weight,
+                                      self.inside_eps, self.quality)

@@ -2217,6 +2217,54 @@ def atss_gen_targets(gt_boxes: torch.Tensor, labels: torch.Tensor, level_hw, str
     return (cls, cnt, reg, thr, npos) if return_stats else (cls, cnt, reg)
 
 
+SIMOTA_MAX_TOPQ, SIMOTA_MAX_GT = 16, 256      # include/fcosdet.h FD_SIMOTA_MAX_TOPQ, FD_SIMOTA_MAX_GT
+SIMOTA_QUALITY = {"centerness": 0, "iou": 1}
+
+
+def simota_gen_targets(cls_logits: torch.Tensor, cnt_logits: torch.Tensor, reg_pred: torch.Tensor, gt_boxes: torch.Tensor,
+                       labels: torch.Tensor, level_hw, strides, top_q: int = 10, centre_radius: float = 2.5, iou_weight: float = 3.0,
+                       inside_eps: float = 0.01, quality: str = "centerness", return_stats: bool = False):
+    """SimOTA assignment (fd_simota_gen_targets) on the contract of fcos_gen_targets, ranked by the current
+    predictions: cls_logits [B,L,C], cnt_logits [B,L] or [B,L,1], reg_pred [B,L,4] (l, t, r, b in pixels), all f32 in the location
+    order of level_hw; gt_boxes [B,M,4] f32, labels [B,M] int64 in 1..C (M may be 0) -> (cls [B,L,1] int64, cnt [B,L,1] f32,
+    reg [B,L,4] f32).  quality: "centerness" (cnt as fcos_gen_targets) or "iou" (cnt = the predicted box's IoU).  With
+    return_stats also pair_iou, pair_cost [B,M,L] f32 (0 / +inf for non-candidates), k and ncand [B,M] int32."""
+    _need_gpu(cls_logits, cnt_logits, reg_pred, gt_boxes, labels)
+    B, M = labels.shape
+    L = sum(h * w for h, w in level_hw)
+    if quality not in SIMOTA_QUALITY:
+        raise FdError(f"simota_gen_targets: quality must be one of {sorted(SIMOTA_QUALITY)} (got {quality!r})")
+    if (len(strides) != len(level_hw) or tuple(gt_boxes.shape) != (B, M, 4) or cls_logits.dim() != 3 or tuple(cls_logits.shape[:2]) != (B, L)
+            or cnt_logits.numel() != B * L or tuple(reg_pred.shape) != (B, L, 4)):
+        raise FdError(f"simota_gen_targets: {len(level_hw)} levels of {L} locations, {len(strides)} strides, cls_logits {tuple(cls_logits.shape)}, "
+                      f"cnt_logits {tuple(cnt_logits.shape)}, reg_pred {tuple(reg_pred.shape)}, gt_boxes {tuple(gt_boxes.shape)}, labels {tuple(labels.shape)}")
+    for t in (cls_logits, cnt_logits, reg_pred):
+        if t.dtype != torch.float32:
+            raise FdError(f"simota_gen_targets: predictions must be float32 (got {t.dtype})")
+    Cn = int(cls_logits.shape[2])
+    segs = Segs.make(B, list(level_hw))
+    dev = gt_boxes.device
+    cls = torch.empty(B, L, 1, dtype=torch.int64, device=dev)
+    cnt = torch.empty(B, L, 1, dtype=torch.float32, device=dev)
+    reg = torch.empty(B, L, 4, dtype=torch.float32, device=dev)
+    stats = None
+    if return_stats:
+        stats = (torch.empty(B, M, L, dtype=torch.float32, device=dev), torch.empty(B, M, L, dtype=torch.float32, device=dev),
+                 torch.empty(B, M, dtype=torch.int32, device=dev), torch.empty(B, M, dtype=torch.int32, device=dev))
+    ws = torch.empty(max(_lib.lib().fd_simota_workspace_bytes(B, M, L), 8) // 8, dtype=torch.int64, device=dev)
+    n = len(level_hw)
+    st = (C.c_int32 * n)(*[int(s) for s in strides])
+    cl, cn, rp = cls_logits.detach().contiguous(), cnt_logits.detach().contiguous(), reg_pred.detach().contiguous()
+    gb = gt_boxes.contiguous().float()
+    lb = labels.contiguous().to(torch.int64)
+    sp = [t.data_ptr() if M else None for t in stats] if return_stats else [None] * 4
+    check(_lib.lib().fd_simota_gen_targets(cl.data_ptr(), cn.data_ptr(), rp.data_ptr(), Cn, gb.data_ptr() if M else None,
+                                           lb.data_ptr() if M else None, M, C.byref(segs), st, int(top_q), float(centre_radius),
+                                           float(iou_weight), float(inside_eps), SIMOTA_QUALITY[quality], cls.data_ptr(), cnt.data_ptr(),
+                                           reg.data_ptr(), sp[0], sp[1], sp[2], sp[3], ws.data_ptr(), _stream()), "fd_simota_gen_targets")
+    return (cls, cnt, reg) + stats if return_stats else (cls, cnt, reg)
+
+
 # ---------------------------------------------------------------------------------------------------- anchors (DataEncoder)
 ANCHOR_LEVELS, ANCHOR_PER_CELL = 5, 9
 
