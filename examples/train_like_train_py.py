@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The reference's train.py:97-181 loop on the MI355X path, with synthetic VOC-shaped batches.
 
-    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-bn-f16] [--hip-optim] [--ema 0.999] [--update-bn 8] [--assigner atss|simota]
+    python examples/train_like_train_py.py [--steps 20] [--amp] [--model MNFCOS] [--hip-stem] [--hip-bn-f16] [--hip-optim] [--ema 0.999] [--update-bn 8] [--assigner atss|simota] [--cls-loss qfl|vfl]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 examples/train_like_train_py.py   # DDP / RCCL
 
 Same objects and call order as the reference: HalfInvertedStageFCOS([512, 1024, 2048], 20, 256), FCOSGenTargets,
@@ -23,6 +23,8 @@ statistics, and its FPN BatchNorms run on batch statistics; update_bn recomputes
 DDP: the statistics are global) and leaves the frozen backbone's alone.  --assigner atss replaces the one line train.py:98 by ATSSGenTargets(strides):
 Adaptive Training Sample Selection on the device (fd_atss_gen_targets) instead of the scale ranges and the centre radius; --assigner simota by SimOTAGenTargets(strides): SimOTA on the device (fd_simota_gen_targets),
 which ranks the locations inside a box by the score and the box the model currently predicts there; nothing else changes.
+--cls-loss qfl | vfl replaces the hard-label focal term by Quality Focal Loss or Varifocal Loss (FCOSLoss('giou', cls_mode=...), fd_quality_loss_fwd / _bwd):
+the losses GFL and VarifocalNet train with, e.g. `--assigner simota --cls-loss qfl`.
 """
 import argparse
 import os
@@ -54,6 +56,8 @@ def main():
                     help="recompute the averaged copy's batch-statistics BatchNorms over N batches before its eval forward (optim.update_bn); needs --ema")
     ap.add_argument("--assigner", choices=["fcos", "atss", "simota"], default="fcos",
                     help="target assignment: FCOSGenTargets (train.py:98), ATSSGenTargets or SimOTAGenTargets")
+    ap.add_argument("--cls-loss", choices=["focal", "qfl", "vfl"], default="focal",
+                    help="classification term: the reference's focal loss, Quality Focal Loss or Varifocal Loss (e.g. --assigner simota --cls-loss qfl)")
     args = ap.parse_args()
     if args.ema is not None and not args.hip_optim:
         ap.error("--ema gates on the HIP optimizer's skip flag: pass --hip-optim as well")
@@ -96,7 +100,7 @@ def main():
     # train.py:125 (commented out there): the averaged copy; pairs by position, so the DDP wrapper's parameters pair with the bare copy's
     avg = optim.AveragedModel(model.module if world > 1 else model, decay=args.ema, optimizer=optimizer) if args.ema is not None else None
     scaler = torch.amp.GradScaler("cuda", enabled=args.amp)                                         # train.py:133
-    criterion = FCOSLoss("giou")
+    criterion = FCOSLoss("giou", cls_mode=args.cls_loss)       # "qfl" / "vfl": the class target of a positive is the IoU of its current box prediction
 
     g = torch.Generator(device=dev).manual_seed(100 + rank)      # synthetic batches are drawn on the device (no dataloader here)
     model.train()

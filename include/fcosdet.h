@@ -1048,6 +1048,30 @@ int32_t fd_focal_loss_fwd(const float* logits, const int64_t* labels, int32_t B,
 int32_t fd_focal_loss_bwd(const float* logits, const int64_t* labels, const float* gscale, int32_t B, int32_t L, int32_t C,
                           float alpha, float gamma, float* grad_logits, fd_stream_t stream);
 
+/* IoU-aware classification losses from logits (the project's own definitions): Quality Focal Loss (kind 0,
+ * beta = 2; alpha ignored) and Varifocal Loss (kind 1, gamma = 2, alpha 0.75 as published).  With s = sigmoid(x),
+ * bce(x, y) = max(x, 0) - x*y + log1p(exp(-|x|)) and the soft target y = q[b][l] where labels[b][l] == c + 1, else 0:
+ *   QFL   (y - s)^2 * bce(x, y)
+ *   VFL   y * bce(x, y) where y > 0, alpha * s^2 * bce(x, 0) elsewhere
+ * fd_ltrb_quality: q_out [B][L] = 0 where labels <= 0, else iou of pred / target [B][L][4] (LTRB distances, 16-byte
+ * aligned) exactly as the LTRB loss computes it, then (iou > 0) ? min(iou, 1) : 0 (NaN and negative values give 0).
+ * q is a target: the backward has no gradient for it; a caller may pass any q [B][L] of its own instead.
+ * fd_quality_loss_fwd: logits [B][L][C], labels [B][L] int64 (a label outside 1..C matches no class) ->
+ * loss_per_image [B] = sum over [L][C], qsum_per_image [B] = sum over [L] of q; both summed in doubles in a fixed order
+ * (no atomics: equal inputs give equal bits).  Two launches.  workspace: fd_quality_loss_workspace_bytes(B) bytes,
+ * 8-byte aligned; it may hold anything.  fd_quality_loss_bwd: grad_logits [B][L][C] = dloss_b/dlogits * gscale[b], one
+ * launch.  Rows are read in 16-, 8- or 4-byte pieces as C and the alignment of logits / grad_logits allow.  B <= 65535.
+ * beta / gamma other than 2: FD_E_UNSUPPORTED; other bad arguments: FD_E_INVAL; nothing is enqueued on a refusal. */
+int32_t fd_ltrb_quality(const float* pred, const float* target, const int64_t* labels, int32_t B, int32_t L, float* q_out,
+                        fd_stream_t stream);
+int64_t fd_quality_loss_workspace_bytes(int32_t B);
+int32_t fd_quality_loss_fwd(const float* logits, const int64_t* labels, const float* q, int32_t B, int32_t L, int32_t C,
+                            int32_t kind, float alpha, float gamma, float* loss_per_image, float* qsum_per_image,
+                            void* workspace, fd_stream_t stream);
+int32_t fd_quality_loss_bwd(const float* logits, const int64_t* labels, const float* q, const float* gscale, int32_t B,
+                            int32_t L, int32_t C, int32_t kind, float alpha, float gamma, float* grad_logits,
+                            fd_stream_t stream);
+
 /* Centerness loss: binary_cross_entropy_with_logits(reduction='sum') over positives (model/loss.py:31-57).
  * x / target / mask [B][L]; loss_per_image [B] (sum), num_pos [B]; backward grad [B][L] = (sigmoid(x)-t)*gscale[b]. */
 int32_t fd_bce_logits_loss_fwd(const float* x, const float* target, const uint8_t* mask, int32_t B, int32_t L,

@@ -337,6 +337,10 @@ _SIGS = {
     "fd_focal_workspace_bytes": (_L, [_I]),
     "fd_focal_loss_fwd": (_I, [_P, _P, _I, _I, _I, _F, _F, _P, _P, _P]),
     "fd_focal_loss_bwd": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _P, _P]),
+    "fd_ltrb_quality": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "fd_quality_loss_workspace_bytes": (_L, [_I]),
+    "fd_quality_loss_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P]),
+    "fd_quality_loss_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P]),
     "fd_bce_logits_loss_fwd": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "fd_bce_logits_loss_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "fd_eval_ap_workspace_bytes": (_L, [_I, _I, _I, _I, _I]),

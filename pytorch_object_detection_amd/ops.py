@@ -2146,6 +2146,73 @@ def focal_loss_bwd(logits, labels, gscale, alpha: float = 0.25, gamma: float = 2
     return grad
 
 
+QUALITY_KIND = {"qfl": 0, "vfl": 1}      # include/fcosdet.h fd_quality_loss_fwd `kind`
+
+
+def _quality_kind(kind, who: str) -> int:
+    if kind in QUALITY_KIND:
+        return QUALITY_KIND[kind]
+    if kind in (0, 1) and not isinstance(kind, bool):
+        return int(kind)
+    raise FdError(f"{who}: kind must be one of {sorted(QUALITY_KIND)} (got {kind!r})")
+
+
+def _quality_check(who: str, logits, labels, q) -> None:
+    if logits.dim() != 3 or tuple(labels.shape) != tuple(logits.shape[:2]) or tuple(q.shape) != tuple(logits.shape[:2]):
+        raise FdError(f"{who}: logits {tuple(logits.shape)}, labels {tuple(labels.shape)}, q {tuple(q.shape)}: expected [B,L,C], [B,L], [B,L]")
+    if logits.dtype != torch.float32 or q.dtype != torch.float32 or labels.dtype != torch.int64:
+        raise FdError(f"{who}: logits and q must be float32 and labels int64 (got {logits.dtype}, {q.dtype}, {labels.dtype})")
+    if not (logits.is_contiguous() and labels.is_contiguous() and q.is_contiguous()):
+        raise FdError(f"{who}: logits, labels and q must be contiguous")
+
+
+def ltrb_quality(reg_pred: torch.Tensor, reg_target: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """The soft classification target (fd_ltrb_quality): reg_pred / reg_target [B,L,4] f32 LTRB distances, labels
+    [B,L] or [B,L,1] int64 -> q [B,L] f32: 0 where labels <= 0, else the pair's IoU as the LTRB loss computes it, in [0, 1]
+    (NaN gives 0).  No gradient: q is a target."""
+    _need_gpu(reg_pred, reg_target, labels)
+    if reg_pred.dim() != 3 or reg_pred.shape[2] != 4 or reg_target.shape != reg_pred.shape or labels.numel() != reg_pred.shape[0] * reg_pred.shape[1]:
+        raise FdError(f"ltrb_quality: reg_pred {tuple(reg_pred.shape)}, reg_target {tuple(reg_target.shape)}, labels {tuple(labels.shape)}: "
+                      "expected [B,L,4], [B,L,4], [B,L]")
+    if reg_pred.dtype != torch.float32 or reg_target.dtype != torch.float32 or labels.dtype != torch.int64:
+        raise FdError(f"ltrb_quality: boxes must be float32 and labels int64 (got {reg_pred.dtype}, {reg_target.dtype}, {labels.dtype})")
+    B, L, _ = reg_pred.shape
+    rp, rt, lb = reg_pred.detach().contiguous(), reg_target.detach().contiguous(), labels.contiguous()
+    q = torch.empty(B, L, dtype=torch.float32, device=reg_pred.device)
+    check(_lib.lib().fd_ltrb_quality(rp.data_ptr(), rt.data_ptr(), lb.data_ptr(), B, L, q.data_ptr(), _stream()), "fd_ltrb_quality")
+    return q
+
+
+def quality_loss_fwd(logits: torch.Tensor, labels: torch.Tensor, q: torch.Tensor, kind, alpha: float = 0.75, gamma: float = 2.0):
+    """QFL (kind "qfl") or VFL ("vfl") summed per image (fd_quality_loss_fwd): logits [B,L,C] f32, labels [B,L] int64,
+    q [B,L] f32, all contiguous -> (loss [B] f32, qsum [B] f32 = sum of q), both summed in doubles in a fixed order."""
+    _need_gpu(logits, labels, q)
+    k = _quality_kind(kind, "quality_loss_fwd")
+    _quality_check("quality_loss_fwd", logits, labels, q)
+    B, L, Cn = logits.shape
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    qsum = torch.empty(B, dtype=torch.float32, device=logits.device)
+    ws = torch.empty(max(_lib.lib().fd_quality_loss_workspace_bytes(B), 8) // 8, dtype=torch.float64, device=logits.device)
+    check(_lib.lib().fd_quality_loss_fwd(logits.data_ptr(), labels.data_ptr(), q.data_ptr(), B, L, Cn, k, float(alpha), float(gamma),
+                                         loss.data_ptr(), qsum.data_ptr(), ws.data_ptr(), _stream()), "fd_quality_loss_fwd")
+    return loss, qsum
+
+
+def quality_loss_bwd(logits: torch.Tensor, labels: torch.Tensor, q: torch.Tensor, gscale: torch.Tensor, kind, alpha: float = 0.75,
+                     gamma: float = 2.0) -> torch.Tensor:
+    """grad [B,L,C] = d loss_b / d logits * gscale[b] of quality_loss_fwd (fd_quality_loss_bwd); gscale [B] f32."""
+    _need_gpu(logits, labels, q, gscale)
+    k = _quality_kind(kind, "quality_loss_bwd")
+    _quality_check("quality_loss_bwd", logits, labels, q)
+    B, L, Cn = logits.shape
+    if tuple(gscale.shape) != (B,) or gscale.dtype != torch.float32 or not gscale.is_contiguous():
+        raise FdError(f"quality_loss_bwd: gscale must be contiguous float32 [{B}] (got {gscale.dtype} {tuple(gscale.shape)})")
+    grad = torch.empty_like(logits)
+    check(_lib.lib().fd_quality_loss_bwd(logits.data_ptr(), labels.data_ptr(), q.data_ptr(), gscale.data_ptr(), B, L, Cn, k, float(alpha),
+                                         float(gamma), grad.data_ptr(), _stream()), "fd_quality_loss_bwd")
+    return grad
+
+
 def bce_loss_fwd(x: torch.Tensor, target: torch.Tensor, mask: torch.Tensor):
     _need_gpu(x, target, mask)
     B, L = x.shape
